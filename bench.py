@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched forward NTT on the reference's benchmark ring R15, plus the CKKS / BFV caller sequences.
 
-    python bench.py --gpus N --steps K --warmup W [--workload ntt|ckks16]
+    python bench.py --gpus N --steps K --warmup W [--workload ntt|ckks16] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step if --dump-outputs is given, and prints the
+result line.  Everything else the line can carry (oracle checks, CPU baselines, the other operations, rings, parameter sets and
+legs, power, counters, `summary`) runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the last step computed (the batch the caller of the timed path receives) goes to
+DIR as float64 .npy files: <name>.npy holds the uint64 words as doubles (rounded to 53 bits), <name>_hi32.npy and <name>_lo32.npy
+their exact upper and lower halves.  An output of more than 2^20 words is sampled at a fixed, seeded set of positions
+(dump_sample_index); the inputs are seeded, so two builds given the same arguments can be compared output for output.
 
 Workload "ntt" (default; BASELINE.json metric "NTT/s ... at N=2^15, L=16"): ring.DefaultParamsQi[15]
 (ring/params.go:14: N = 2^15, 16 x 60-bit limbs), a batch of B uniform polynomials resident in HBM
@@ -14,18 +23,18 @@ Workload "ckks16" (BASELINE.json config 5): independent CKKS MulRelin at Default
 limbs, ckks/params.go:78-86), --config5-units ciphertext products per GPU (128 = config 5's share of one GPU of eight), each rank
 on its contiguous block, then ONE gather of the results to rank 0 (torch.distributed.gather on the nccl backend = RCCL
 send/recv over xGMI; lattigo-fhe-by-go_amd/sharding.py).  One step = the whole block + the gather; compute-only and
-compute+gather times are reported separately.  The default run carries this leg as the `config5` object.
+compute+gather times are reported separately.  A --full run of workload ntt carries this leg as the `config5` object.
 
 Prints one JSON line (rank 0).  `value` = units per second over all GPUs; `roofline.achieved` = algorithmic bytes
  / device time measured with HIP events on the launch stream inside this run; `roofline.kernel` is the
-kernel the library reports it dispatched.  `roofline.traffic` (HBM bytes per launch, and per product on the MulRelin leg) is counted in
-the run at N = 1: PMC counters need their own rocprofv3 passes, so four short child runs of `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE, one
+kernel the library reports it dispatched; `bit_exact` (the oracle spot-check) is null unless --full.  `roofline.traffic` (HBM bytes per
+launch, and per product on the MulRelin leg) is counted by a --full run at N = 1: PMC counters need their own rocprofv3 passes, so four short child runs of `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE, one
 counter each) execute the same kernel / pipeline on the same shape at the end; null with the reason in `traffic_source` if the profiler
 cannot run (--no-traffic skips it; tools/collect_profiles.sh writes the committed figures named in `traffic_profile`).  `cpu_baseline` objects time the CPU oracle
 (C restatement of the Go algorithm, rebuilt -O2 -march=native on this machine; Go itself is not installable here) on the
 host cores, rank 0 at N=1 only, on bounded samples.
 
-Beside the headline the line carries (N = 1): `extras` / `rings` / `mulrelin_sets` (the other ring operations and sizes), `ckks_mulrelin`, `bfv_mul`
+With --full, beside the headline the line carries (N = 1): `extras` / `rings` / `mulrelin_sets` (the other ring operations and sizes), `ckks_mulrelin`, `bfv_mul`
 (BASELINE config 4) and `pipelines` -- one timed call per entry point of the reference's ring, ckks-evaluator and bfv-evaluator benchmark lists
 (tools/bench_legs.py), each with roofline, in-run traffic, vector issue, kernel split, bit_exact and cpu_baseline --, `evaluator_threads`,
 `evaluator_threads_bfv` (one evaluator per host thread, direct and through the batchers, Python threads), `evaluator_threads_native` (the same
@@ -62,6 +71,29 @@ def mulrelin_bytes(N, nq, np_, products=1):
     evaluation key beta*2*(nq+np) limbs, the output ciphertext 2*nq limbs; PN15QP880: 8N*360 per product."""
     beta = -(-nq // np_)
     return 8 * N * (4 * nq + beta * 2 * (nq + np_) + 2 * nq) * products
+
+
+DUMP_WORDS = 1 << 20    # words per dumped array: three float64 arrays of 8 MiB, well under the 64 MB the dump may take
+
+
+def dump_sample_index(total):
+    """The positions of a flat output of `total` words that --dump-outputs writes: all of them up to DUMP_WORDS, else a fixed, seeded,
+    sorted sample of DUMP_WORDS positions (the same for every run of the same shape)."""
+    import numpy as np
+    if total <= DUMP_WORDS:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(0x5EED).integers(0, total, DUMP_WORDS, dtype=np.int64))
+
+
+def dump_words(out_dir, name, words):
+    """--dump-outputs: uint64 words (already sampled) -> out_dir/<name>.npy (the words as float64, rounded to 53 bits) and
+    <name>_hi32.npy / <name>_lo32.npy (their exact 32-bit halves as float64)."""
+    import numpy as np
+    w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), w.astype(np.float64))
+    np.save(os.path.join(out_dir, name + "_hi32.npy"), (w >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(out_dir, name + "_lo32.npy"), (w & np.uint64(0xFFFFFFFF)).astype(np.float64))
 
 
 def dist_env():
@@ -564,6 +596,10 @@ def main():
     ap.add_argument("--config5-chunk", type=int, default=32, help="products per lr_ckks_mulrelin call")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1 and no launcher: print the child command as JSON and exit")
     ap.add_argument("--launch-check", action="store_true", help="ranks only rendezvous over gloo and print one line (CPU rehearsal of the self-launch path)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: oracle checks, CPU baselines, the other operations, "
+                    "rings, parameter sets and legs, power and counters (the --no-* switches select among them); off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed to DIR/<name>.npy "
+                    "(float64; outputs over 2^20 words sampled at fixed, seeded positions)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -629,7 +665,7 @@ def main():
     ring, params, sampling, sharding, nat = pkg.ring, pkg.params, pkg.sampling, pkg.sharding, pkg._native
     sync = torch.cuda.synchronize
     oracle = graft.load_oracle() if rank == 0 else None
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     if want_cpu:
         oracle.use_native()
 
@@ -708,7 +744,7 @@ def main():
             root_out = torch.empty((total, 2, nq, cN), dtype=torch.int64, device="cuda") if overlapped and rank == 0 else None
         return dict(cN=cN, cQm=cQm, cPm=cPm, nq=nq, np_=np_, level=level, beta=beta, per_gpu=per_gpu, total=total, start=start, count=count,
                     chunk=chunk, cQ=cQ, cP=cP, st=st, plan=plan, evk_h=evk_h, evk=evk, dev_in=dev_in, dev_out=dev_out, calls=calls,
-                    spans=spans, overlapped=overlapped, root_out=root_out)
+                    spans=spans, overlapped=overlapped, root_out=root_out, result=None)
 
     def config5_run(c, steps, warmup):
         cN, cQm, cPm, nq, np_, level, beta = c["cN"], c["cQm"], c["cPm"], c["nq"], c["np_"], c["level"], c["beta"]
@@ -748,6 +784,7 @@ def main():
         step()
         sync()
         barrier()
+        c["result"] = gathered[0] if gathered[0] is not None else dev_out
         res = {
             "value": total * steps / seconds, "unit": "MulRelin/s", "params": "PN16QP1761 (N=2^16, %d Q + %d P limbs, beta=%d), level %d" % (nq, np_, beta, level),
             "units_total": total, "units_per_gpu": c["per_gpu"], "chunk": chunk, "n_gpus": world,
@@ -789,11 +826,17 @@ def main():
         return res
 
     if args.workload == "ckks16":
-        c5 = config5_run(config5_prepare(), max(1, min(args.steps, 10)), max(1, min(args.warmup, 2)))
+        c5_state = config5_prepare()
+        c5 = config5_run(c5_state, args.steps, args.warmup)
+        if rank == 0 and args.dump_outputs:
+            # the products of the last step as rank 0 holds them after the gather: [units, 2, limbs, N] words
+            res_t = c5_state["result"].reshape(-1)
+            idx = dump_sample_index(res_t.numel())
+            dump_words(args.dump_outputs, "mulrelin_out", res_t[torch.from_numpy(idx).to(res_t.device)].cpu().numpy().view(np.uint64))
+        del c5_state
         if rank == 0:
-            steps = max(1, min(args.steps, 10))
             out = {"metric": "CKKS homomorphic-mul/s at N=2^16 (MulRelin, DefaultParams[PN16QP1761]), sharded batch + gather to rank 0",
-                   "value": c5["value"], "unit": "MulRelin/s", "n_gpus": world, "steps": steps, "warmup": max(1, min(args.warmup, 2)),
+                   "value": c5["value"], "unit": "MulRelin/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                    "ms_per_step": c5["ms_per_step_compute_and_gather"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                    "dtype": "u64", "data": "synthetic",
                    "config": {"workload": "BASELINE config 5: %d independent CKKS MulRelin per GPU at PN16QP1761, contiguous blocks, RCCL gather" % args.config5_units,
@@ -967,12 +1010,15 @@ def main():
     kernel_ms = dev_ms / args.steps
     kernel_name = ctx.last_ntt_kernel()
     progress("headline NTT timed: %.4f ms per launch, kernel %s" % (kernel_ms, kernel_name))
+    if rank == 0 and args.dump_outputs:
+        # this rank's transformed batch after the last timed step: [polys, limbs, N] words (the later legs of --full overwrite dst)
+        dump_words(args.dump_outputs, "ntt_out", dst.get().reshape(-1)[dump_sample_index(my_polys * L * N)])
 
-    power = sample_power(step, ctx.Sync) if (rank == 0 and world == 1 and not args.no_traffic) else None
-    # parity spot-check inside the bench: first and last poly against the oracle (checker only)
+    power = sample_power(step, ctx.Sync) if (args.full and rank == 0 and world == 1 and not args.no_traffic) else None
+    # parity spot-check inside the bench: first and last poly against the oracle (checker only; --full)
     bit_exact = None
     oc = None
-    if rank == 0:
+    if rank == 0 and args.full:
         oc = oracle.Context(N, moduli)
         full = dst.get().reshape(my_polys, L, N)
         bit_exact = bool(np.array_equal(full[0], oc.ntt(base[0])) and
@@ -1009,6 +1055,14 @@ def main():
                      # the north star says "HBM-read roofline"; `achieved` counts read + write, this is the read half
                      "achieved_read_only": achieved / 2},
     }
+    if not args.full:
+        # a plain run ends with the headline: no checks, baselines or other legs
+        if rank == 0:
+            emit(out)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     def timed_on(c, fn, reps):
         # the CPU baselines before a leg leave the device idle for seconds: bring its clock up first (see warm_clock; three launches were

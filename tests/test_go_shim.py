@@ -1,17 +1,30 @@
 """The Go shim (go/ring) cannot be compiled here (no Go toolchain in the image).  These checks keep it honest without a
 compiler: every C symbol it calls is declared in include/lattigo_ring.h with the same number of arguments, its braces and
 parentheses balance, and the exported-identifier checklist (go/ring/SURFACE.md) is complete and current."""
+import json
 import os
 import re
 import subprocess
 import sys
 
-import pytest
-
 from conftest import ROOT
 
 GO_DIR = os.path.join(ROOT, "go", "ring")
 OVERLAYS = {"ckks": os.path.join(ROOT, "go", "ckks", "evaluator_device.go"), "bfv": os.path.join(ROOT, "go", "bfv", "evaluator_device.go")}
+# names and parameter types read from the reference module (v1.3.1) by tests/golden/make_reference_go_names.py
+REFERENCE_NAMES = os.path.join(ROOT, "tests", "golden", "reference_go_names.json")
+# the unexported upstream identifiers the overlays lean on (fields, helpers)
+UPSTREAM_IDENTIFIERS = {
+    "ckks": ["getElemAndCheckBinary", "ckksContext", "contextQ", "contextP", "evakeyRotColLeft", "baseconverter", "permuteNTTLeftIndex",
+             "DropLevel", "logN", "poolQ[", "Resize(", "DivScale("],
+    "bfv": ["getElemAndCheckBinary", "bfvContext", "contextQMul", "keyswitchpool", "SetValue(", "evakey.evakey", "baseconverterQ1P",
+            "tensorAndRescale("],
+}
+
+
+def _reference_names():
+    with open(REFERENCE_NAMES) as f:
+        return json.load(f)
 
 
 def _go_sources():
@@ -104,9 +117,9 @@ def test_status_constants_exist_in_header():
             assert re.search(r"\b%s\b" % m.group(1), text), (name, m.group(1))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/ring"), reason="the reference tree exists only in the build container")
 def test_surface_checklist_is_complete_and_current():
-    rc = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "go_surface.py"), "--check"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    rc = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "go_surface.py"), "--names", REFERENCE_NAMES, "--check"],
+                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert rc.returncode == 0, rc.stdout.decode()
     text = open(os.path.join(GO_DIR, "SURFACE.md")).read()
     assert "MISSING" not in text
@@ -185,24 +198,27 @@ def test_evaluator_overlays_use_only_what_the_shim_exports():
         assert re.search(r"delete\s+%s\b" % meth, bf), meth
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/ckks"), reason="the reference tree exists only in the build container")
+def evaluator_signatures(text):
+    """{method: [parameter types, results]} of the methods declared on *evaluator in Go source text"""
+    out = {}
+    for m in re.finditer(r"func \(\w+ \*evaluator\) (\w+)\(([^)]*)\)([^{]*)\{", text):
+        params = re.sub(r"\s+", " ", m.group(2)).strip()
+        types = [re.sub(r"^\w+ ", "", g.strip()) if " " in g.strip() else None for g in _split_args(params)] if params else []
+        # names without a type take the type of the next typed parameter
+        for i in range(len(types) - 2, -1, -1):
+            if types[i] is None:
+                types[i] = types[i + 1]
+        out[m.group(1)] = [types, re.sub(r"\s+", " ", m.group(3)).strip()]
+    return out
+
+
 def test_replacement_bodies_keep_the_upstream_signatures():
     """every method the overlays define on *evaluator under an upstream name has the upstream parameter list, so upstream callers
     (polynomial_evaluation.go, the ...New wrappers, rotateColumnsPow2) compile against it unchanged"""
-    def sigs(text):
-        out = {}
-        for m in re.finditer(r"func \(\w+ \*evaluator\) (\w+)\(([^)]*)\)([^{]*)\{", text):
-            params = re.sub(r"\s+", " ", m.group(2)).strip()
-            types = [re.sub(r"^\w+ ", "", g.strip()) if " " in g.strip() else None for g in _split_args(params)] if params else []
-            # names without a type take the type of the next typed parameter
-            for i in range(len(types) - 2, -1, -1):
-                if types[i] is None:
-                    types[i] = types[i + 1]
-            out[m.group(1)] = (types, re.sub(r"\s+", " ", m.group(3)).strip())
-        return out
+    ref = _reference_names()["evaluator_signatures"]
     for pkg in ("ckks", "bfv"):
-        up = sigs(open(os.path.join("/root/reference", pkg, "evaluator.go")).read())
-        mine = sigs(open(OVERLAYS[pkg]).read())
+        up = ref[pkg]
+        mine = evaluator_signatures(open(OVERLAYS[pkg]).read())
         helpers = {"dev", "keyImage", "resident", "hostLoop", "galoisElement", "halfScalar", "batcher", "ReleaseDevice"}
         for name, (types, ret) in mine.items():
             if name in helpers:
@@ -214,16 +230,11 @@ def test_replacement_bodies_keep_the_upstream_signatures():
             assert strip_names(ret) == strip_names(up[name][1]), (pkg, name, ret, up[name][1])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/ckks"), reason="the reference tree exists only in the build container")
 def test_overlays_name_upstream_identifiers_that_exist():
     """every unexported upstream identifier the overlays lean on (fields, helpers) exists in the reference's package sources"""
-    for pkg, idents in (("ckks", ["getElemAndCheckBinary", "ckksContext", "contextQ", "contextP", "evakeyRotColLeft", "baseconverter",
-                                  "permuteNTTLeftIndex", "DropLevel", "logN", "poolQ[", "Resize(", "DivScale("]),
-                        ("bfv", ["getElemAndCheckBinary", "bfvContext", "contextQMul", "keyswitchpool", "SetValue(", "evakey.evakey",
-                                 "baseconverterQ1P", "tensorAndRescale("])):
-        src = "\n".join(open(os.path.join("/root/reference", pkg, f)).read() for f in os.listdir(os.path.join("/root/reference", pkg))
-                        if f.endswith(".go") and not f.endswith("_test.go"))
+    found = _reference_names()["upstream_identifiers_found"]
+    for pkg, idents in UPSTREAM_IDENTIFIERS.items():
         overlay = open(OVERLAYS[pkg]).read()
         for ident in idents:
             assert ident in overlay, (pkg, ident, "no longer used by the overlay")
-            assert ident in src, (pkg, ident, "not in the reference package")
+            assert ident in found[pkg], (pkg, ident, "not in the reference package")

@@ -13,8 +13,45 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def test_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """without --full the run times the headline and nothing else; --dump-outputs writes the last step's transform, which is the NTT of
+    the seeded inputs at every dumped position"""
+    import numpy as np
+
+    import __graft_entry__ as graft
+    import bench
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["unit"] == "limb-NTT/s" and d["dtype"] == "u64" and d["higher_is_better"] is True
+    units = d["config"]["polys_per_gpu"] * d["config"]["limbs"]
+    assert abs(d["value"] - units / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["roofline"]["kernel"] == "lr_ntt_fwd15_m1" and d["roofline"]["traffic"] is None and d["bit_exact"] is None
+    for key in ("cpu_baseline", "extras", "ckks_mulrelin", "pipelines", "rings", "config5", "summary"):
+        assert key not in d, key
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["ntt_out.npy", "ntt_out_hi32.npy", "ntt_out_lo32.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 * 10**6
+    hi, lo, val = (np.load(tmp_path / f) for f in ("ntt_out_hi32.npy", "ntt_out_lo32.npy", "ntt_out.npy"))
+    assert hi.dtype == lo.dtype == val.dtype == np.float64
+    words = hi.astype(np.uint64) << np.uint64(32) | lo.astype(np.uint64)
+    assert np.array_equal(val, words.astype(np.float64))
+    # the same seeded operands bench.py tiles over the batch, transformed by the oracle
+    pkg, oracle = graft.load_package(), graft.load_oracle()
+    N, moduli = pkg.params.DefaultParamsQi(15)
+    L, B = len(moduli), d["config"]["polys_per_gpu"]
+    base = pkg.sampling.uniform_poly(moduli, N, min(B, 8), seed=0x4C415454)
+    oc = oracle.Context(N, moduli)
+    want = np.stack([oc.ntt(base[i]) for i in range(base.shape[0])])
+    poly, rest = np.divmod(bench.dump_sample_index(B * L * N), L * N)
+    assert np.array_equal(words, want.reshape(base.shape[0], L * N)[poly % base.shape[0], rest])
+
+
 def test_one_json_line_with_roofline_and_cpu_baseline():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-config5", "--no-rings", "--no-extras", "--no-ckks"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-config5", "--no-rings", "--no-extras", "--no-ckks"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -55,7 +92,7 @@ def test_every_benchmarked_pipeline_has_a_roofline_and_a_cpu_baseline():
     """every pipeline entry point the reference benchmarks carries `roofline` (in-run traffic, bound, vector issue, kernel
     split) and `cpu_baseline` in the line, bfv_mul (BASELINE config 4) included; the short `summary` object is the LAST key (it survives a
     tail of the line) and the headline roofline carries `floor` and `companions`"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-config5", "--no-rings", "--no-extras", "--no-threads"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-config5", "--no-rings", "--no-extras", "--no-threads"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -92,7 +129,7 @@ def test_every_benchmarked_pipeline_has_a_roofline_and_a_cpu_baseline():
 
 
 def test_secondary_legs_carry_their_roofs_and_the_rescale_leg():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-config5", "--no-rings", "--no-ckks", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-config5", "--no-rings", "--no-ckks", "--no-cpu-baseline"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.strip()][-1])

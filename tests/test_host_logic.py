@@ -40,6 +40,24 @@ def test_algorithmic_bytes():
     assert bench.ntt_bytes(1 << 15, 16) == 8 << 20
 
 
+def test_dump_outputs_sample_and_encoding(tmp_path):
+    # --dump-outputs: a small output is written whole, a large one at the same seeded positions every time, within the size bound
+    assert np.array_equal(bench.dump_sample_index(1000), np.arange(1000))
+    big = 256 * 16 * (1 << 15)
+    idx = bench.dump_sample_index(big)
+    assert idx.size == bench.DUMP_WORDS and np.array_equal(idx, bench.dump_sample_index(big))
+    assert np.all(np.diff(idx) >= 0) and idx[0] >= 0 and idx[-1] < big
+    # the words survive exactly in the hi32 / lo32 halves; the float64 copy is the same value rounded to 53 bits
+    w = np.array([0, 1, (1 << 32) - 1, 1 << 32, 1152921504606584833, (1 << 64) - 1], dtype=np.uint64)
+    bench.dump_words(str(tmp_path), "x", w)
+    got = {n: np.load(tmp_path / ("x%s.npy" % n)) for n in ("", "_hi32", "_lo32")}
+    assert all(a.dtype == np.float64 and a.shape == w.shape for a in got.values())
+    back = got["_hi32"].astype(np.uint64) << np.uint64(32) | got["_lo32"].astype(np.uint64)
+    assert np.array_equal(back, w)
+    assert np.array_equal(got[""], w.astype(np.float64))
+    assert 3 * bench.DUMP_WORDS * 8 <= 64 * 10**6
+
+
 def test_precompute_under_sanitizers(tmp_path):
     """the host-side table generation (constants, primitive roots with the reference's factorisation quirks, psi tables,
     basis-extension tables) compiled with AddressSanitizer + UndefinedBehaviorSanitizer and run on the CPU"""

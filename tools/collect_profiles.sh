@@ -5,10 +5,11 @@
 #   per-phase timeline of the headline kernel.  The traced bench runs with --no-traffic: bench.py's own rocprofv3 --pmc child passes are
 #   not nested inside the outer profiler (the PMC passes are collected separately below and by tools/collect_r03_pmc.sh).  Output: gpurun_out/prof_r03/* (copy what is to be judged into profiles/r03/).
 set -e
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/prof_r03
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 /root/repo/bench.py --no-cpu-baseline --no-traffic --no-threads --steps 50 --warmup 5 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-traffic --no-threads --steps 50 --warmup 5 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 cp $OUT/trace/*kernel_stats.csv $OUT/kernel_stats.csv
 echo "bench trace done"
 for c in FETCH_SIZE WRITE_SIZE; do

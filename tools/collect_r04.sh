@@ -1,16 +1,17 @@
 #!/bin/bash
 # Collects round 4's rocprofv3 evidence on the GPU box (through gpurun); output: gpurun_out/prof_r04/* (copy what is to be judged into profiles/r04/).
-#   1. the default bench line (its own --pmc child passes fill every roofline object: headline, extras, MulRelin, the pipeline legs)
+#   1. the --full bench line (its own --pmc child passes fill every roofline object: headline, extras, MulRelin, the pipeline legs)
 #   2. kernel-trace statistics of the same command (--no-traffic: no profiler nested in the profiler) -> kernel_stats.csv
 #   3. kernel-trace statistics of the pipeline legs with the lowest fractions, one leg per trace -> legs_<name>_kernel_stats.csv
 #   4. FETCH_SIZE / WRITE_SIZE of the headline launch and of one MulRelin product in separate --pmc passes -> pmc_hbm.json, mulrelin_pmc_hbm.json
 set -e
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/prof_r04
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 /root/repo/bench.py > $OUT/bench.json 2> $OUT/bench.stderr.txt
+python3 "$ROOT/bench.py" --full > $OUT/bench.json 2> $OUT/bench.stderr.txt
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 /root/repo/bench.py --no-cpu-baseline --no-traffic --no-threads --steps 50 --warmup 5 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-traffic --no-threads --steps 50 --warmup 5 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 cp $OUT/trace/*kernel_stats.csv $OUT/kernel_stats.csv
 echo "bench trace done"
 for leg in bfv_mul moddown_ntt bfv_rotate_columns ckks_encrypt_pk ckks_rotate_hoisted; do

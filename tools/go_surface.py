@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Checklist of the reference `ring` package's exported identifiers against the Go shim in go/ring.
 
-    python tools/go_surface.py [--reference /root/reference] [--check]
+    python tools/go_surface.py (--reference LATTIGO_CHECKOUT | --names tests/golden/reference_go_names.json) [--check]
 
 Reads the exported functions, methods, types and variables of every non-test file of <reference>/ring (names only: the
 equivalent of `grep '^func ' ring/*.go`), looks each one up in go/ring/*.go, and writes go/ring/SURFACE.md.  --check exits
 non-zero when an identifier of a REPLACED file is neither defined in the shim nor listed in OMITTED below, or when SURFACE.md
-is stale.  The reference tree exists only in the build container; the committed SURFACE.md is the artefact a reviewer reads.
+is stale.  --names reads the same names from the committed fixture (tests/golden/make_reference_go_names.py writes it from a
+checkout of the reference), so the check runs without the reference tree; the committed SURFACE.md is the artefact a reviewer reads.
 """
 import argparse
+import json
 import os
 import re
 import sys
@@ -67,15 +69,23 @@ def exported(path):
     return out
 
 
+def ring_exported(reference):
+    """{file: exported names} of every non-test .go file of <reference>/ring"""
+    ref = os.path.join(reference, "ring")
+    return {f: exported(os.path.join(ref, f)) for f in sorted(os.listdir(ref)) if f.endswith(".go") and not f.endswith("_test.go")}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reference", default="/root/reference")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--reference", help="a checkout of the reference module (v1.3.1)")
+    src.add_argument("--names", help="the JSON fixture of its ring package's exported names (key ring_exported)")
     ap.add_argument("--check", action="store_true")
     args = ap.parse_args()
-    ref = os.path.join(args.reference, "ring")
-    if not os.path.isdir(ref):
-        print("reference tree not present; nothing to do")
-        return 0
+    if args.names:
+        ref_names = json.load(open(args.names))["ring_exported"]
+    else:
+        ref_names = ring_exported(args.reference)
     shim_dir = os.path.join(ROOT, "go", "ring")
     shim = {}
     for f in sorted(os.listdir(shim_dir)):
@@ -88,10 +98,8 @@ def main():
              "the reason; `upstream file`: the identifier lives in a file the shim does not replace (see go/ring/cgo.go).", ""]
     missing = []
     counts = {"device": 0, "host": 0, "omitted": 0, "upstream file": 0}
-    for f in sorted(os.listdir(ref)):
-        if not f.endswith(".go") or f.endswith("_test.go"):
-            continue
-        names = exported(os.path.join(ref, f))
+    for f in sorted(ref_names):
+        names = ref_names[f]
         if f in KEPT:
             lines += ["## %s -- kept from upstream (%s)" % (f, KEPT[f]), "", ", ".join("`%s`" % n for n in names), ""]
             counts["upstream file"] += len(names)
@@ -112,7 +120,7 @@ def main():
                 missing.append(f + ": " + n)
                 lines.append("| `%s` | **MISSING** | |" % n)
         lines.append("")
-    extra = sorted(n for n in shim if not any(n in exported(os.path.join(ref, f)) for f in os.listdir(ref) if f.endswith(".go") and not f.endswith("_test.go")))
+    extra = sorted(n for n in shim if not any(n in names for names in ref_names.values()))
     lines += ["## additions of the shim (no counterpart in the reference)", "", ", ".join("`%s` (%s)" % (n, shim[n]) for n in extra), "",
               "Totals: %d device, %d host, %d omitted, %d in upstream files; missing: %d." %
               (counts["device"], counts["host"], counts["omitted"], counts["upstream file"], len(missing)), ""]
