@@ -7,7 +7,9 @@
 // The patch to upstream bfv/evaluator.go, line numbers of v1.3.1:
 //
 //	delete  Mul          :467-470   -> below: degree 1 x degree 1 is ONE call, BfvPlan.Mul (extension to QMul, transforms, tensor, division by
-//	                                   Q with the float-corrected extension, centring, extension back, times t); other degrees go
+//	                                   Q with the float-corrected extension, centring, extension back, times t); every other product
+//	                                   with d0 + d1 <= 5 and a receiver of degree d0 + d1 (ciphertext x plaintext, products with a
+//	                                   degree-2 operand: :371-415) is ONE call, BfvPlan.MulDeg; a receiver of larger degree goes
 //	                                   through upstream's tensorAndRescale (:278-464, kept) on host views -- its copy loop into
 //	                                   polyBig (:430-436) indexes Coeffs
 //	delete  relinearize  :480-501   -> below: degree 2 is ONE call, CkksPlan.BfvRelinearize (key switch + the two Adds); higher degrees
@@ -101,9 +103,18 @@ func (evaluator *evaluator) resident(ps ...*ring.Poly) {
 	}
 }
 
-// Mul (:467): degree-1 x degree-1 on the device; anything else through upstream's tensorAndRescale on host views.
+// Mul (:467): degree-1 x degree-1 and every product with d0 + d1 <= 5 into a receiver of degree d0 + d1 on the device; a larger receiver
+// through upstream's tensorAndRescale on host views.
 func (evaluator *evaluator) Mul(op0 *Ciphertext, op1 Operand, ctOut *Ciphertext) {
 	el0, el1, elOut := evaluator.getElemAndCheckBinary(op0, op1, ctOut, op0.Degree()+op1.Degree())
+	if d := el0.Degree() + el1.Degree(); !(el0.Degree() == 1 && el1.Degree() == 1) && d <= 5 && elOut.Degree() == d {
+		// :371-415; el0 == el1 passes the same polys twice, which is the squaring case of lr_bfv_mul_deg
+		evaluator.resident(el0.value...)
+		evaluator.resident(el1.value...)
+		evaluator.resident(elOut.value...)
+		evaluator.dev().mul.MulDeg(el0.value, el1.value, elOut.value)
+		return
+	}
 	if el0.Degree() == 1 && el1.Degree() == 1 {
 		evaluator.resident(el0.value[0], el0.value[1], el1.value[0], el1.value[1], elOut.value[0], elOut.value[1], elOut.value[2])
 		if b := evaluator.batcher(); b != nil {

@@ -274,13 +274,14 @@ func (b *CkksBatcher) Stats() (batches, products uint64, largest int) {
 }
 
 // BfvPlan: what bfv.NewEvaluator builds for Mul (bfv/evaluator.go:89-112) and tensorAndRescale (:278-464).
+// contextQMul is held so that the context outlives the plan that reads it (a caller's only reference may be a loop-local variable).
 type BfvPlan struct {
-	contextQ *Context
-	h        *C.lr_bfv_plan
+	contextQ, contextQMul *Context
+	h                     *C.lr_bfv_plan
 }
 
 func NewBfvPlan(contextQ, contextQMul *Context, t uint64, maxBatch int) *BfvPlan {
-	p := &BfvPlan{contextQ: contextQ}
+	p := &BfvPlan{contextQ: contextQ, contextQMul: contextQMul}
 	call(func() C.int {
 		return C.lr_bfv_plan_create_ex(contextQ.h, contextQMul.h, C.uint64_t(t), C.int(maxBatch), DefaultOptions.ptr(), &p.h)
 	})
@@ -296,4 +297,30 @@ func (p *BfvPlan) Mul(ct0, ct1 [2]*Poly, ctOut [3]*Poly) {
 		return C.lr_bfv_mul(p.h, ct0[0].d, ct0[1].d, ct1[0].d, ct1[1].d, ctOut[0].d, ctOut[1].d, ctOut[2].d)
 	})
 	done(ctOut[0], ctOut[1], ctOut[2])
+}
+
+// MulDeg = evaluator.Mul for operands that are not both of degree 1 (bfv/evaluator.go:371-415 of tensorAndRescale), e.g. a ciphertext
+// times a Plaintext (degree 0) or a product with a degree-2 result: len(ct0) + len(ct1) <= 7, ctOut holds len(ct0) + len(ct1) - 1 distinct
+// polys.  The same polys in ct0 and ct1 are the squaring case (el0 == el1); an output may be an operand.
+func (p *BfvPlan) MulDeg(ct0, ct1, ctOut []*Poly) {
+	q := p.contextQ
+	q.use(ct0...)
+	q.use(ct1...)
+	q.want(ctOut...)
+	n0, n1, no := len(ct0), len(ct1), len(ctOut)
+	raw := C.malloc(C.size_t(n0+n1+no) * C.size_t(unsafe.Sizeof(uintptr(0))))
+	defer C.free(raw)
+	arr := polyArray(raw, n0+n1+no)
+	for i, c := range ct0 {
+		arr[i] = c.d
+	}
+	for i, c := range ct1 {
+		arr[n0+i] = c.d
+	}
+	for i, c := range ctOut {
+		arr[n0+n1+i] = c.d
+	}
+	a0, a1, ao := (**C.lr_poly)(raw), (**C.lr_poly)(unsafe.Pointer(&arr[n0])), (**C.lr_poly)(unsafe.Pointer(&arr[n0+n1]))
+	call(func() C.int { return C.lr_bfv_mul_deg(p.h, a0, C.int(n0-1), a1, C.int(n1-1), ao) })
+	done(ctOut...)
 }

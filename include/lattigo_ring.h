@@ -468,6 +468,15 @@ int lr_bfv_plan_destroy(lr_bfv_plan *plan);
  * reference's squaring case, bfv/evaluator.go:306,334-349) lifts and transforms the operand once; outputs may be operands. */
 int lr_bfv_mul(lr_bfv_plan *plan, const lr_poly *ct0_c0, const lr_poly *ct0_c1, const lr_poly *ct1_c0,
                const lr_poly *ct1_c1, lr_poly *out_c0, lr_poly *out_c1, lr_poly *out_c2);
+/* bfv.Evaluator.Mul for every operand degree: tensorAndRescale's branch for operands that are not both of degree 1
+ * (bfv/evaluator.go:371-415), e.g. a ciphertext times a Plaintext (an element of degree 0) or a product with an unrelinearised
+ * degree-2 result.  ct0[0..deg0], ct1[0..deg1] and out[0..deg0+deg1] over Q in the coefficient domain, one batch, batch <= max_batch.
+ * deg0, deg1 >= 0 and 1 <= deg0 + deg1 <= 5 (bfv.NewEvaluator's pools hold 6 polys, :74-82), else LR_ERR_ARG; shapes as lr_bfv_mul.
+ * deg0 == deg1 with ct1[i] == ct0[i] for every i (the same handles: Go's el0 == el1) is the squaring case (:379-402): the operand
+ * is lifted and transformed once.  (1, 1) is lr_bfv_mul.  Every operand is lifted before any output is written, so an output may
+ * be an operand; the outputs must be distinct handles (LR_ERR_ARG). */
+int lr_bfv_mul_deg(lr_bfv_plan *plan, const lr_poly *const *ct0, int deg0, const lr_poly *const *ct1, int deg1,
+                   lr_poly *const *out);
 
 /* The batcher for the workload the reference itself pools: every task of examples/dbfv/psi/psi.go:215-233 runs evaluator.Mul and
  * evaluator.Relinearize on one BFV ciphertext pair.  Concurrent calls from any number of host threads are merged into batched launches

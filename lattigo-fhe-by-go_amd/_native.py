@@ -135,6 +135,7 @@ SYMBOLS = {
     "lr_bfv_plan_create_ex": [vp, vp, u64, i32, vp, C.POINTER(vp)],
     "lr_bfv_plan_destroy": [vp],
     "lr_bfv_mul": [vp, vp, vp, vp, vp, vp, vp, vp],
+    "lr_bfv_mul_deg": [vp, C.POINTER(vp), i32, C.POINTER(vp), i32, C.POINTER(vp)],
     "lr_bfv_batcher_create": [vp, vp, i32, vp],
     "lr_bfv_batcher_destroy": [vp],
     "lr_bfv_batcher_mul": [vp, vp, vp, vp, vp, vp, vp, vp],

@@ -181,6 +181,21 @@ struct TensorLaunch {
 };
 hipError_t launch_tensor(const TensorLaunch &L, int limbs, int batch, hipStream_t stream);
 
+// the tensor of bfv tensorAndRescale for operands that are not both of degree 1 (bfv/evaluator.go:371-415) in one pass: c[i+j] accumulates
+// MRed(MForm(a_i), b_j) with CRed (MulCoeffsMontgomeryAndAdd), or, squaring (a == b, degree 2 only), c[i+j] = 2 MRed(MForm(a_i), a_j) for
+// i < j and c[2i] += MRed(MForm(a_i), a_i).  Every accumulator is canonical, so the order of the terms does not change a bit.
+constexpr int kTensorMaxDegree = 5;     // d0 + d1 <= 5: bfv.NewEvaluator's pools hold 6 polys (bfv/evaluator.go:74-82)
+struct TensorDegLaunch {
+    const u64 *a[kTensorMaxDegree + 1];   // a[0..d0]
+    const u64 *b[kTensorMaxDegree + 1];   // b[0..d1] (unread when squaring)
+    u64 *c[kTensorMaxDegree + 1];         // c[0..d0+d1]; may alias an operand (every thread reads its operands before it writes)
+    long long stride;                     // between batch polys, operands and products alike
+    int n;
+    const LimbParams *lp;
+};
+// d0, d1 >= 0, 1 <= d0 + d1 <= 5, (d0, d1) != (1, 1) (that is tensor_kernel); square only with d0 == d1 == 2; else hipErrorInvalidValue
+hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool square, int limbs, int batch, hipStream_t stream);
+
 // decryptor.Decrypt (ckks/decryptor.go:53-78) in one pass: Horner evaluation of ct[0..degree] at the secret key with the reference's
 // element operations and reduction cadence -- acc = ct[degree]; for i = degree..1: acc = CRed(MRed(acc, sk) + ct[i-1]), BRedAdd when
 // i & 7 == 7; a final BRedAdd unless degree & 7 == 7 -- every operand read once, the result written once
@@ -224,13 +239,15 @@ struct GatherLaunch {
 };
 hipError_t launch_gather(const GatherLaunch &L, int limbs, int batch, hipStream_t stream);
 
-// up to four polys with unrelated addresses copied to / from the slots of one contiguous buffer (BFV Mul at a small batch: the four
-// operand polys become one batch of 4 B, the three results leave one batch of 3 B): poly k = z / batch, batch element z % batch
+// up to eight polys with unrelated addresses copied to / from the slots of one contiguous buffer (BFV Mul at a small batch: the four
+// operand polys become one batch of 4 B, the three results leave one batch of 3 B; lr_bfv_mul_deg gathers up to 7 operand polys and
+// scatters up to 6 results): poly k = z / batch, batch element z % batch; slots from `count` on are not read
+constexpr int kMultiCopyMax = 8;
 struct MultiCopyLaunch {
-    const u64 *src[4];
-    long long src_stride[4];
-    u64 *dst[4];
-    long long dst_stride[4];
+    const u64 *src[kMultiCopyMax];
+    long long src_stride[kMultiCopyMax];
+    u64 *dst[kMultiCopyMax];
+    long long dst_stride[kMultiCopyMax];
     int count, batch, n;
 };
 hipError_t launch_multicopy(const MultiCopyLaunch &L, int limbs, hipStream_t stream);

@@ -198,6 +198,73 @@ __global__ __launch_bounds__(256) void tensor_kernel(TensorLaunch L) {
     }
 }
 
+// One coefficient of the general-degree tensor (bfv/evaluator.go:371-415).  Every index below is a compile-time constant once the loops
+// are unrolled: the operands, their Montgomery forms and the accumulators live in VGPRs.
+template <int D0, int D1, bool SQUARE>
+LR_D void tensor_deg_coeff(const u64 (&a)[D0 + 1], const u64 (&b)[D1 + 1], u64 (&c)[D0 + D1 + 1], const LimbParams &lp) {
+    const u64 q = lp.q;
+    u64 m[D0 + 1];
+#pragma unroll
+    for (int i = 0; i <= D0; ++i) m[i] = mform(a[i], q, lp.bred_hi, lp.bred_lo);        // :385-386 / :407-408
+#pragma unroll
+    for (int k = 0; k <= D0 + D1; ++k) c[k] = 0;                                           // :373-376
+    if constexpr (SQUARE) {
+        // :389-396: c[i+j] = MRed(MForm(a_i), a_j) overwrites, then Add doubles it (one pair per index in the 2 x 2 case)
+#pragma unroll
+        for (int i = 0; i <= D0; ++i)
+#pragma unroll
+            for (int j = i + 1; j <= D0; ++j) {
+                const u64 v = mred(m[i], a[j], q, lp.qinv);
+                c[i + j] = cred(v + v, q);
+            }
+        // :398-401: c[2i] = CRed(c[2i] + MRed(MForm(a_i), a_i))
+#pragma unroll
+        for (int i = 0; i <= D0; ++i) c[2 * i] = cred(c[2 * i] + mred(m[i], a[i], q, lp.qinv), q);
+    } else {
+        // :405-413: MulCoeffsMontgomeryAndAdd
+#pragma unroll
+        for (int i = 0; i <= D0; ++i)
+#pragma unroll
+            for (int j = 0; j <= D1; ++j) c[i + j] = cred(c[i + j] + mred(m[i], b[j], q, lp.qinv), q);
+    }
+}
+
+// grid as tensor_kernel: x = coefficient pairs / 256, y = limb, z = batch.  Each operand row is read once and each product written once.
+template <int D0, int D1, bool SQUARE>
+__global__ __launch_bounds__(256) void tensor_deg_kernel(TensorDegLaunch L) {
+    static_assert(D0 >= 0 && D1 >= 0 && D0 + D1 >= 1 && D0 + D1 <= kTensorMaxDegree, "reachable degrees only");
+    static_assert(!SQUARE || (D0 == D1 && D0 <= 2), "the squaring case overwrites c[i+j]: exact while each index has one pair i < j");
+    constexpr int NB = SQUARE ? D0 : D1;
+    const int limb = blockIdx.y;
+    const long long off = (long long)blockIdx.z * L.stride + (long long)limb * L.n;
+    const LimbParams lp = L.lp[limb];
+    const int pairs = L.n >> 1;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+        ulonglong2 va[D0 + 1], vb[NB + 1];
+#pragma unroll
+        for (int i = 0; i <= D0; ++i) va[i] = ld_stream(reinterpret_cast<const ulonglong2 *>(L.a[i] + off) + e);
+        if constexpr (!SQUARE) {
+#pragma unroll
+            for (int j = 0; j <= D1; ++j) vb[j] = ld_stream(reinterpret_cast<const ulonglong2 *>(L.b[j] + off) + e);
+        }
+        u64 ax[D0 + 1], ay[D0 + 1], bx[NB + 1], by[NB + 1], cx[D0 + D1 + 1], cy[D0 + D1 + 1];
+#pragma unroll
+        for (int i = 0; i <= D0; ++i) {
+            ax[i] = va[i].x;
+            ay[i] = va[i].y;
+        }
+#pragma unroll
+        for (int j = 0; j <= NB; ++j) {
+            bx[j] = SQUARE ? va[j].x : vb[j].x;
+            by[j] = SQUARE ? va[j].y : vb[j].y;
+        }
+        tensor_deg_coeff<D0, NB, SQUARE>(ax, bx, cx, lp);
+        tensor_deg_coeff<D0, NB, SQUARE>(ay, by, cy, lp);
+#pragma unroll
+        for (int k = 0; k <= D0 + D1; ++k) st_stream(reinterpret_cast<ulonglong2 *>(L.c[k] + off) + e, ulonglong2{cx[k], cy[k]});
+    }
+}
+
 // decryptor.Decrypt, ckks/decryptor.go:61-77 (HornerLaunch): the copy, degree x (MulCoeffsMontgomeryLvl, AddLvl), the ReduceLvl cadence
 __global__ __launch_bounds__(256) void horner_kernel(HornerLaunch L) {
     const int limb = blockIdx.y;
@@ -371,6 +438,32 @@ hipError_t launch_tensor(const TensorLaunch &L, int limbs, int batch, hipStream_
     return hipGetLastError();
 }
 
+hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool square, int limbs, int batch, hipStream_t stream) {
+    if (d0 < 0 || d1 < 0 || d0 + d1 < 1 || d0 + d1 > kTensorMaxDegree) return hipErrorInvalidValue;
+    if (square && !(d0 == 2 && d1 == 2)) return hipErrorInvalidValue;
+    using K = void (*)(TensorDegLaunch);
+    // [d0][d1] for d0 + d1 <= 5; (1, 1) is tensor_kernel's (bfv/evaluator.go:320-369)
+    static const K table[kTensorMaxDegree + 1][kTensorMaxDegree + 1] = {
+        {nullptr, tensor_deg_kernel<0, 1, false>, tensor_deg_kernel<0, 2, false>, tensor_deg_kernel<0, 3, false>, tensor_deg_kernel<0, 4, false>,
+         tensor_deg_kernel<0, 5, false>},
+        {tensor_deg_kernel<1, 0, false>, nullptr, tensor_deg_kernel<1, 2, false>, tensor_deg_kernel<1, 3, false>, tensor_deg_kernel<1, 4, false>},
+        {tensor_deg_kernel<2, 0, false>, tensor_deg_kernel<2, 1, false>, tensor_deg_kernel<2, 2, false>, tensor_deg_kernel<2, 3, false>},
+        {tensor_deg_kernel<3, 0, false>, tensor_deg_kernel<3, 1, false>, tensor_deg_kernel<3, 2, false>},
+        {tensor_deg_kernel<4, 0, false>, tensor_deg_kernel<4, 1, false>},
+        {tensor_deg_kernel<5, 0, false>}};
+    const K k = square ? tensor_deg_kernel<2, 2, true> : table[d0][d1];
+    if (!k) return hipErrorInvalidValue;
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    const int pairs = L.n >> 1;
+    int gx = (pairs + 255) / 256;
+    if (gx > 64) gx = 64;
+    if (gx < 1) gx = 1;
+    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k, grid, block, 0, stream, L);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void scatter_kernel(ScatterLaunch L) {
     const long long row = (long long)blockIdx.y * L.n;
     const long long b = blockIdx.z;
@@ -462,6 +555,7 @@ __global__ __launch_bounds__(256) void multicopy_kernel(MultiCopyLaunch L) {
 }
 
 hipError_t launch_multicopy(const MultiCopyLaunch &L, int limbs, hipStream_t stream) {
+    if (L.count > kMultiCopyMax) return hipErrorInvalidValue;
     if (limbs <= 0 || L.batch <= 0 || L.count <= 0) return hipSuccess;
     const int pairs = L.n >> 1;
     int gx = (pairs + 255) / 256;

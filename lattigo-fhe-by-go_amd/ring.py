@@ -749,6 +749,15 @@ class BfvPlan:
         """ct0, ct1: pairs of Poly over Q (coefficient domain); ctOut: triple (degree 2)."""
         check(lib().lr_bfv_mul(self.h, ct0[0].h, ct0[1].h, ct1[0].h, ct1[1].h, ctOut[0].h, ctOut[1].h, ctOut[2].h))
 
+    def MulDeg(self, ct0, ct1, ctOut):
+        """evaluator.Mul (bfv/evaluator.go:467) for operands of any degree with len(ct0) + len(ct1) <= 7 (lr_bfv_mul_deg): ct0, ct1
+        sequences of Poly over Q (coefficient domain; a Plaintext is a sequence of one), ctOut of len(ct0) + len(ct1) - 1 distinct
+        Poly.  The same Poly objects in ct0 and ct1 are the squaring case.  An output may be an operand."""
+        if len(ctOut) != len(ct0) + len(ct1) - 1:
+            raise LatticeRingError(4, "MulDeg: ctOut must hold len(ct0) + len(ct1) - 1 polys")      # LR_ERR_ARG
+        arr = lambda ps: (C.c_void_p * max(len(ps), 1))(*[None if p is None else p.h.value for p in ps])
+        check(lib().lr_bfv_mul_deg(self.h, arr(ct0), len(ct0) - 1, arr(ct1), len(ct1) - 1, arr(ctOut)))
+
     def NewRelinearizer(self, contextP, max_batch=1):
         """the key-switch half of bfv.NewEvaluator (decomposer, baseconverterQ1P, keyswitchpool: bfv/evaluator.go:100-112) over
         (contextQ, contextP): a CkksPlan, whose BfvRelinearize / BfvSwitchKeys / NewSwitchingKey serve Evaluator.Relinearize"""
