@@ -11,7 +11,7 @@ mkdir -p build
 # the C ABI, one translation unit per handle family (lr_host.hpp is what they share)
 ABI_UNITS="lr_abi_core lr_abi_ring lr_abi_bext lr_abi_ckks lr_abi_batcher lr_abi_bfv lr_abi_bfv_batcher lr_abi_peer"
 link() {
-  $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../liblattigo_ring_hip.so build/lr_ntt.o build/lr_ewise.o build/lr_bext.o $(for u in $ABI_UNITS; do echo build/$u.o; done) build/lr_bfv_tensor.o build/lr_precompute.o build/lr_asm.o build/lr_asm_blob.o
+  $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../liblattigo_ring_hip.so build/lr_ntt.o build/lr_ewise.o build/lr_bext.o $(for u in $ABI_UNITS; do echo build/$u.o; done) build/lr_precompute.o build/lr_asm.o build/lr_asm_blob.o
   echo "built $(cd .. && pwd)/liblattigo_ring_hip.so"
 }
 # developer shortcut: `build.sh lr_abi_ckks.cpp lr_ewise.hip` recompiles only the named sources and relinks (everything else must
@@ -131,9 +131,6 @@ for u in $ABI_UNITS; do
   $HIPCC $FLAGS -x hip -c $u.cpp -o build/$u.o &
   pids+=($!)
 done
-# bfv Mul for every operand degree: outside the lr_abi_* glob of the host-sanitizer build, which links against the launch stubs
-$HIPCC $FLAGS -x hip -c lr_bfv_tensor.cpp -o build/lr_bfv_tensor.o &
-pids+=($!)
 $HIPCC $FLAGS -x hip -c lr_precompute.cpp -o build/lr_precompute.o &
 pids+=($!)
 $HIPCC $FLAGS -x hip -c lr_asm.cpp -o build/lr_asm.o &

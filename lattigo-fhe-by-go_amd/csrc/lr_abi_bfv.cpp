@@ -1,8 +1,8 @@
-// lr_abi_bfv.cpp -- C ABI: lr_bfv_plan and bfv.Evaluator.Mul (tensorAndRescale).
+// lr_abi_bfv.cpp -- C ABI: lr_bfv_plan and bfv.Evaluator.Mul (tensorAndRescale): lr_bfv_mul and lr_bfv_mul_deg, two entry points of one pipeline.
 #include "lr_host.hpp"
 
 // ------------------------------------------------------------------------------------------
-// bfv.Evaluator.Mul (tensorAndRescale, bfv/evaluator.go:278-464)
+// lr_bfv_plan: what bfv.NewEvaluator builds for Mul (bfv/evaluator.go:89-112)
 // ------------------------------------------------------------------------------------------
 namespace lr_host {
 // (prod of moduli) >> 1, then reduced modulo every prime of `targets` (little-endian multi-precision)
@@ -75,125 +75,160 @@ extern "C" int lr_bfv_plan_destroy(lr_bfv_plan *p) {
     });
 }
 
-extern "C" int lr_bfv_mul(lr_bfv_plan *pl, const lr_poly *a0, const lr_poly *a1, const lr_poly *b0, const lr_poly *b1,
-                          lr_poly *o0, lr_poly *o1, lr_poly *o2) {
-    return guarded([&]() -> int {
-    if (!pl || !a0 || !a1 || !b0 || !b1 || !o0 || !o1 || !o2) return fail(LR_ERR_ARG, "null argument");
-    lr_context *cQ = pl->cQ, *cM = pl->cM;
-    const int nQ = cQ->h.L(), nM = cM->h.L(), n = (int)cQ->h.N;
-    const int batch = a0->batch;
+// ------------------------------------------------------------------------------------------
+// bfv.Evaluator.Mul (:467) -> tensorAndRescale (:278-464) for every degree pair with 1 <= d0 + d1 <= 5: ONE host pipeline in three
+// stages (lift, tensor, rescale tail) behind the two entry points lr_bfv_mul (degree 1 x degree 1, fixed arity) and lr_bfv_mul_deg.
+// ------------------------------------------------------------------------------------------
+namespace lr_host {
+namespace {
+// the derived sizes of one call
+struct BfvMulShape {
+    int deg0, deg1, nA, nB, nout;
+    bool square;             // ct0 == ct1: the operand is lifted once and the tensor reads its slots twice
+    int nin;                 // operand polys lifted: slots 0..nA-1 = ct0, then ct1 (for 1 x 1: a0, a1, b0, b1)
+    bool gathered;           // a small batch: the operands are lifted as one batch of nin B, the products go down as one of nout B
+    int nQ, nM, n, batch;
+    long long sQ, sM;        // poly strides of the pools over Q and over QMul
+    long long slotQ, slotM;  // batch * stride: one slot
+};
+
+// null handles, the degree domain, distinct outputs, N / limbs / batch of every poly, batch <= max_batch
+int bfv_mul_check(const lr_bfv_plan *pl, const lr_poly *const *ct0, int deg0, const lr_poly *const *ct1, int deg1, lr_poly *const *out) {
+    if (!pl || !ct0 || !ct1 || !out) return fail(LR_ERR_ARG, "null argument");
+    // bfv.NewEvaluator's pools hold 6 polys (:74-82): a larger product is an index panic in Go, degree 0 x 0 one of
+    // getElemAndCheckBinary (:114)
+    if (deg0 < 0 || deg1 < 0 || deg0 + deg1 < 1 || deg0 + deg1 > kTensorMaxDegree)
+        return fail(LR_ERR_ARG, "BFV Mul: the operand degrees must satisfy deg0, deg1 >= 0 and 1 <= deg0 + deg1 <= 5");
+    const int nA = deg0 + 1, nB = deg1 + 1, nout = deg0 + deg1 + 1;
+    for (int i = 0; i < nA; ++i)
+        if (!ct0[i]) return fail(LR_ERR_ARG, "null argument");
+    for (int j = 0; j < nB; ++j)
+        if (!ct1[j]) return fail(LR_ERR_ARG, "null argument");
+    for (int k = 0; k < nout; ++k) {
+        if (!out[k]) return fail(LR_ERR_ARG, "null argument");
+        for (int l = 0; l < k; ++l)
+            if (out[l] == out[k]) return fail(LR_ERR_ARG, "BFV Mul: the output polys must be distinct");
+    }
+    const lr_context *cQ = pl->cQ;
+    const int nQ = cQ->h.L(), batch = ct0[0]->batch;
     if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    for (const lr_poly *p : {a0, a1, b0, b1, (const lr_poly *)o0, (const lr_poly *)o1, (const lr_poly *)o2}) {
+    for (int i = 0; i < nA + nB + nout; ++i) {
+        const lr_poly *p = i < nA ? ct0[i] : i < nA + nB ? ct1[i - nA] : out[i - nA - nB];
         if (p->N != cQ->h.N || p->limbs < nQ || p->batch != batch) return fail(LR_ERR_SHAPE, "BFV Mul: operands must hold |Q| limbs and share the batch");
     }
-    LR_TRY(same_stream(cQ, cM));
-    LR_HIP(hipSetDevice(cQ->device));
-    const long long sQ = (long long)nQ * n, sM = (long long)nM * n;
-    const lr_poly *A[2] = {a0, a1}, *B[2] = {b0, b1};
-    lr_poly *O[3] = {o0, o1, o2};
-    LR_TRY(pl->liftQ.ensure(cQ, (size_t)4 * batch * sQ));
-    LR_TRY(pl->liftM.ensure(cQ, (size_t)4 * batch * sM));
-    LR_TRY(pl->prodQ.ensure(cQ, (size_t)3 * batch * sQ));
-    LR_TRY(pl->prodM.ensure(cQ, (size_t)3 * batch * sM));
-    const long long slotQ = (long long)batch * sQ, slotM = (long long)batch * sM;
-    // ct0 == ct1 (:306, :334 "squaring case"): the second operand is not lifted and transformed again.  Its tensor (c0 = c0[0]^2,
-    // c1 = 2 c0[0] c0[1] by AddNoMod, c2 = c0[1]^2) and the regular one give the same canonical polys after the InvNTT -- MRed(MForm(x), y)
-    // and MRed(MForm(y), x) are the same residue below q --, so the tensor kernel simply reads the first operand's slots twice.
-    const bool square = a0 == b0 && a1 == b1;
-    const int sides = square ? 1 : 2;
-    // slots: a0, a1, b0, b1
-    u64 *const aQ[2] = {pl->liftQ.d, pl->liftQ.d + slotQ};
-    u64 *const aM[2] = {pl->liftM.d, pl->liftM.d + slotM};
-    u64 *const bQ[2] = {square ? aQ[0] : pl->liftQ.d + 2 * slotQ, square ? aQ[1] : pl->liftQ.d + 3 * slotQ};
-    u64 *const bM[2] = {square ? aM[0] : pl->liftM.d + 2 * slotM, square ? aM[1] : pl->liftM.d + 3 * slotM};
-    u64 *const cQ3[3] = {pl->prodQ.d, pl->prodQ.d + slotQ, pl->prodQ.d + 2 * slotQ};
-    u64 *const cM3[3] = {pl->prodM.d, pl->prodM.d + slotM, pl->prodM.d + 2 * slotM};
+    return LR_OK;
+}
+
+// :298-313 basis extension Q -> QMul, then NTT in both bases, for every operand poly src[0..nin-1] into its slot of liftQ / liftM
+int bfv_lift(lr_bfv_plan *pl, const BfvMulShape &s, const lr_poly *const *src) {
+    lr_context *cQ = pl->cQ, *cM = pl->cM;
     lr_bext *bx = pl->bext;
-    // A small batch: the four operand polys (unrelated addresses) are gathered into one batch of 4 B and every step of :298-313 runs
-    // once on it; the three products go down as one batch of 3 B and are scattered to the callers' polys at the end.  One ciphertext
-    // pair at PN14QP438: 26 launches of 3 - 6 workgroups in a row, 424 us; 11 launches, 138 us (profiles/r03/bfv_small_batch.txt).
-    // The copies (two passes over 7 polys) buy nothing once a launch of one operand fills the chip.
-    const bool gathered = !pl->no_gather && (long long)4 * batch * std::max(nQ, nM) * (n >= (1 << 15) ? 2 : 1) <= pl->gather_below;
-    if (gathered) {
-        LR_TRY(pl->stageIn.ensure(cQ, (size_t)4 * batch * sQ));
-        LR_TRY(pl->stageOut.ensure(cQ, (size_t)3 * batch * sQ));
-        MultiCopyLaunch G;
-        const lr_poly *srcs[4] = {a0, a1, b0, b1};
-        const int polys = 2 * sides;
-        for (int k = 0; k < 4; ++k) {
-            G.src[k] = k < polys ? srcs[k]->d : nullptr;
-            G.src_stride[k] = k < polys ? srcs[k]->stride() : 0;
-            G.dst[k] = k < polys ? pl->stageIn.d + k * slotQ : nullptr;
-            G.dst_stride[k] = k < polys ? sQ : 0;
+    const int nQ = s.nQ, nM = s.nM;
+    const long long sQ = s.sQ, sM = s.sM;
+    if (s.gathered) {
+        // the operand polys (unrelated addresses) are gathered into one batch of nin B and every step runs once on it.  One ciphertext pair
+        // at PN14QP438: 26 launches of 3 - 6 workgroups in a row, 424 us; 11 launches, 138 us (profiles/r03/bfv_small_batch.txt).  The
+        // copies buy nothing once a launch of one operand fills the chip.
+        LR_TRY(pl->stageIn.ensure(cQ, (size_t)s.nin * s.batch * sQ));
+        MultiCopyLaunch G{};
+        for (int k = 0; k < s.nin; ++k) {
+            G.src[k] = src[k]->d;
+            G.src_stride[k] = src[k]->stride();
+            G.dst[k] = pl->stageIn.d + k * s.slotQ;
+            G.dst_stride[k] = sQ;
         }
-        G.count = polys;
-        G.batch = batch;
-        G.n = n;
+        G.count = s.nin;
+        G.batch = s.batch;
+        G.n = s.n;
         LR_HIP(launch_multicopy(G, nQ, cQ->stream));
-        Rows in4{pl->stageIn.d, sQ, 0, 1};
-        LR_TRY(run_ext(cQ, bx->qp, nQ, in4, polys * batch, segment(pl->liftM.d, sM, 0, 0, nM), segment(nullptr, 0, 0, 0, 0)));
-        LR_TRY(run_ntt(cQ, false, in4, Rows{pl->liftQ.d, sQ, 0, 1}, 0, 1, nQ, polys * batch));
-        LR_TRY(run_ntt(cM, false, Rows{pl->liftM.d, sM, 0, 1}, Rows{pl->liftM.d, sM, 0, 1}, 0, 1, nM, polys * batch));
-    } else {
-        // :298-313  basis extension Q -> QMul, then NTT in both bases
-        for (int i = 0; i < 2; ++i) {
-            for (int side = 0; side < sides; ++side) {
-                const lr_poly *src = side == 0 ? A[i] : B[i];
-                u64 *dQ = side == 0 ? aQ[i] : bQ[i];
-                u64 *dM = side == 0 ? aM[i] : bM[i];
-                LR_TRY(run_ext(cQ, bx->qp, nQ, rows_of(src), batch, segment(dM, sM, 0, 0, nM), segment(nullptr, 0, 0, 0, 0)));
-                LR_TRY(run_ntt(cQ, false, rows_of(src), Rows{dQ, sQ, 0, 1}, 0, 1, nQ, batch));
-                LR_TRY(run_ntt(cM, false, Rows{dM, sM, 0, 1}, Rows{dM, sM, 0, 1}, 0, 1, nM, batch));
-            }
+        Rows in{pl->stageIn.d, sQ, 0, 1};
+        LR_TRY(run_ext(cQ, bx->qp, nQ, in, s.nin * s.batch, segment(pl->liftM.d, sM, 0, 0, nM), segment(nullptr, 0, 0, 0, 0)));
+        LR_TRY(run_ntt(cQ, false, in, Rows{pl->liftQ.d, sQ, 0, 1}, 0, 1, nQ, s.nin * s.batch));
+        LR_TRY(run_ntt(cM, false, Rows{pl->liftM.d, sM, 0, 1}, Rows{pl->liftM.d, sM, 0, 1}, 0, 1, nM, s.nin * s.batch));
+        return LR_OK;
+    }
+    for (int k = 0; k < s.nin; ++k) {
+        u64 *dQ = pl->liftQ.d + k * s.slotQ, *dM = pl->liftM.d + k * s.slotM;
+        LR_TRY(run_ext(cQ, bx->qp, nQ, rows_of(src[k]), s.batch, segment(dM, sM, 0, 0, nM), segment(nullptr, 0, 0, 0, 0)));
+        LR_TRY(run_ntt(cQ, false, rows_of(src[k]), Rows{dQ, sQ, 0, 1}, 0, 1, nQ, s.batch));
+        LR_TRY(run_ntt(cM, false, Rows{dM, sM, 0, 1}, Rows{dM, sM, 0, 1}, 0, 1, nM, s.batch));
+    }
+    return LR_OK;
+}
+
+// the tensor, one pass per base, from the lift slots into product slots 0..nout-1.  The one stage that tells 1 x 1 from the rest:
+//   1 x 1 (:320-369): MForm x2 and the four products, the kernel ckks MulRelin shares (the middle component comes out reduced where the
+//     reference leaves it in [0,2q): the InvNTT that follows is canonical either way).  Squaring (:306, :334) is b0 == a0: its tensor
+//     (c0 = a0^2, c1 = 2 a0 a1 by AddNoMod, c2 = a1^2) and the regular one give the same canonical polys after the InvNTT -- MRed(MForm(x), y)
+//     and MRed(MForm(y), x) are the same residue below q --, so the kernel simply reads the first operand's slots twice;
+//   every other pair (:371-415): the accumulators are zeroed, MForm'd and summed in registers (every one canonical).
+int bfv_tensor(lr_bfv_plan *pl, const BfvMulShape &s) {
+    for (int base = 0; base < 2; ++base) {
+        lr_context *cx = base == 0 ? pl->cQ : pl->cM;
+        u64 *lift = base == 0 ? pl->liftQ.d : pl->liftM.d, *prod = base == 0 ? pl->prodQ.d : pl->prodM.d;
+        const long long slot = base == 0 ? s.slotQ : s.slotM, stride = base == 0 ? s.sQ : s.sM;
+        const int limbs = base == 0 ? s.nQ : s.nM;
+        if (s.deg0 == 1 && s.deg1 == 1) {
+            TensorLaunch T;
+            T.a0 = lift;
+            T.a1 = lift + slot;
+            T.b0 = s.square ? T.a0 : lift + 2 * slot;
+            T.b1 = s.square ? T.a1 : lift + 3 * slot;
+            T.a0_stride = T.a1_stride = T.b0_stride = T.b1_stride = stride;
+            T.c0 = prod;
+            T.c1 = prod + slot;
+            T.c2 = prod + 2 * slot;
+            T.c_stride = T.c1_stride = T.c2_stride = stride;
+            T.n = s.n;
+            T.lp = cx->d_lp;
+            LR_HIP(launch_tensor(T, limbs, s.batch, cx->stream));
+        } else {
+            TensorDegLaunch T{};
+            for (int i = 0; i < s.nA; ++i) T.a[i] = lift + i * slot;
+            for (int j = 0; j < s.nB; ++j) T.b[j] = s.square ? T.a[j] : lift + (s.nA + j) * slot;
+            for (int k = 0; k < s.nout; ++k) T.c[k] = prod + k * slot;
+            T.stride = stride;
+            T.n = s.n;
+            T.lp = cx->d_lp;
+            LR_HIP(launch_tensor_deg(T, s.deg0, s.deg1, s.square, limbs, s.batch, cx->stream));
         }
     }
-    // :327-367 MForm x2 and the four products per base, one pass each (the middle component comes out reduced where
-    // the reference leaves it in [0,2q): the InvNTT that follows is canonical either way)
-    for (int base = 0; base < 2; ++base) {
-        lr_context *cx = base == 0 ? cQ : cM;
-        const long long sx = base == 0 ? sQ : sM;
-        TensorLaunch T;
-        T.a0 = base == 0 ? aQ[0] : aM[0];
-        T.a1 = base == 0 ? aQ[1] : aM[1];
-        T.b0 = base == 0 ? bQ[0] : bM[0];
-        T.b1 = base == 0 ? bQ[1] : bM[1];
-        T.a0_stride = T.a1_stride = T.b0_stride = T.b1_stride = sx;
-        T.c0 = base == 0 ? cQ3[0] : cM3[0];
-        T.c1 = base == 0 ? cQ3[1] : cM3[1];
-        T.c2 = base == 0 ? cQ3[2] : cM3[2];
-        T.c_stride = T.c1_stride = T.c2_stride = sx;
-        T.n = n;
-        T.lp = cx->d_lp;
-        LR_HIP(launch_tensor(T, base == 0 ? nQ : nM, batch, cx->stream));
-    }
-    // :423-463 back to coefficients, divide by Q (result over QMul), centre, back to Q, times t
-    const LimbScalars &tsc = pl->t_mont;
-    const long long poolM_stride = sM;
+    return LR_OK;
+}
+
+// :417-463 for every product: back to coefficients, divide by Q (result over QMul), centre, back to Q, times t -- into the callers' polys,
+// one product after the other, or (gathered) as one batch of nout B whose results are scattered afterwards
+int bfv_rescale(lr_bfv_plan *pl, const BfvMulShape &s, lr_poly *const *out) {
+    lr_context *cQ = pl->cQ, *cM = pl->cM;
+    lr_bext *bx = pl->bext;
+    const int nQ = s.nQ, nM = s.nM, n = s.n;
+    const long long sQ = s.sQ, sM = s.sM;
     // the element-wise tails ride in the extensions' stores where the extension kernel in use has the epilogue (ExtSegment::epi_mode)
     const bool fuse_down = !pl->no_ext_epilogue && ext_epilogue_supported(bx->qp.tables(), nQ, n);
     const bool fuse_up = !pl->no_ext_epilogue && ext_epilogue_supported(bx->pq.tables(), nM, n);
-    // the three products one after the other, or (gathered) as one batch of 3 B whose results are scattered afterwards
-    const int rounds = gathered ? 1 : 3, nb = gathered ? 3 * batch : batch;
-    if (!fuse_down) LR_TRY(bx->poolP.ensure(cM, (size_t)nb * poolM_stride));
+    const int rounds = s.gathered ? 1 : s.nout, nb = s.gathered ? s.nout * s.batch : s.batch;
+    if (s.gathered) LR_TRY(pl->stageOut.ensure(cQ, (size_t)s.nout * s.batch * sQ));
+    if (!fuse_down) LR_TRY(bx->poolP.ensure(cM, (size_t)nb * sM));
     for (int i = 0; i < rounds; ++i) {
-        u64 *const outp = gathered ? pl->stageOut.d : O[i]->d;
-        const long long outs = gathered ? sQ : O[i]->stride();
-        Rows q1{cQ3[i], sQ, 0, 1}, q2{cM3[i], sM, 0, 1};
+        u64 *const cq = pl->prodQ.d + i * s.slotQ, *const cm = pl->prodM.d + i * s.slotM;
+        u64 *const outp = s.gathered ? pl->stageOut.d : out[i]->d;
+        const long long outs = s.gathered ? sQ : out[i]->stride();
+        Rows q1{cq, sQ, 0, 1}, q2{cm, sM, 0, 1};
         LR_TRY(run_ntt(cQ, true, q1, q1, 0, 1, nQ, nb));
         LR_TRY(run_ntt(cM, true, q2, q2, 0, 1, nM, nb));
         // ModDownSplitedQP(levelQ, levelQMul, c2Q1, c2Q2, c2Q2), ring_basis_extension.go:314, with the AddScalarBigint(pHalf) of :457
         if (fuse_down) {
-            ExtSegment sd = segment(cM3[i], sM, 0, 0, nM);
+            ExtSegment sd = segment(cm, sM, 0, 0, nM);
             sd.epi_mode = 1;
-            sd.epi_x = cM3[i];                     // read and written at the same position by the same thread
+            sd.epi_x = cm;                         // read and written at the same position by the same thread
             sd.epi_x_stride = sM;
             sd.epi_c = bx->d_moddown_qp;
             sd.epi_s = pl->d_phalf_m;
             LR_TRY(run_ext(cQ, bx->qp, nQ, q1, nb, sd, segment(nullptr, 0, 0, 0, 0)));
         } else {
-            LR_TRY(run_ext(cQ, bx->qp, nQ, q1, nb, segment(bx->poolP.d, poolM_stride, 0, 0, nM), segment(nullptr, 0, 0, 0, 0)));
-            LR_TRY(run_submul(cM, nM, nb, cM3[i], sM, bx->poolP.d, poolM_stride, (long long)n, cM3[i], sM, bx->d_moddown_qp, false, nullptr,
-                              nullptr, 0, &pl->phalf_m));
+            LR_TRY(run_ext(cQ, bx->qp, nQ, q1, nb, segment(bx->poolP.d, sM, 0, 0, nM), segment(nullptr, 0, 0, 0, 0)));
+            LR_TRY(run_submul(cM, nM, nb, cm, sM, bx->poolP.d, sM, (long long)n, cm, sM, bx->d_moddown_qp, false, nullptr, nullptr, 0,
+                              &pl->phalf_m));
         }
         // :458 ModUpSplitPQ, :459 SubScalarBigint(pHalf), :462 MulScalar(t)
         if (fuse_up) {
@@ -211,24 +246,75 @@ extern "C" int lr_bfv_mul(lr_bfv_plan *pl, const lr_poly *a0, const lr_poly *a1,
             S.n = n;
             S.lp = cQ->d_lp;
             S.sub = pl->phalf_q;
-            S.mul = tsc;
+            S.mul = pl->t_mont;
             LR_HIP(launch_scalar_pair(S, nQ, nb, cQ->stream));
         }
     }
-    if (gathered) {
-        MultiCopyLaunch S;
-        for (int k = 0; k < 3; ++k) {
-            S.src[k] = pl->stageOut.d + k * slotQ;
+    if (s.gathered) {
+        MultiCopyLaunch S{};
+        for (int k = 0; k < s.nout; ++k) {
+            S.src[k] = pl->stageOut.d + k * s.slotQ;
             S.src_stride[k] = sQ;
-            S.dst[k] = O[k]->d;
-            S.dst_stride[k] = O[k]->stride();
+            S.dst[k] = out[k]->d;
+            S.dst_stride[k] = out[k]->stride();
         }
-        S.src[3] = nullptr; S.dst[3] = nullptr; S.src_stride[3] = S.dst_stride[3] = 0;
-        S.count = 3;
-        S.batch = batch;
+        S.count = s.nout;
+        S.batch = s.batch;
         S.n = n;
         LR_HIP(launch_multicopy(S, nQ, cQ->stream));
     }
     return LR_OK;
+}
+
+// the arguments have passed bfv_mul_check
+int bfv_tensor_and_rescale(lr_bfv_plan *pl, const lr_poly *const *ct0, int deg0, const lr_poly *const *ct1, int deg1, lr_poly *const *out) {
+    lr_context *cQ = pl->cQ, *cM = pl->cM;
+    LR_TRY(same_stream(cQ, cM));
+    LR_HIP(hipSetDevice(cQ->device));
+    BfvMulShape s;
+    s.deg0 = deg0, s.deg1 = deg1;
+    s.nA = deg0 + 1, s.nB = deg1 + 1, s.nout = deg0 + deg1 + 1;
+    // ct0 == ct1 (Go's pointer comparison, :306 and :379): the same handles in the same order.  The operand is lifted once; in the reachable
+    // domain that is 1 x 1 and 2 x 2 (degree 3 squared needs c[6]).
+    s.square = deg0 == deg1;
+    for (int i = 0; s.square && i < s.nA; ++i) s.square = ct0[i] == ct1[i];
+    s.nin = s.square ? s.nA : s.nA + s.nB;
+    s.nQ = cQ->h.L(), s.nM = cM->h.L(), s.n = (int)cQ->h.N, s.batch = ct0[0]->batch;
+    s.sQ = (long long)s.nQ * s.n, s.sM = (long long)s.nM * s.n;
+    s.slotQ = s.batch * s.sQ, s.slotM = s.batch * s.sM;
+    // workgroups of the operands' joint transform up to which they are gathered: the polys lifted.  1 x 1 counts its four
+    // operand polys even when squaring, where two are lifted -- the threshold it was measured with; no 1 x 1 call changes path.
+    const int counted = deg0 == 1 && deg1 == 1 ? s.nA + s.nB : s.nin;
+    s.gathered = !pl->no_gather && (long long)counted * s.batch * std::max(s.nQ, s.nM) * (s.n >= (1 << 15) ? 2 : 1) <= pl->gather_below;
+    LR_TRY(pl->liftQ.ensure(cQ, (size_t)s.nin * s.batch * s.sQ));
+    LR_TRY(pl->liftM.ensure(cQ, (size_t)s.nin * s.batch * s.sM));
+    LR_TRY(pl->prodQ.ensure(cQ, (size_t)s.nout * s.batch * s.sQ));
+    LR_TRY(pl->prodM.ensure(cQ, (size_t)s.nout * s.batch * s.sM));
+    const lr_poly *src[2 * (kTensorMaxDegree + 1)];
+    for (int i = 0; i < s.nA; ++i) src[i] = ct0[i];
+    for (int j = 0; !s.square && j < s.nB; ++j) src[s.nA + j] = ct1[j];
+    // every operand is lifted before any output is written, so an output may be an operand
+    LR_TRY(bfv_lift(pl, s, src));
+    LR_TRY(bfv_tensor(pl, s));
+    return bfv_rescale(pl, s, out);
+}
+}  // namespace
+}  // namespace lr_host
+
+extern "C" int lr_bfv_mul(lr_bfv_plan *pl, const lr_poly *a0, const lr_poly *a1, const lr_poly *b0, const lr_poly *b1,
+                          lr_poly *o0, lr_poly *o1, lr_poly *o2) {
+    return guarded([&]() -> int {
+    const lr_poly *const ct0[2] = {a0, a1}, *const ct1[2] = {b0, b1};
+    lr_poly *const out[3] = {o0, o1, o2};
+    LR_TRY(bfv_mul_check(pl, ct0, 1, ct1, 1, out));
+    return bfv_tensor_and_rescale(pl, ct0, 1, ct1, 1, out);
+    });
+}
+
+extern "C" int lr_bfv_mul_deg(lr_bfv_plan *pl, const lr_poly *const *ct0, int deg0, const lr_poly *const *ct1, int deg1,
+                              lr_poly *const *out) {
+    return guarded([&]() -> int {
+    LR_TRY(bfv_mul_check(pl, ct0, deg0, ct1, deg1, out));
+    return bfv_tensor_and_rescale(pl, ct0, deg0, ct1, deg1, out);
     });
 }

@@ -193,7 +193,7 @@ struct TensorDegLaunch {
     int n;
     const LimbParams *lp;
 };
-// d0, d1 >= 0, 1 <= d0 + d1 <= 5, (d0, d1) != (1, 1) (that is tensor_kernel); square only with d0 == d1 == 2; else hipErrorInvalidValue
+// d0, d1 >= 0, 1 <= d0 + d1 <= 5, (d0, d1) != (1, 1) (that is launch_tensor); square only with d0 == d1 == 2; else hipErrorInvalidValue
 hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool square, int limbs, int batch, hipStream_t stream);
 
 // decryptor.Decrypt (ckks/decryptor.go:53-78) in one pass: Horner evaluation of ct[0..degree] at the secret key with the reference's
@@ -240,8 +240,8 @@ struct GatherLaunch {
 hipError_t launch_gather(const GatherLaunch &L, int limbs, int batch, hipStream_t stream);
 
 // up to eight polys with unrelated addresses copied to / from the slots of one contiguous buffer (BFV Mul at a small batch: the four
-// operand polys become one batch of 4 B, the three results leave one batch of 3 B; lr_bfv_mul_deg gathers up to 7 operand polys and
-// scatters up to 6 results): poly k = z / batch, batch element z % batch; slots from `count` on are not read
+// operand polys become one batch of 4 B, the three results leave one batch of 3 B; other degrees gather up to 7 operand polys and
+// scatter up to 6 results: bfv_tensor_and_rescale, lr_abi_bfv.cpp): poly k = z / batch, batch element z % batch; slots from `count` on are not read
 constexpr int kMultiCopyMax = 8;
 struct MultiCopyLaunch {
     const u64 *src[kMultiCopyMax];

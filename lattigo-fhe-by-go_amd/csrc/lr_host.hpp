@@ -388,7 +388,7 @@ struct lr_ckks_plan {
     const void *lane_of = nullptr;   // the batcher this plan is a lane of (lanes never fork: their batcher keeps the device busy)
 };
 
-// what bfv.NewEvaluator builds for Mul (bfv/evaluator.go:89-112): lr_abi_bfv.cpp
+// what bfv.NewEvaluator builds for Mul (bfv/evaluator.go:89-112): lr_abi_bfv.cpp (lr_bfv_mul, lr_bfv_mul_deg)
 struct lr_bfv_plan {
     int device = 0;
     lr_context *cQ = nullptr, *cM = nullptr;
@@ -402,9 +402,9 @@ struct lr_bfv_plan {
     bool no_gather = false;           // Options::bfv_no_gather: every operand / product in launches of its own at every batch size
     long long gather_below = 1536;    // Options::bfv_gather_below: workgroups of the four operands' joint transform up to which they are gathered (PN14QP438:
                                       // gathered 346 / 565 / 1015 / 1912 us per batch of 16 / 32 / 64 / 128, per operand 490 / 618 / 1081 / 1805)
-    Pool liftQ, liftM;                // the four operand polys over Q and over QMul, slots a0, a1, b0, b1 of [batch][limbs][N] each
-    Pool prodQ, prodM;                // the three products, slots c0, c1, c2
-    Pool stageIn, stageOut;           // small batches: the operands gathered into one batch of 4 B, the results before they are scattered
+    Pool liftQ, liftM;                // the operand polys over Q and over QMul, slots ct0[0..d0] then ct1[0..d1] of [batch][limbs][N] each
+    Pool prodQ, prodM;                // the d0 + d1 + 1 products, slots c0, c1, ...
+    Pool stageIn, stageOut;           // small batches: the operands gathered into one batch, the results before they are scattered
     const void *lane_of = nullptr;    // the batcher this plan is a lane of (not destroyed while that lives)
     ~lr_bfv_plan() {
         for (u64 *p : {d_phalf_q, d_phalf_m, d_t_mont})

@@ -1,8 +1,9 @@
-// lr_bfv_mul_deg's host side under AddressSanitizer + UBSan (tests/test_host_bfv_mul_deg_sanitizers.py): the REAL host code -- lr_abi_*.cpp,
-// lr_bfv_tensor.cpp, lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in and the recording launch stubs of
-// tests/cpp/hipstub/ (stub_launch.cpp + stub_tensor_deg.cpp), which touch the first and the last word of every row a kernel would read or
-// write.  Every degree pair with 1 <= d0 + d1 <= 5 and the 2 x 2 squaring, at batches on both sides of the gather threshold, with and without
-// the gathered path and the extension epilogues, with operands wider than |Q| limbs, with outputs written over operands, and every refusal.
+// BFV Mul's host side under AddressSanitizer + UBSan (tests/test_host_bfv_mul_deg_sanitizers.py): the REAL host code -- lr_abi_*.cpp (the one
+// tensorAndRescale pipeline of lr_abi_bfv.cpp behind lr_bfv_mul and lr_bfv_mul_deg), lr_host.hpp, lr_precompute.cpp -- compiled with g++
+// against the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/, which touch the first and the last word of every
+// row a kernel would read or write.  Every degree pair with 1 <= d0 + d1 <= 5 through lr_bfv_mul_deg, 1 x 1 through lr_bfv_mul as well, the
+// 1 x 1 and 2 x 2 squarings, at batches on both sides of the gather threshold, with and without the gathered path and the extension
+// epilogues, with operands wider than |Q| limbs, with outputs written over operands, and every refusal.
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <atomic>
 #include <cstdint>
@@ -56,6 +57,10 @@ static int call(lr_bfv_plan *pl, const std::vector<lr_poly *> &a, const std::vec
     std::vector<const lr_poly *> ca(a.begin(), a.end()), cb(b.begin(), b.end());
     return lr_bfv_mul_deg(pl, ca.data(), (int)a.size() - 1, cb.data(), (int)b.size() - 1, o.data());
 }
+// degree 1 x degree 1 through the fixed-arity entry point
+static int call_mul(lr_bfv_plan *pl, const std::vector<lr_poly *> &a, const std::vector<lr_poly *> &b, const std::vector<lr_poly *> &o) {
+    return lr_bfv_mul(pl, a[0], a[1], b[0], b[1], o[0], o[1], o[2]);
+}
 
 int main() {
     lr_context *q = nullptr, *m = nullptr;
@@ -90,6 +95,12 @@ int main() {
                     if (!wide) alias[d0 + d1] = r.b[d1];
                     OK(call(pl, r.a, r.b, alias));
                     ++calls;
+                    if (d0 == 1 && d1 == 1) {                             // lr_bfv_mul's pointer packing: the same three calls
+                        OK(call_mul(pl, r.a, r.b, r.o));
+                        OK(call_mul(pl, r.a, r.a, r.o));
+                        OK(call_mul(pl, r.a, r.b, alias));
+                        calls += 3;
+                    }
                     r.free_all();
                 }
         }
@@ -119,8 +130,9 @@ int main() {
             CHECK(call(pl, r.a, r.b, {r.o[0], r.o[1], r.o[2], other}) == LR_ERR_SHAPE);
             std::vector<lr_poly *> bigs{big, poly(q, NQ, MAXB + 1)}, bigo{poly(q, NQ, MAXB + 1), poly(q, NQ, MAXB + 1)};
             CHECK(call(pl, bigs, {bigs[0]}, bigo) == LR_ERR_SHAPE);                                                    // batch > max_batch
+            CHECK(call_mul(pl, r.a, r.b, {r.o[0], r.o[1], r.o[0]}) == LR_ERR_ARG);                                     // lr_bfv_mul: duplicate outputs
             CHECK(lr::g_stub_launches.load() == before);
-            refusals += 14;
+            refusals += 15;
             for (lr_poly *p : {seven[4], seven[5], seven[6], narrow, other, bigs[1], bigo[0], bigo[1]}) lr_poly_free(p);
             lr_poly_free(big);
             r.free_all();

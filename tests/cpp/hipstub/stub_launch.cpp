@@ -156,6 +156,18 @@ hipError_t launch_tensor(const TensorLaunch &L, int limbs, int batch, hipStream_
     }
     return hipSuccess;
 }
+// refuses what the real launcher refuses: the host code never sends 1 x 1 here (that is launch_tensor)
+hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool square, int limbs, int batch, hipStream_t) {
+    if (d0 < 0 || d1 < 0 || d0 + d1 < 1 || d0 + d1 > kTensorMaxDegree || (d0 == 1 && d1 == 1)) return hipErrorInvalidValue;
+    if (square && !(d0 == 2 && d1 == 2)) return hipErrorInvalidValue;
+    for (int k = 0; k <= d0 + d1; ++k)          // (rows_r / rows_w skip a null base: an unset slot is an error here)
+        if ((k <= d0 && !L.a[k]) || (!square && k <= d1 && !L.b[k]) || !L.c[k]) return hipErrorInvalidValue;
+    g_stub_launches.fetch_add(1);
+    for (int i = 0; i <= d0; ++i) rows_r(L.a[i], L.stride, 0, 1, limbs, batch, L.n);
+    for (int j = 0; !square && j <= d1; ++j) rows_r(L.b[j], L.stride, 0, 1, limbs, batch, L.n);
+    for (int k = 0; k <= d0 + d1; ++k) rows_w(L.c[k], L.stride, 0, 1, limbs, batch, L.n);
+    return hipSuccess;
+}
 hipError_t launch_horner(const HornerLaunch &L, int limbs, int batch, hipStream_t) {
     g_stub_launches.fetch_add(1);
     for (int i = 0; i <= L.degree; ++i) rows_r(L.ct[i], L.ct_stride[i], 0, 1, limbs, batch, L.n);

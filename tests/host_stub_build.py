@@ -1,0 +1,29 @@
+"""The CPU build of the product's host side that the sanitizer tests share: every lattigo-fhe-by-go_amd/csrc/lr_abi_*.cpp, lr_host.hpp and
+lr_precompute.cpp, compiled with g++ against the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/ (hipstub.cpp,
+stub_launch.cpp), and linked with one driver from tests/cpp/."""
+import concurrent.futures as cf
+import glob
+import os
+import subprocess
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "lattigo-fhe-by-go_amd", "csrc")
+STUB = os.path.join(ROOT, "tests", "cpp", "hipstub")
+
+
+def build_host_driver(tmp, driver, flags, tag):
+    """Compiles the product units and tests/cpp/<driver>.cpp with `flags` into the directory `tmp`; returns the executable's path."""
+    units = sorted(glob.glob(os.path.join(CSRC, "lr_abi_*.cpp"))) + [os.path.join(CSRC, "lr_precompute.cpp"), os.path.join(STUB, "hipstub.cpp"),
+                                                                      os.path.join(STUB, "stub_launch.cpp"), os.path.join(ROOT, "tests", "cpp", driver + ".cpp")]
+    common = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-pthread", "-I" + STUB, "-I" + CSRC, "-I" + os.path.join(ROOT, "include")] + flags
+
+    def one(src):
+        obj = os.path.join(tmp, tag + "_" + os.path.basename(src) + ".o")
+        subprocess.check_call(common + ["-c", src, "-o", obj])
+        return obj
+    with cf.ThreadPoolExecutor(max_workers=6) as ex:
+        objs = list(ex.map(one, units))
+    exe = os.path.join(tmp, driver + "_" + tag)
+    subprocess.check_call(common + objs + ["-o", exe])
+    return exe

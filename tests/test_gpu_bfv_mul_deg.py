@@ -160,6 +160,9 @@ def test_refusals(gpu_pkg):
     assert code([P(3), P(3)], [P(3)], [P(3), P(3)]) == 3                        # batch above max_batch
     assert code(a, [b[0], P(limbs=len(Q) - 1)], o) == 3                         # limb mismatch
     assert code(a, [b[0], P(1)], o) == 3                                        # batch mismatch
+    with pytest.raises(nat.LatticeRingError) as e:                              # lr_bfv_mul: duplicate outputs
+        plan.Mul(a[:2], b, [o[0], o[1], o[0]])
+    assert e.value.code == 4 and "distinct" in str(e.value)
     # the plan stays usable after its refusals
     plan.MulDeg(a[:2], [b[0]], o[:2])
 

@@ -4,33 +4,12 @@ the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/ 
 mixing batched MulRelin / rotation requests, refused requests, an injected device failure in the middle of a batch, direct pipelines over
 shared contexts, scratch leases, handle churn and peer copies.  A sanitizer report fails the test; so does a caller that got another
 caller's result back (the stubs carry one tag word per poly through the pipelines)."""
-import concurrent.futures as cf
-import glob
 import os
 import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "lattigo-fhe-by-go_amd", "csrc")
-STUB = os.path.join(ROOT, "tests", "cpp", "hipstub")
-
-
-def _build(tmp, tag, flags):
-    units = sorted(glob.glob(os.path.join(CSRC, "lr_abi_*.cpp"))) + [os.path.join(CSRC, "lr_precompute.cpp"), os.path.join(STUB, "hipstub.cpp"),
-                                                                      os.path.join(STUB, "stub_launch.cpp"), os.path.join(ROOT, "tests", "cpp", "host_concurrency.cpp")]
-    common = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-pthread", "-I" + STUB, "-I" + CSRC, "-I" + os.path.join(ROOT, "include")] + flags
-
-    def one(src):
-        obj = os.path.join(tmp, tag + "_" + os.path.basename(src) + ".o")
-        subprocess.check_call(common + ["-c", src, "-o", obj])
-        return obj
-    with cf.ThreadPoolExecutor(max_workers=6) as ex:
-        objs = list(ex.map(one, units))
-    exe = os.path.join(tmp, "host_concurrency_" + tag)
-    subprocess.check_call(common + objs + ["-o", exe])
-    return exe
+from host_stub_build import build_host_driver
 
 
 @pytest.mark.parametrize("tag,flags,env", [
@@ -38,7 +17,7 @@ def _build(tmp, tag, flags):
     ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
 ])
 def test_host_concurrency_under_sanitizers(tmp_path, tag, flags, env):
-    exe = _build(str(tmp_path), tag, flags)
+    exe = build_host_driver(str(tmp_path), "host_concurrency", flags, tag)
     # no LR_* override may leak in from the caller's environment: the run is about the default paths
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}
     res = subprocess.run([exe, "64", "12"], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
