@@ -75,7 +75,7 @@ int batcher_run(lr_ckks_batcher *B, lr_ckks_batcher::Lane &lane, const std::vect
         LR_TRY(run_permute_ntt(cQ, L1, batch, nullptr, 0, pl->c0.d, s, reqs[0]->gen, tab));             // ckks/evaluator.go:1458
         LR_TRY(run_permute_ntt(cQ, L1, batch, nullptr, 0, pl->c2x.d, s, reqs[0]->gen, tab + batch));    // :1459
         KeySwitchEpilogue fin{lane.o0.d, lane.o1.d, s, pl->c0.d, nullptr, s};
-        LR_TRY(switch_keys_core(pl, level, batch, pl->c2x.d, s, reqs[0]->evk, pl->q1.d, s, pl->q2.d, s, &fin));   // :1464-1467
+        LR_TRY(switch_keys_core(pl, level, batch, pl->c2x.d, s, reqs[0]->evk, {{pl->q1.d, pl->q2.d}, {s, s}}, &fin));   // :1464-1467
     } else {
     LR_HIP(hipMemcpyAsync(lane.d_table, lane.h_table, (size_t)6 * mb * sizeof(u64 *), hipMemcpyHostToDevice, cQ->stream));
     TensorLaunch T{};

@@ -273,7 +273,7 @@ int moddown_pq_core(lr_bext *b, int level, const u64 *p1Q, long long p1Q_stride,
     LR_TRY(run_ext(cQ, b->pq, nP, pP, batch, segment(b->poolQ.d, pool_stride, 0, 0, level + 1), segment(nullptr, 0, 0, 0, 0)));
     if (ntt && ntt_epilogue_ok(cQ) && !cQ->opt.no_epilogue) {
         // NTT domain: the subtract-multiply rides in the forward transform's copy-out (the kernels the key switch uses for its ModDown,
-        // ks_accumulate) for every run of limbs that takes the epilogue; the other limbs keep the separate pass.  Nothing is added.
+        // ks_ntt_tail) for every run of limbs that takes the epilogue; the other limbs keep the separate pass.  Nothing is added.
         if (b->zerosQ.words < (size_t)pool_stride) {
             LR_TRY(b->zerosQ.ensure(cQ, (size_t)pool_stride));
             LR_HIP(hipMemsetAsync(b->zerosQ.d, 0, (size_t)pool_stride * sizeof(u64), cQ->stream));
@@ -448,72 +448,73 @@ extern "C" int lr_decomposer_destroy(lr_decomposer *d) {
 
 namespace lr_host {
 
-// Decompose (split == false, outP ignored) / DecomposeAndSplit.  in: rows of p0 (coefficient domain).
-// does digit `crt` at `level` go through the extension kernel (false: the trivial-copy branch, :490-497 / :613-623)?
-bool digit_is_extended(const lr_decomposer *d, int level, int crt) {
+// the one place that derives what digit `crt` of the decomposition is at `level` (ring_basis_extension.go:433, :490-497, :531-537):
+// decompose_core and every decision of the key switch (lr_abi_ckks.cpp) read it from here.  crt < beta, crt * alpha <= level.
+DigitShape digit_shape(const lr_decomposer *d, int level, int crt) {
     const int alphai = d->xalpha[crt];
-    const int ed = crt * d->alpha + alphai;
-    return !((ed > level + 1 && (level + 1) % d->nP == 1) || alphai == 1);
+    DigitShape g;
+    g.d0 = crt * d->alpha;
+    g.d1 = std::min(g.d0 + alphai, level + 1);
+    g.full = g.d1 - g.d0 == d->alpha;
+    // the trivial-copy branch, :490-497 / :613-623: one limb to reconstruct from
+    g.extended = !((g.d0 + alphai > level + 1 && (level + 1) % d->nP == 1) || alphai == 1);
+    g.index = level >= alphai + g.d0 ? alphai - 2 : (level - 1) % d->alpha;
+    g.modup = g.extended ? d->modup[crt][g.index].get() : nullptr;
+    return g;
 }
 
-// top: write the first forward stage over index bit logN - 1 instead of the plain extension (N = 2^16 key switch; split form only,
-// extended digits only -- the caller checks digit_is_extended and ext_top_supported)
-// skip_own: do not write the rows the digit owns (the key switch reads them from the NTT-domain input, or copies them in)
-int decompose_core(lr_decomposer *d, int level, int crt, Rows in, int batch, u64 *outQ, long long outQ_stride, u64 *outP,
-                   long long outP_stride, bool split, bool top, bool skip_own, std::vector<ExtPending> *collect,
-                   bool inv_top) {
+// Decompose (outP == nullptr: the special primes go to rows level+1.. of outQ) / DecomposeAndSplit.  in: rows of p0 (coefficient domain).
+// DigitExtension::top: write the first forward stage over index bit logN - 1 instead of the plain extension (N = 2^16 key switch; split form
+// only, extended digits only -- the caller checks DigitShape::extended and ext_top_supported)
+// DigitExtension::skip_own: do not write the rows the digit owns (the key switch reads them from the NTT-domain input, or copies them in)
+int decompose_core(lr_decomposer *d, int level, int crt, Rows in, int batch, Rows outQ, const Rows *outP, DigitExtension how) {
     lr_context *c = d->cQ;
     if (crt < 0 || crt >= d->beta) return fail(LR_ERR_SHAPE, "crtDecompLevel out of range");
     if (level < 0 || level + 1 > d->nQ) return fail(LR_ERR_SHAPE, "level out of range");
-    const int alphai = d->xalpha[crt];
-    const int st = crt * d->alpha, ed = st + alphai;
-    if (st > level) return fail(LR_ERR_SHAPE, "digit lies above the level");
+    if (crt * d->alpha > level) return fail(LR_ERR_SHAPE, "digit lies above the level");
+    const DigitShape g = digit_shape(d, level, crt);
+    const bool split = outP != nullptr;
     const int n = (int)c->h.N;
-    if ((ed > level + 1 && (level + 1) % d->nP == 1) || alphai == 1) {
-        if (top) return fail(LR_ERR_ARG, "top-stage extension requested for a digit that takes the copy branch");
+    if (!g.extended) {
+        if (how.top) return fail(LR_ERR_ARG, "top-stage extension requested for a digit that takes the copy branch");
         // no reconstruction needed: every target limb receives limb p0idxst, :490-497 / :613-623
         RowAddLaunch L;
-        L.in = in.base + (long long)(in.limb0 + st) * n;
+        L.in = in.base + (long long)(in.limb0 + g.d0) * n;
         L.in_stride = in.stride;
         L.n = n;
         L.q = 0;
         std::memset(&L.adds, 0, sizeof(L.adds));
-        L.out = outQ;
-        L.out_stride = outQ_stride;
+        L.out = outQ.base;
+        L.out_stride = outQ.stride;
         LR_HIP(launch_rowadd(L, split ? level + 1 : level + 1 + d->nP, batch, c->stream));
         if (split) {
-            L.out = outP;
-            L.out_stride = outP_stride;
+            L.out = outP->base;
+            L.out_stride = outP->stride;
             LR_HIP(launch_rowadd(L, d->nP, batch, c->stream));
         }
         return LR_OK;
     }
-    int index;
-    if (level >= alphai + crt * d->alpha) index = alphai - 2;
-    else index = (level - 1) % d->alpha;
-    const DevModup &m = *d->modup[crt][index];
     Rows digit = in;
-    digit.limb0 = in.limb0 + st;
+    digit.limb0 = in.limb0 + g.d0;
     // rows 0..level take table columns 0..level (the own-digit rows are rewritten by the
     // "index greater" loop of the reference, :571 / :687, so the copy at :553 / :669 is dead);
     // the special primes take columns nQ.., written to the P poly or to rows level+1.. of p1.
-    ExtSegment sq = segment(outQ, outQ_stride, 0, 0, level + 1);
-    ExtSegment sp = split ? segment(outP, outP_stride, 0, d->nQ, d->nP) : segment(outQ, outQ_stride, level + 1, d->nQ, d->nP);
-    if (top) {
+    ExtSegment sq = segment(outQ.base, outQ.stride, 0, 0, level + 1);
+    ExtSegment sp = split ? segment(outP->base, outP->stride, 0, d->nQ, d->nP) : segment(outQ.base, outQ.stride, level + 1, d->nQ, d->nP);
+    if (how.top) {
         if (!split) return fail(LR_ERR_ARG, "top-stage extension: split form only");
         sq.top_tw = d->cQ->d_fwd;      // rows 0..level of the Q part are the context's limbs 0..level
         sp.top_tw = d->cP->d_fwd;
     }
-    if (skip_own && split) {
-        // rows [st, own_end) are the digit's own: two Q segments around them
-        const int own_end = ed > level + 1 ? level + 1 : ed;
-        ExtSegment lo = segment(outQ, outQ_stride, 0, 0, st);
-        ExtSegment hi = segment(outQ, outQ_stride, own_end, own_end, level + 1 - own_end);
+    if (how.skip_own && split) {
+        // rows [d0, d1) are the digit's own: two Q segments around them
+        ExtSegment lo = segment(outQ.base, outQ.stride, 0, 0, g.d0);
+        ExtSegment hi = segment(outQ.base, outQ.stride, g.d1, g.d1, level + 1 - g.d1);
         lo.top_tw = hi.top_tw = sq.top_tw;
-        hi.top_mod0 = own_end;
-        return run_ext(c, m, index + 2, digit, batch, lo, hi, &sp, collect, inv_top);
+        hi.top_mod0 = g.d1;
+        return run_ext(c, *g.modup, g.n_in(), digit, batch, lo, hi, &sp, how.collect, how.inv_top);
     }
-    return run_ext(c, m, index + 2, digit, batch, sq, sp, nullptr, collect, inv_top);
+    return run_ext(c, *g.modup, g.n_in(), digit, batch, sq, sp, nullptr, how.collect, how.inv_top);
 }
 
 }  // namespace lr_host
@@ -524,7 +525,7 @@ extern "C" int lr_decompose(lr_decomposer *d, int level, int crt, const lr_poly 
     if (p0->limbs < level + 1 || p1->limbs < level + 1 + d->nP) return fail(LR_ERR_SHAPE, "Decompose: limb counts");
     if (p0->batch != p1->batch) return fail(LR_ERR_SHAPE, "batch mismatch");
     LR_HIP(hipSetDevice(d->cQ->device));
-    return decompose_core(d, level, crt, rows_of(p0), p1->batch, p1->d, p1->stride(), nullptr, 0, false);
+    return decompose_core(d, level, crt, rows_of(p0), p1->batch, rows_of(p1), nullptr);
     });
 }
 
@@ -535,6 +536,7 @@ extern "C" int lr_decompose_and_split(lr_decomposer *d, int level, int crt, cons
         return fail(LR_ERR_SHAPE, "DecomposeAndSplit: limb counts");
     if (p0->batch != p1Q->batch || p0->batch != p1P->batch) return fail(LR_ERR_SHAPE, "batch mismatch");
     LR_HIP(hipSetDevice(d->cQ->device));
-    return decompose_core(d, level, crt, rows_of(p0), p1Q->batch, p1Q->d, p1Q->stride(), p1P->d, p1P->stride(), true);
+    const Rows outP = rows_of(p1P);
+    return decompose_core(d, level, crt, rows_of(p0), p1Q->batch, rows_of(p1Q), &outP);
     });
 }

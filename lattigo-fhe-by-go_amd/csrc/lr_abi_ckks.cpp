@@ -149,24 +149,44 @@ int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long lon
     return LR_OK;
 }
 
-// Digit decomposition of switchKeysInPlace / RotateHoisted (ckks/evaluator.go:1503-1510, 1258-1272, 1561-1591):
-// pl->c2QiQ = [beta][batch][|Q|][N], pl->c2QiP = [beta][batch][|P|][N], both in the NTT domain.  The limbs a digit
-// owns are the NTT-domain input itself; they are copied into the digit only when `copy_own` (the hoisted path
-// permutes whole digits), otherwise the inner product reads them in place.
-// coeff_input (bfv.switchKeys, bfv/evaluator.go:736-770): cx is in the coefficient domain -- the digits are decomposed from cx itself
-// and the digits' own limbs are NTT(cx) (:753, kept in pl->c2); otherwise (ckks) cx is in the NTT domain, the digits come from
-// InvNTT(cx) and the own limbs are cx.
-int ks_decompose(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, bool copy_own, bool coeff_input) {
-    lr_context *cQ = pl->cQ, *cP = pl->cP;
-    lr_decomposer *dec = pl->dec;
-    const int nQ = cQ->h.L(), nP = cP->h.L(), n = (int)cQ->h.N;
-    const int alpha = dec->alpha;
-    const int beta = (level + 1 + alpha - 1) / alpha;  // :1508
-    const long long sQ = (long long)nQ * n, sP = (long long)nP * n;
-    const long long dQ = (long long)batch * sQ, dP = (long long)batch * sP;
-    LR_TRY(pl->c2QiQ.ensure(cQ, (size_t)beta * dQ));
-    LR_TRY(pl->c2.ensure(cQ, (size_t)batch * sQ));
-    LR_TRY(pl->c2QiP.ensure(cQ, (size_t)beta * dP));
+// ------------------------------------------------------------------------------------------
+// the key switch: ks_decompose, then ks_inner_product, then one of the two ModDown tails
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct KsSizes {
+    int beta;                    // digits at this level, :1508
+    long long sQ, sP, dQ, dP;    // words of one poly over Q / over P, and of one digit (`batch` polys) over Q / over P
+};
+KsSizes ks_sizes(const lr_ckks_plan *pl, int level, int batch) {
+    const int alpha = pl->dec->alpha;
+    const long long n = (long long)pl->cQ->h.N, sQ = pl->cQ->h.L() * n, sP = pl->cP->h.L() * n;
+    return {(level + 1 + alpha - 1) / alpha, sQ, sP, batch * sQ, batch * sP};
+}
+
+// where the decomposition's input is and where the limbs a digit owns come from
+enum class KsInput {
+    Ntt,          // ckks: cx in the NTT domain, the digits come from InvNTT(cx); the own limbs are cx itself, which the inner product reads in place
+    NttCopyOwn,   // the same with the own limbs copied into the digits (the hoisted path permutes whole digits), :1579-1584
+    Coeff,        // bfv.switchKeys, bfv/evaluator.go:736-770: cx in the coefficient domain -- the digits are decomposed from cx itself and the
+                  // own limbs are NTT(cx) (:753, kept in pl->c2)
+};
+
+// what ks_decompose launches, decided once from the level, the batch and the plan's options
+struct KsDecomposition {
+    KsSizes z;
+    int full;         // leading digits that own exactly alpha limbs at this level: their transforms share one launch
+    bool exttop;      // the digits' extensions apply the top stage of the forward transforms that follow them
+    bool invtop;      // ... and the last stage and the scaling of the inverse transform in front of them
+    bool staged;      // the extensions land in staging buffers and the transforms go out of place
+};
+KsDecomposition ks_plan_decomposition(const lr_ckks_plan *pl, int level, int batch, bool coeff_input) {
+    const lr_context *cQ = pl->cQ, *cP = pl->cP;
+    const lr_decomposer *dec = pl->dec;
+    const int nP = cP->h.L(), n = (int)cQ->h.N, alpha = dec->alpha;
+    KsDecomposition d;
+    d.z = ks_sizes(pl, level, batch);
+    const int beta = d.z.beta;
     // N = 2^16: a forward transform whose input and output rows are disjoint computes its top stage while loading (one
     // launch); in place it needs a separate streaming pass first.  The extensions therefore land in staging buffers of the
     // same shape and the transforms write the pools the consumers read.
@@ -178,98 +198,93 @@ int ks_decompose(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long lon
     // ... or, better, the extension itself applies the stage over index bit 15 (each of its threads holds the coefficients j and
     // j + N/2) and the plain sub-block kernels transform in place, reading their own half only.  Possible when every digit of
     // this level goes through the sum-form extension kernel (no trivial-copy digit).
-    bool exttop = (asm16 || asm15) && !pl->opt.no_exttop;
-    for (int i = 0; i < beta && exttop; ++i) {
-        if (!digit_is_extended(dec, level, i)) {
-            exttop = false;
-            break;
-        }
-        const int alphai = dec->xalpha[i];
-        const int index = level >= alphai + i * dec->alpha ? alphai - 2 : (level - 1) % dec->alpha;
-        exttop = ext_top_supported(dec->modup[i][index]->tables(), index + 2, n);
+    d.exttop = (asm16 || asm15) && !pl->opt.no_exttop;
+    // the digits' extensions apply the top stage of the transforms that follow them (exttop): then they also take the last stage and
+    // the scaling of the inverse transform in front of them (its sub-blocks leave the rows lazy; nothing else reads c2 on this path)
+    d.invtop = !coeff_input && !pl->opt.no_invtop && cQ->asm_inv >= 0;
+    d.full = 0;
+    for (int i = 0; i < beta; ++i) {
+        const DigitShape g = digit_shape(dec, level, i);
+        if (g.full && d.full == i) ++d.full;
+        d.exttop = d.exttop && g.extended && ext_top_supported(g.modup->tables(), g.n_in(), n);
+        d.invtop = d.invtop && g.extended && g.modup->invtop0 != nullptr && g.n_in() <= 8;
     }
-    const bool staged = asm16 && !exttop && !pl->opt.no_staging;
-    if (staged) {
+    d.invtop = d.invtop && d.exttop;
+    d.staged = asm16 && !d.exttop && !pl->opt.no_staging;
+    return d;
+}
+
+// Digit decomposition of switchKeysInPlace / RotateHoisted (ckks/evaluator.go:1503-1510, 1258-1272, 1561-1591) and of bfv.switchKeys:
+// pl->c2QiQ = [beta][batch][|Q|][N], pl->c2QiP = [beta][batch][|P|][N], both in the NTT domain, without the limbs a digit owns unless
+// KsInput::NttCopyOwn.
+int ks_decompose(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, KsInput input) {
+    lr_context *cQ = pl->cQ, *cP = pl->cP;
+    lr_decomposer *dec = pl->dec;
+    const int nP = cP->h.L(), n = (int)cQ->h.N, alpha = dec->alpha;
+    const bool coeff_input = input == KsInput::Coeff;
+    const KsDecomposition d = ks_plan_decomposition(pl, level, batch, coeff_input);
+    const int beta = d.z.beta;
+    const long long sQ = d.z.sQ, sP = d.z.sP, dQ = d.z.dQ, dP = d.z.dP;
+    const bool exttop = d.exttop;
+    LR_TRY(pl->c2QiQ.ensure(cQ, (size_t)beta * dQ));
+    LR_TRY(pl->c2.ensure(cQ, (size_t)batch * sQ));
+    LR_TRY(pl->c2QiP.ensure(cQ, (size_t)beta * dP));
+    if (d.staged) {
         LR_TRY(pl->stageQ.ensure(cQ, (size_t)beta * dQ));
         LR_TRY(pl->stageP.ensure(cQ, (size_t)beta * dP));
     }
-    u64 *const srcQ = staged ? pl->stageQ.d : pl->c2QiQ.d, *const srcP = staged ? pl->stageP.d : pl->c2QiP.d;
-    Rows cxr{const_cast<u64 *>(cx), cx_stride, 0, 1};
-    Rows c2r{pl->c2.d, sQ, 0, 1};
-    // the digits' extensions apply the top stage of the transforms that follow them (exttop): then they also take the last stage and
-    // the scaling of the inverse transform in front of them (its sub-blocks leave the rows lazy; nothing else reads c2 on this path)
-    bool invtop = exttop && !coeff_input && !pl->opt.no_invtop && cQ->asm_inv >= 0;
-    for (int i = 0; i < beta && invtop; ++i) {
-        const int alphai = dec->xalpha[i];
-        const int index = level >= alphai + i * dec->alpha ? alphai - 2 : (level - 1) % dec->alpha;
-        invtop = dec->modup[i][index]->invtop0 != nullptr && index + 2 <= 8;
-    }
-    LR_TRY(run_ntt(cQ, !coeff_input, cxr, c2r, 0, 1, level + 1, batch, 0, 0, nullptr, false, invtop));  // ckks :1503 (InvNTT) / bfv :753 (NTT)
-    if (coeff_input) {
-        // the decomposition reads the caller's coefficient-domain rows; the transformed copy serves the digits' own limbs
-        if (copy_own) return fail(LR_ERR_UNSUPPORTED, "coefficient-domain key switch: own limbs are read in place");
-        c2r = cxr;
-    }
-    int full = 0;   // leading digits that own exactly alpha limbs at this level: their transforms share one launch
-    std::vector<ExtPending> pending;   // the digits' extensions: independent, same shape -> one grouped launch (copy-branch digits launch at once)
+    u64 *const outQ = pl->c2QiQ.d, *const outP = pl->c2QiP.d;
+    u64 *const srcQ = d.staged ? pl->stageQ.d : outQ, *const srcP = d.staged ? pl->stageP.d : outP;     // where the extensions land
+
+    // the input transform: ckks :1503 (InvNTT) / bfv :753 (NTT)
+    const Rows cxr{const_cast<u64 *>(cx), cx_stride, 0, 1}, c2r{pl->c2.d, sQ, 0, 1};
+    LR_TRY(run_ntt(cQ, !coeff_input, cxr, c2r, 0, 1, level + 1, batch, 0, 0, nullptr, false, d.invtop));
+    // (bfv: the decomposition reads the caller's coefficient-domain rows; the transformed copy serves the digits' own limbs)
+    const Rows coeffs = coeff_input ? cxr : c2r;
+
+    // the digits' extensions: independent, same shape -> one grouped launch (copy-branch digits launch at once)
+    std::vector<ExtPending> pending;
     pending.reserve((size_t)beta);
+    const DigitExtension how{exttop, true, d.invtop, pl->opt.no_ext_group ? nullptr : &pending};
     for (int i = 0; i < beta; ++i) {
-        u64 *dq = pl->c2QiQ.d + (long long)i * dQ;
-        // decomposeAndSplitNTT, :1561-1591
-        LR_TRY(decompose_core(dec, level, i, c2r, batch, srcQ + (long long)i * dQ, sQ, srcP + (long long)i * dP, sP, true, exttop, true,
-                              pl->opt.no_ext_group ? nullptr : &pending, invtop));
-        const int d0 = i * alpha;
-        int d1 = d0 + dec->xalpha[i];
-        if (d1 > level + 1) d1 = level + 1;
-        if (copy_own)   // :1579-1584
-            LR_TRY(run_ewise(cQ, LR_COPY, d1 - d0, batch, cx + (long long)d0 * n, cx_stride, nullptr, 0, dq + (long long)d0 * n,
-                             sQ, nullptr, d0));
-        if (d1 - d0 == alpha && full == i) ++full;
+        const Rows digP{srcP + (long long)i * dP, sP, 0, 1};
+        LR_TRY(decompose_core(dec, level, i, coeffs, batch, Rows{srcQ + (long long)i * dQ, sQ, 0, 1}, &digP, how));    // decomposeAndSplitNTT, :1561-1591
+        if (input == KsInput::NttCopyOwn) {   // :1579-1584
+            const DigitShape g = digit_shape(dec, level, i);
+            LR_TRY(run_ewise(cQ, LR_COPY, g.d1 - g.d0, batch, cx + (long long)g.d0 * n, cx_stride, nullptr, 0,
+                             outQ + (long long)i * dQ + (long long)g.d0 * n, sQ, nullptr, g.d0));
+        }
     }
     LR_TRY(flush_ext(cQ, pending, batch, &pl->grouped_ext));
+
+    // the digits' forward transforms, every row but the own ones
+    auto outside_own = [&](int i) -> int {   // the rows below and above the own block of digit i (the digits that are not full: their own launches)
+        const DigitShape g = digit_shape(dec, level, i);
+        u64 *dq = outQ + (long long)i * dQ, *sq = srcQ + (long long)i * dQ;
+        LR_TRY(run_ntt(cQ, false, Rows{sq, sQ, 0, 1}, Rows{dq, sQ, 0, 1}, 0, 1, g.d0, batch, 0, 0, nullptr, exttop));
+        return run_ntt(cQ, false, Rows{sq, sQ, g.d1, 1}, Rows{dq, sQ, g.d1, 1}, g.d1, 1, level + 1 - g.d1, batch, 0, 0, nullptr, exttop);
+    };
+    auto p_rows = [&]() -> int {             // :1590, every digit's P rows: one launch
+        return run_ntt(cP, false, Rows{srcP, sP, 0, 1}, Rows{outP, sP, 0, 1}, 0, 1, nP, beta * batch, 0, 0, nullptr, exttop);
+    };
+    auto full_digits = [&]() -> int {        // the rows outside each full digit's own block, all full digits at once (grid z = digit)
+        if (d.full == 0 || level + 1 - alpha <= 0) return LR_OK;
+        return run_ntt(cQ, false, Rows{srcQ, sQ, 0, 1}, Rows{outQ, sQ, 0, 1}, 0, 1, level + 1 - alpha, d.full * batch, alpha, batch, nullptr, exttop);
+    };
     // the digits' P rows beside their Q rows (another kernel variant, so another launch: at a small batch each fills a fraction of the chip)
     PlanFork forkP(pl, nP * beta * batch);
     LR_TRY(forkP.rc);
-    auto partial_digits = [&]() -> int {   // the digits that own fewer than alpha limbs at this level: their own launches
-        for (int i = full; i < beta; ++i) {
-            u64 *dq = pl->c2QiQ.d + (long long)i * dQ, *sq = srcQ + (long long)i * dQ;
-            const int d0 = i * alpha;
-            int d1 = d0 + dec->xalpha[i];
-            if (d1 > level + 1) d1 = level + 1;
-            Rows lo{dq, sQ, 0, 1}, lo_in{sq, sQ, 0, 1};
-            LR_TRY(run_ntt(cQ, false, lo_in, lo, 0, 1, d0, batch, 0, 0, nullptr, exttop));                  // limbs below the digit
-            Rows hi{dq, sQ, d1, 1}, hi_in{sq, sQ, d1, 1};
-            LR_TRY(run_ntt(cQ, false, hi_in, hi, d1, 1, level + 1 - d1, batch, 0, 0, nullptr, exttop));     // limbs above the digit
-        }
-        return LR_OK;
-    };
     if (forkP.on) {
         // beside the full digits' grouped launch: the P rows and the partial digits' Q rows (PN16QP1761, one ciphertext: 70 + 34 us
         // next to 99 us)
-        Rows pr{pl->c2QiP.d, sP, 0, 1}, pr_in{srcP, sP, 0, 1};                   // :1590, every digit's P rows
-        LR_TRY(run_ntt(cP, false, pr_in, pr, 0, 1, nP, beta * batch, 0, 0, nullptr, exttop));
-        LR_TRY(partial_digits());
+        LR_TRY(p_rows());
+        for (int i = d.full; i < beta; ++i) LR_TRY(outside_own(i));
         forkP.back();
-    }
-    const bool p_rows_done = forkP.on;
-    if (full > 0 && level + 1 - alpha > 0) {
-        // limbs outside each digit's own block, all full digits at once (grid z = digit)
-        Rows in{srcQ, sQ, 0, 1}, all{pl->c2QiQ.d, sQ, 0, 1};
-        LR_TRY(run_ntt(cQ, false, in, all, 0, 1, level + 1 - alpha, full * batch, alpha, batch, nullptr, exttop));
-    }
-    for (int i = p_rows_done ? beta : full; i < beta; ++i) {
-        u64 *dq = pl->c2QiQ.d + (long long)i * dQ, *sq = srcQ + (long long)i * dQ;
-        const int d0 = i * alpha;
-        int d1 = d0 + dec->xalpha[i];
-        if (d1 > level + 1) d1 = level + 1;
-        Rows lo{dq, sQ, 0, 1}, lo_in{sq, sQ, 0, 1};
-        LR_TRY(run_ntt(cQ, false, lo_in, lo, 0, 1, d0, batch, 0, 0, nullptr, exttop));                  // limbs below the digit
-        Rows hi{dq, sQ, d1, 1}, hi_in{sq, sQ, d1, 1};
-        LR_TRY(run_ntt(cQ, false, hi_in, hi, d1, 1, level + 1 - d1, batch, 0, 0, nullptr, exttop));     // limbs above the digit
-    }
-    if (!p_rows_done) {
-        Rows pr{pl->c2QiP.d, sP, 0, 1}, pr_in{srcP, sP, 0, 1};                   // :1590, every digit's P rows
-        LR_TRY(run_ntt(cP, false, pr_in, pr, 0, 1, nP, beta * batch, 0, 0, nullptr, exttop));
+        LR_TRY(full_digits());
+    } else {
+        LR_TRY(full_digits());
+        for (int i = d.full; i < beta; ++i) LR_TRY(outside_own(i));
+        LR_TRY(p_rows());
     }
     return forkP.join();
 }
@@ -282,217 +297,197 @@ bool keymac_wide_ok(const lr_ckks_plan *pl, const lr_context *c, int beta) {
     return (u128)qmax * (u128)beta < ((u128)1 << 64);
 }
 
-// Inner product of the digits with a switching key and the two ModDownSplitedNTTPQ (:1511-1557 / :1339-1387).
-// digQ/digP: [beta][batch][|Q| resp. |P|][N]; own/own_stride: where the digits' own limbs live when they were not
-// copied (nullptr: inside digQ).
-int ks_accumulate(lr_ckks_plan *pl, int level, int batch, const u64 *digQ, const u64 *digP, const u64 *own, long long own_stride,
-                  const lr_poly *evk, u64 *p0, long long p0_stride, u64 *p1, long long p1_stride, const KeySwitchEpilogue *fin,
-                  bool coeff_out, u64 perm_gen) {
-    lr_context *cQ = pl->cQ, *cP = pl->cP;
-    const int nQ = cQ->h.L(), nP = cP->h.L(), n = (int)cQ->h.N;
-    const int alpha = pl->dec->alpha;
-    const int beta = (level + 1 + alpha - 1) / alpha;
-    if (evk->batch < 2 * beta || evk->limbs < nQ + nP) return fail(LR_ERR_SHAPE, "evaluation key: need batch >= 2*beta and |Q|+|P| limbs");
-    const long long sQ = (long long)nQ * n, sP = (long long)nP * n;
-    const long long dQ = (long long)batch * sQ, dP = (long long)batch * sP;
-    LR_TRY(pl->poolPP.ensure(cQ, (size_t)2 * batch * sP));   // P parts of both accumulators, [2][batch][|P|][N]
-    u64 *const pool2P = pl->poolPP.d, *const pool3P = pl->poolPP.d + (long long)batch * sP;
-    // sum over the digits of evakey[i][0/1] (*) c2_i, canonical, Q part then P part
-    {
-        KeyMacLaunch K;
-        K.tile8 = 0;
-        K.wide = 0;
-        K.perm_gen = (unsigned)(perm_gen & ((cQ->h.N << 1) - 1));      // hoisted rotations: the digits through the Galois permutation
-        K.logn = (int)cQ->h.logN;
-        if (K.perm_gen != 0 && own) return fail(LR_ERR_ARG, "permuted digits carry their own limbs");
-        K.key = evk->d;
-        K.key_poly_stride = evk->stride();
-        K.n = n;
-        K.beta = beta;
-        K.c2 = digQ;
-        K.c2_digit_stride = dQ;
-        K.c2_poly_stride = sQ;
-        K.key_limb0 = 0;
-        K.out0 = p0;
-        K.out1 = p1;
-        K.out_stride = p0_stride;
-        K.out1_stride = p1_stride;
-        K.lp = cQ->d_lp;
-        K.wide = keymac_wide_ok(pl, cQ, beta) ? 1 : 0;
-        K.own = own;
-        K.own_stride = own_stride;
-        K.alpha = own ? alpha : 0;
-        const KeyMacLaunch KQ = K;
-        K.c2 = digP;
-        K.c2_digit_stride = dP;
-        K.c2_poly_stride = sP;
-        K.key_limb0 = nQ;
-        K.out0 = pool2P;
-        K.out1 = pool3P;
-        K.out_stride = sP;
-        K.out1_stride = sP;
-        K.lp = cP->d_lp;
-        K.wide = keymac_wide_ok(pl, cP, beta) ? 1 : 0;
-        K.own = nullptr;
-        K.own_stride = 0;
-        K.alpha = 0;
-        // a small batch: the Q part and the P part as one launch (they share nothing and each is a few hundred workgroups)
-        hipError_t pe = hipErrorNotSupported;
-        if (!pl->opt.no_pair && (long long)batch * (level + 1) <= pl->opt.pair_max_workgroups) pe = launch_keymac_pair(KQ, level + 1, K, nP, batch, cQ->stream);
-        if (pe == hipErrorNotSupported) {
-            LR_HIP(launch_keymac(KQ, level + 1, batch, cQ->stream));
-            LR_HIP(launch_keymac(K, nP, batch, cQ->stream));
-        } else if (pe != hipSuccess) {
-            return fail(LR_ERR_HIP, std::string("launch_keymac_pair: ") + hipGetErrorString(pe));
-        }
-    }
-    lr_bext *bx = pl->bext;
-    if (coeff_out) {
-        // bfv.switchKeys' tail (bfv/evaluator.go:806-811): InvNTT over Q||P, then ModDownPQ in the coefficient domain (in place:
-        // the extension reads x where it stores, ExtSegment::epi_mode 1)
-        if (fin) return fail(LR_ERR_ARG, "coefficient-domain key switch: no epilogue");
-        Rows q0r{p0, p0_stride, 0, 1}, q1r{p1, p1_stride, 0, 1}, pr{pool2P, sP, 0, 1};
-        // the two accumulators as ONE batch where base + p * stride reaches both: laid out back to back (the relinearisation's pool), or
-        // one poly each at any distance (see lr_ckks_rescale)
-        auto words = [](const u64 *a, const u64 *b) { return (long long)(((intptr_t)b - (intptr_t)a) / (intptr_t)sizeof(u64)); };
-        const bool back_to_back = p0_stride == p1_stride && p1 == p0 + (long long)batch * p0_stride;
-        const bool one_each = batch == 1 && p0 != p1;
-        const bool pair = !pl->opt.no_pair && (back_to_back || one_each);
-        const long long pair_stride = back_to_back ? p0_stride : words(p0, p1);
-        if (pair) {
-            Rows qr{p0, pair_stride, 0, 1};
-            LR_TRY(run_ntt(cQ, true, qr, qr, 0, 1, level + 1, 2 * batch));
-        } else {
-            LR_TRY(run_ntt(cQ, true, q0r, q0r, 0, 1, level + 1, batch));
-            LR_TRY(run_ntt(cQ, true, q1r, q1r, 0, 1, level + 1, batch));
-        }
-        LR_TRY(run_ntt(cP, true, pr, pr, 0, 1, nP, 2 * batch));
-        const bool fused = !cQ->opt.no_epilogue && ext_epilogue_supported(bx->pq.tables(), nP, n);
-        if (pair && fused) {
-            ExtSegment sd = segment(p0, pair_stride, 0, 0, level + 1);
-            sd.epi_mode = 1;
-            sd.epi_x = p0;
-            sd.epi_x_stride = pair_stride;
-            sd.epi_c = bx->d_moddown_pq;
-            return run_ext(cQ, bx->pq, nP, pr, 2 * batch, sd, segment(nullptr, 0, 0, 0, 0));      // (pool2P / pool3P lie back to back)
-        }
-        for (int k = 0; k < 2; ++k) {
-            u64 *pq = k == 0 ? p0 : p1;
-            const long long pqs = k == 0 ? p0_stride : p1_stride;
-            Rows pk{k == 0 ? pool2P : pool3P, sP, 0, 1};
-            if (fused) {
-                ExtSegment sd = segment(pq, pqs, 0, 0, level + 1);
-                sd.epi_mode = 1;
-                sd.epi_x = pq;
-                sd.epi_x_stride = pqs;
-                sd.epi_c = bx->d_moddown_pq;
-                LR_TRY(run_ext(cQ, bx->pq, nP, pk, batch, sd, segment(nullptr, 0, 0, 0, 0)));
-            } else {
-                LR_TRY(bx->poolQ.ensure(cQ, (size_t)batch * sQ));
-                LR_TRY(run_ext(cQ, bx->pq, nP, pk, batch, segment(bx->poolQ.d, sQ, 0, 0, level + 1), segment(nullptr, 0, 0, 0, 0)));
-                LR_TRY(run_submul(cQ, level + 1, batch, pq, pqs, bx->poolQ.d, sQ, (long long)n, pq, pqs, bx->d_moddown_pq, false, nullptr));
-            }
-        }
-        return LR_OK;
-    }
-    // ModDownSplitedNTTPQ x2; the two calls share every launch up to the final subtract-multiply
-    {
-        Rows pr{pool2P, sP, 0, 1};
-        LR_TRY(bx->poolQ.ensure(cQ, (size_t)2 * batch * sQ));
-        u64 *ext_out = bx->poolQ.d;
-        const bool asm16 = cQ->h.logN == 16 && cQ->use_asm && cQ->asm_fwd >= 0;
-        const bool asm15 = cQ->h.logN == 15 && ntt_split15(cQ, (long long)(level + 1) * batch);     // (one launch per component)
-        const bool exttop = (asm16 || asm15) && !pl->opt.no_exttop && ext_top_supported(bx->pq.tables(), nP, n);
-        if (asm16 && !exttop && !pl->opt.no_staging) {
-            LR_TRY(pl->stageQ.ensure(cQ, (size_t)2 * batch * sQ));     // (the digits' staging area is free again)
-            ext_out = pl->stageQ.d;
-        }
-        ExtSegment mseg = segment(ext_out, sQ, 0, 0, level + 1);
-        if (exttop) mseg.top_tw = cQ->d_fwd;                           // the ModDown transform's top stage inside the extension
-        // ... and the last stage of the inverse transform in front of it (see ks_decompose)
-        const bool invtop = exttop && !pl->opt.no_invtop && cP->asm_inv >= 0 && bx->pq.invtop0 != nullptr && nP <= 8;
-        LR_TRY(run_ntt(cP, true, pr, pr, 0, 1, nP, 2 * batch, 0, 0, nullptr, false, invtop));
-        LR_TRY(run_ext(cQ, bx->pq, nP, pr, 2 * batch, mseg, segment(nullptr, 0, 0, 0, 0), nullptr, nullptr, invtop));
-        Rows qr{bx->poolQ.d, sQ, 0, 1}, qr_in{ext_out, sQ, 0, 1};
-        if (ntt_epilogue_ok(cQ)) {
-            // the subtract-multiply and the addition of MulRelin / the rotations inside the forward transform's copy-out, for
-            // every run of limbs below 2^46 (FP64 body); the other limbs keep the separate pass
-            const long long n64 = (long long)n;
-            // without `fin` (plain SwitchKeysInPlace) the results replace p0 / p1 and nothing is added
-            u64 *const outs[2] = {fin ? fin->out0 : p0, fin ? fin->out1 : p1};
-            const long long out_strides[2] = {fin ? fin->out_stride : p0_stride, fin ? fin->out_stride : p1_stride};
-            const u64 *const pluses[2] = {fin ? fin->plus0 : nullptr, fin ? fin->plus1 : nullptr};
-            const long long plus_stride = fin ? fin->plus_stride : 0;
-            const bool need_zeros = !pluses[0] || !pluses[1];
-            if (need_zeros && pl->zerosQ.words < (size_t)sQ) {
-                LR_TRY(pl->zerosQ.ensure(cQ, (size_t)sQ));
-                LR_HIP(hipMemsetAsync(pl->zerosQ.d, 0, (size_t)sQ * sizeof(u64), cQ->stream));
-            }
-            int l0 = 0;
-            while (l0 <= level) {
-                const bool fpc = ntt_epilogue_limb(cQ, l0);
-                int l1 = l0 + 1;
-                while (l1 <= level && ntt_epilogue_limb(cQ, l1) == fpc) ++l1;
-                if (fpc && batch == 1 && !pl->opt.no_pair && outs[0] != outs[1]) {
-                    // one ciphertext: the two components as a batch of two whose strides are the distances between their operands
-                    // (ext_out holds them back to back; x, plus and the outputs are separate allocations) -- one launch instead of two
-                    auto words = [](const u64 *a, const u64 *b) { return (long long)(((intptr_t)b - (intptr_t)a) / (intptr_t)sizeof(u64)); };
-                    Rows src{ext_out, sQ, l0, 1};
-                    Rows dst{outs[0], words(outs[0], outs[1]), l0, 1};
-                    // (a component without an addend -- the rotations' second one -- adds the row of zeros: one more distance)
-                    const u64 *plus_a = pluses[0] ? pluses[0] : pl->zerosQ.d, *plus_b = pluses[1] ? pluses[1] : pl->zerosQ.d;
-                    const NttEpilogue ep{p0, words(p0, p1), plus_a, words(plus_a, plus_b), bx->d_moddown_pq_epi};
-                    LR_TRY(run_ntt(cQ, false, src, dst, l0, 1, l1 - l0, 2, 0, 0, &ep, exttop));
-                } else if (fpc) {
-                    // the two components are independent launches: side by side while one alone leaves most of the chip idle
-                    PlanFork fork1(pl, (l1 - l0) * batch);
-                    LR_TRY(fork1.rc);
-                    for (int k = 1; k >= 0; --k) {
-                        Rows src{ext_out + (long long)k * batch * sQ, sQ, l0, 1};
-                        Rows dst{outs[k], out_strides[k], l0, 1};
-                        const u64 *plus = pluses[k];
-                        const NttEpilogue ep{k == 0 ? p0 : p1, k == 0 ? p0_stride : p1_stride, plus ? plus : pl->zerosQ.d,
-                                             plus ? plus_stride : 0, bx->d_moddown_pq_epi};
-                        LR_TRY(run_ntt(cQ, false, src, dst, l0, 1, l1 - l0, batch, 0, 0, &ep, exttop));
-                        fork1.back();
-                    }
-                    LR_TRY(fork1.join());
-                } else {
-                    Rows src{ext_out, sQ, l0, 1}, dst{bx->poolQ.d, sQ, l0, 1};
-                    LR_TRY(run_ntt(cQ, false, src, dst, l0, 1, l1 - l0, 2 * batch, 0, 0, nullptr, exttop));
-                    for (int k = 0; k < 2; ++k) {
-                        const u64 *pq = (k == 0 ? p0 : p1) + l0 * n64;
-                        const u64 *ext = bx->poolQ.d + (long long)k * batch * sQ + l0 * n64;
-                        const u64 *plus = pluses[k];
-                        LR_TRY(run_submul(cQ, l1 - l0, batch, pq, k == 0 ? p0_stride : p1_stride, ext, sQ, n64,
-                                          outs[k] + l0 * n64, out_strides[k], bx->d_moddown_pq + l0, false,
-                                          nullptr, plus ? plus + l0 * n64 : nullptr, plus_stride, nullptr, l0));
-                    }
-                }
-                l0 = l1;
-            }
-            return LR_OK;
-        }
-        LR_TRY(run_ntt(cQ, false, qr_in, qr, 0, 1, level + 1, 2 * batch, 0, 0, nullptr, exttop));
-    }
-    for (int k = 0; k < 2; ++k) {
-        u64 *pq = k == 0 ? p0 : p1;
-        const long long pqs = k == 0 ? p0_stride : p1_stride;
-        const u64 *ext = bx->poolQ.d + (long long)k * batch * sQ;
-        if (fin)
-            LR_TRY(run_submul(cQ, level + 1, batch, pq, pqs, ext, sQ, (long long)n, k == 0 ? fin->out0 : fin->out1,
-                              fin->out_stride, bx->d_moddown_pq, false, nullptr, k == 0 ? fin->plus0 : fin->plus1, fin->plus_stride));
-        else
-            LR_TRY(run_submul(cQ, level + 1, batch, pq, pqs, ext, sQ, (long long)n, pq, pqs, bx->d_moddown_pq, false, nullptr));
+// The digits the inner product reads: [beta][batch][|Q| resp. |P|][N].  Either they lack the limbs they own, which are then read from the
+// key switch's NTT-domain input (in_place), or they carry them and may be read through a Galois permutation (whole).  The kernel has no
+// permuted read of `own`: build a KsDigits with one of the two factories, which never combine the two.
+struct KsDigits {
+    const u64 *Q, *P;
+    const u64 *own;           // nullptr: inside Q
+    long long own_stride;
+    u64 perm_gen;             // hoisted rotations: the Galois element the digits are read through (KeyMacLaunch::perm_gen); 0 = as they are
+    static KsDigits in_place(const lr_ckks_plan *pl, const u64 *own, long long own_stride) { return {pl->c2QiQ.d, pl->c2QiP.d, own, own_stride, 0}; }
+    static KsDigits whole(const u64 *Q, const u64 *P, u64 perm_gen = 0) { return {Q, P, nullptr, 0, perm_gen}; }
+};
+
+// the P part of the inner product from its Q part: the digits' P rows and the key's limbs |Q|.. into the two halves of poolPP
+KeyMacLaunch keymac_p_part(const lr_ckks_plan *pl, KeyMacLaunch K, const KsSizes &z, const u64 *digP, u64 *pool2P, u64 *pool3P) {
+    K.c2 = digP; K.c2_digit_stride = z.dP; K.c2_poly_stride = z.sP;
+    K.key_limb0 = pl->cQ->h.L();
+    K.out0 = pool2P; K.out1 = pool3P; K.out_stride = K.out1_stride = z.sP;
+    K.lp = pl->cP->d_lp;
+    K.wide = keymac_wide_ok(pl, pl->cP, z.beta) ? 1 : 0;
+    K.own = nullptr; K.own_stride = 0; K.alpha = 0;
+    return K;
+}
+
+// Inner product of the digits with a switching key (:1511-1535 / :1339-1365): acc <- the Q parts, pl->poolPP = [2][batch][|P|][N] <- the
+// P parts of sum over the digits of evakey[i][0/1] (*) c2_i, canonical
+int ks_inner_product(lr_ckks_plan *pl, int level, int batch, const KsDigits &dig, const lr_poly *evk, const KeySwitchAcc &acc) {
+    lr_context *cQ = pl->cQ;
+    const int nQ = cQ->h.L(), nP = pl->cP->h.L();
+    const KsSizes z = ks_sizes(pl, level, batch);
+    if (evk->batch < 2 * z.beta || evk->limbs < nQ + nP) return fail(LR_ERR_SHAPE, "evaluation key: need batch >= 2*beta and |Q|+|P| limbs");
+    LR_TRY(pl->poolPP.ensure(cQ, (size_t)2 * batch * z.sP));
+    KeyMacLaunch KQ;
+    KQ.tile8 = 0;
+    KQ.perm_gen = (unsigned)(dig.perm_gen & ((cQ->h.N << 1) - 1));
+    KQ.n = (int)cQ->h.N; KQ.logn = (int)cQ->h.logN; KQ.beta = z.beta;
+    KQ.key = evk->d; KQ.key_poly_stride = evk->stride(); KQ.key_limb0 = 0;
+    KQ.c2 = dig.Q; KQ.c2_digit_stride = z.dQ; KQ.c2_poly_stride = z.sQ;
+    KQ.out0 = acc.p[0]; KQ.out1 = acc.p[1]; KQ.out_stride = acc.stride[0]; KQ.out1_stride = acc.stride[1];
+    KQ.lp = cQ->d_lp;
+    KQ.wide = keymac_wide_ok(pl, cQ, z.beta) ? 1 : 0;
+    KQ.own = dig.own; KQ.own_stride = dig.own_stride; KQ.alpha = dig.own ? pl->dec->alpha : 0;
+    const KeyMacLaunch KP = keymac_p_part(pl, KQ, z, dig.P, pl->poolPP.d, pl->poolPP.d + (long long)batch * z.sP);
+    // a small batch: the Q part and the P part as one launch (they share nothing and each is a few hundred workgroups)
+    hipError_t pe = hipErrorNotSupported;
+    if (!pl->opt.no_pair && (long long)batch * (level + 1) <= pl->opt.pair_max_workgroups) pe = launch_keymac_pair(KQ, level + 1, KP, nP, batch, cQ->stream);
+    if (pe == hipErrorNotSupported) {
+        LR_HIP(launch_keymac(KQ, level + 1, batch, cQ->stream));
+        LR_HIP(launch_keymac(KP, nP, batch, cQ->stream));
+    } else if (pe != hipSuccess) {
+        return fail(LR_ERR_HIP, std::string("launch_keymac_pair: ") + hipGetErrorString(pe));
     }
     return LR_OK;
 }
 
-// switchKeysInPlace, ckks/evaluator.go:1475-1558, on raw buffers: cx/p0/p1 have `q_stride` between batch polys
-int switch_keys_core(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, u64 *p0,
-                     long long p0_stride, u64 *p1, long long p1_stride, const KeySwitchEpilogue *fin) {
-    LR_TRY(ks_decompose(pl, level, batch, cx, cx_stride, false));
-    return ks_accumulate(pl, level, batch, pl->c2QiQ.d, pl->c2QiP.d, cx, cx_stride, evk, p0, p0_stride, p1, p1_stride, fin);
+// bfv.switchKeys' tail (bfv/evaluator.go:806-811): InvNTT over Q||P, then ModDownPQ in the coefficient domain (in place: the extension
+// reads x where it stores, ExtSegment::epi_mode 1).  acc / pl->poolPP as ks_inner_product left them.
+int ks_coeff_tail(lr_ckks_plan *pl, int level, int batch, const KeySwitchAcc &acc) {
+    lr_context *cQ = pl->cQ, *cP = pl->cP;
+    lr_bext *bx = pl->bext;
+    const int nP = cP->h.L(), n = (int)cQ->h.N;
+    const KsSizes z = ks_sizes(pl, level, batch);
+    u64 *const poolP[2] = {pl->poolPP.d, pl->poolPP.d + z.dP};
+    const Rows pr{poolP[0], z.sP, 0, 1};
+    // the two accumulators as ONE batch where they can be (the relinearisation's pool lies back to back; one poly each at any distance)
+    const ComponentPair both = component_pair(acc.p[0], acc.stride[0], acc.p[1], acc.stride[1], batch);
+    const bool pair = !pl->opt.no_pair && both;
+    if (pair) {
+        const Rows qr{acc.p[0], both.stride, 0, 1};
+        LR_TRY(run_ntt(cQ, true, qr, qr, 0, 1, level + 1, 2 * batch));
+    } else {
+        for (int k = 0; k < 2; ++k) {
+            const Rows qr{acc.p[k], acc.stride[k], 0, 1};
+            LR_TRY(run_ntt(cQ, true, qr, qr, 0, 1, level + 1, batch));
+        }
+    }
+    LR_TRY(run_ntt(cP, true, pr, pr, 0, 1, nP, 2 * batch));
+    const bool fused = !cQ->opt.no_epilogue && ext_epilogue_supported(bx->pq.tables(), nP, n);
+    auto moddown = [&](u64 *x, long long x_stride, const Rows &p, int polys) -> int {
+        if (!fused) {
+            LR_TRY(bx->poolQ.ensure(cQ, (size_t)polys * z.sQ));
+            LR_TRY(run_ext(cQ, bx->pq, nP, p, polys, segment(bx->poolQ.d, z.sQ, 0, 0, level + 1), segment(nullptr, 0, 0, 0, 0)));
+            return run_submul(cQ, level + 1, polys, x, x_stride, bx->poolQ.d, z.sQ, (long long)n, x, x_stride, bx->d_moddown_pq, false, nullptr);
+        }
+        ExtSegment sd = segment(x, x_stride, 0, 0, level + 1);
+        sd.epi_mode = 1;
+        sd.epi_x = x;
+        sd.epi_x_stride = x_stride;
+        sd.epi_c = bx->d_moddown_pq;
+        return run_ext(cQ, bx->pq, nP, p, polys, sd, segment(nullptr, 0, 0, 0, 0));
+    };
+    if (pair && fused) return moddown(acc.p[0], both.stride, pr, 2 * batch);      // (the two halves of poolPP lie back to back)
+    for (int k = 0; k < 2; ++k) LR_TRY(moddown(acc.p[k], acc.stride[k], Rows{poolP[k], z.sP, 0, 1}, batch));
+    return LR_OK;
+}
+
+// ModDownSplitedNTTPQ x2 (:1537-1557 / :1367-1387); the two calls share every launch up to the final subtract-multiply.
+// acc / pl->poolPP as ks_inner_product left them; without `fin` (plain SwitchKeysInPlace) the results replace acc and nothing is added.
+int ks_ntt_tail(lr_ckks_plan *pl, int level, int batch, const KeySwitchAcc &acc, const KeySwitchEpilogue *fin) {
+    lr_context *cQ = pl->cQ, *cP = pl->cP;
+    lr_bext *bx = pl->bext;
+    const int nP = cP->h.L(), n = (int)cQ->h.N;
+    const long long n64 = (long long)n;
+    const KsSizes z = ks_sizes(pl, level, batch);
+    const long long sQ = z.sQ;
+    // the two components: x - ext goes, times the ModDown constant and plus the addend, to out
+    struct Component {
+        const u64 *x;
+        u64 *out;
+        const u64 *plus;      // nullptr: none (the rotations' second component)
+        long long x_stride, out_stride, plus_stride;
+    };
+    const Component comp[2] = {
+        {acc.p[0], fin ? fin->out0 : acc.p[0], fin ? fin->plus0 : nullptr, acc.stride[0], fin ? fin->out_stride : acc.stride[0], fin ? fin->plus_stride : 0},
+        {acc.p[1], fin ? fin->out1 : acc.p[1], fin ? fin->plus1 : nullptr, acc.stride[1], fin ? fin->out_stride : acc.stride[1], fin ? fin->plus_stride : 0}};
+    const Rows pr{pl->poolPP.d, z.sP, 0, 1};
+    LR_TRY(bx->poolQ.ensure(cQ, (size_t)2 * batch * sQ));
+    u64 *ext_out = bx->poolQ.d;
+    const bool asm16 = cQ->h.logN == 16 && cQ->use_asm && cQ->asm_fwd >= 0;
+    const bool asm15 = cQ->h.logN == 15 && ntt_split15(cQ, (long long)(level + 1) * batch);     // (one launch per component)
+    const bool exttop = (asm16 || asm15) && !pl->opt.no_exttop && ext_top_supported(bx->pq.tables(), nP, n);
+    if (asm16 && !exttop && !pl->opt.no_staging) {
+        LR_TRY(pl->stageQ.ensure(cQ, (size_t)2 * batch * sQ));     // (the digits' staging area is free again)
+        ext_out = pl->stageQ.d;
+    }
+    ExtSegment mseg = segment(ext_out, sQ, 0, 0, level + 1);
+    if (exttop) mseg.top_tw = cQ->d_fwd;                           // the ModDown transform's top stage inside the extension
+    // ... and the last stage of the inverse transform in front of it (see ks_plan_decomposition)
+    const bool invtop = exttop && !pl->opt.no_invtop && cP->asm_inv >= 0 && bx->pq.invtop0 != nullptr && nP <= 8;
+    LR_TRY(run_ntt(cP, true, pr, pr, 0, 1, nP, 2 * batch, 0, 0, nullptr, false, invtop));
+    LR_TRY(run_ext(cQ, bx->pq, nP, pr, 2 * batch, mseg, segment(nullptr, 0, 0, 0, 0), nullptr, nullptr, invtop));
+    // limbs [l0, l1): both components' forward transform in one launch, then the separate subtract-multiply passes
+    auto transform_then_submul = [&](int l0, int l1) -> int {
+        LR_TRY(run_ntt(cQ, false, Rows{ext_out, sQ, l0, 1}, Rows{bx->poolQ.d, sQ, l0, 1}, l0, 1, l1 - l0, 2 * batch, 0, 0, nullptr, exttop));
+        for (int k = 0; k < 2; ++k) {
+            const Component &c = comp[k];
+            LR_TRY(run_submul(cQ, l1 - l0, batch, c.x + l0 * n64, c.x_stride, bx->poolQ.d + (long long)k * batch * sQ + l0 * n64, sQ, n64, c.out + l0 * n64,
+                              c.out_stride, bx->d_moddown_pq + l0, false, nullptr, c.plus ? c.plus + l0 * n64 : nullptr, c.plus_stride, nullptr, l0));
+        }
+        return LR_OK;
+    };
+    if (!ntt_epilogue_ok(cQ)) return transform_then_submul(0, level + 1);
+    // the subtract-multiply and the addition of MulRelin / the rotations inside the forward transform's copy-out, for
+    // every run of limbs below 2^46 (FP64 body); the other limbs keep the separate pass
+    if ((!comp[0].plus || !comp[1].plus) && pl->zerosQ.words < (size_t)sQ) {
+        LR_TRY(pl->zerosQ.ensure(cQ, (size_t)sQ));
+        LR_HIP(hipMemsetAsync(pl->zerosQ.d, 0, (size_t)sQ * sizeof(u64), cQ->stream));
+    }
+    // (a component without an addend adds the row of zeros)
+    const NttEpilogue ep[2] = {
+        {comp[0].x, comp[0].x_stride, comp[0].plus ? comp[0].plus : pl->zerosQ.d, comp[0].plus ? comp[0].plus_stride : 0, bx->d_moddown_pq_epi},
+        {comp[1].x, comp[1].x_stride, comp[1].plus ? comp[1].plus : pl->zerosQ.d, comp[1].plus ? comp[1].plus_stride : 0, bx->d_moddown_pq_epi}};
+    // one ciphertext: the two components as a batch of two whose strides are the distances between their operands (ext_out holds them
+    // back to back; x, plus and the outputs are separate allocations) -- one launch instead of two
+    const ComponentPair outs = component_pair(comp[0].out, comp[0].out_stride, comp[1].out, comp[1].out_stride, batch);
+    const bool pair = batch == 1 && !pl->opt.no_pair && outs;
+    for (int l0 = 0, l1; l0 <= level; l0 = l1) {
+        const bool fpc = ntt_epilogue_limb(cQ, l0);
+        for (l1 = l0 + 1; l1 <= level && ntt_epilogue_limb(cQ, l1) == fpc; ++l1) {}
+        if (!fpc) {
+            LR_TRY(transform_then_submul(l0, l1));
+        } else if (pair) {
+            const NttEpilogue both{ep[0].x, component_distance(ep[0].x, ep[1].x), ep[0].plus, component_distance(ep[0].plus, ep[1].plus), ep[0].consts};
+            LR_TRY(run_ntt(cQ, false, Rows{ext_out, sQ, l0, 1}, Rows{comp[0].out, outs.stride, l0, 1}, l0, 1, l1 - l0, 2, 0, 0, &both, exttop));
+        } else {
+            // the two components are independent launches: side by side while one alone leaves most of the chip idle
+            PlanFork fork1(pl, (l1 - l0) * batch);
+            LR_TRY(fork1.rc);
+            for (int k = 1; k >= 0; --k) {
+                LR_TRY(run_ntt(cQ, false, Rows{ext_out + (long long)k * batch * sQ, sQ, l0, 1}, Rows{comp[k].out, comp[k].out_stride, l0, 1}, l0, 1, l1 - l0, batch,
+                               0, 0, &ep[k], exttop));
+                fork1.back();
+            }
+            LR_TRY(fork1.join());
+        }
+    }
+    return LR_OK;
+}
+
+// the inner product and the NTT-domain tail: what follows the decomposition in every CKKS key switch
+int ks_product_and_ntt_tail(lr_ckks_plan *pl, int level, int batch, const KsDigits &dig, const lr_poly *evk, const KeySwitchAcc &acc, const KeySwitchEpilogue *fin) {
+    LR_TRY(ks_inner_product(pl, level, batch, dig, evk, acc));
+    return ks_ntt_tail(pl, level, batch, acc, fin);
+}
+
+}  // namespace
+
+// switchKeysInPlace, ckks/evaluator.go:1475-1558, on raw buffers
+int switch_keys_core(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc,
+                     const KeySwitchEpilogue *fin) {
+    LR_TRY(ks_decompose(pl, level, batch, cx, cx_stride, KsInput::Ntt));
+    return ks_product_and_ntt_tail(pl, level, batch, KsDigits::in_place(pl, cx, cx_stride), evk, acc, fin);
 }
 
 int check_ct(const lr_ckks_plan *pl, int level, const lr_poly *p, int batch) {
@@ -503,35 +498,51 @@ int check_ct(const lr_ckks_plan *pl, int level, const lr_poly *p, int batch) {
     return LR_OK;
 }
 
+namespace {
+// The checks the pipelines' entry points share, after their null checks.  The first that fails decides the code a doubly wrong call gets,
+// so each entry point keeps the order it always had: most are check_call; lr_bfv_switch_keys and lr_bfv_relinearize ask in another.
+int check_batch(const lr_ckks_plan *pl, int batch) {
+    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
+    return LR_OK;
+}
+int check_cts(const lr_ckks_plan *pl, int level, int batch, std::initializer_list<const lr_poly *> cts) {
+    for (const lr_poly *p : cts) LR_TRY(check_ct(pl, level, p, batch));
+    return LR_OK;
+}
+int check_call(const lr_ckks_plan *pl, int level, int batch, std::initializer_list<const lr_poly *> cts) {
+    if (level < 0 || level + 1 > pl->cQ->h.L()) return fail(LR_ERR_SHAPE, "level out of range");
+    LR_TRY(check_batch(pl, batch));
+    return check_cts(pl, level, batch, cts);
+}
+// a pipeline that interleaves launches of both contexts: they must be on one stream; the plan's device becomes current
+int begin_pipeline(const lr_ckks_plan *pl) {
+    LR_TRY(same_stream(pl->cQ, pl->cP));
+    LR_HIP(hipSetDevice(pl->device));
+    return LR_OK;
+}
+}  // namespace
+
 }  // namespace lr_host
 
 extern "C" int lr_ckks_switch_keys(lr_ckks_plan *pl, int level, const lr_poly *cx, const lr_poly *evk, lr_poly *p0, lr_poly *p1) {
     return guarded([&]() -> int {
     if (!pl || !cx || !evk || !p0 || !p1) return fail(LR_ERR_ARG, "null argument");
-    if (level < 0 || level + 1 > pl->cQ->h.L()) return fail(LR_ERR_SHAPE, "level out of range");
     const int batch = cx->batch;
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    LR_TRY(check_ct(pl, level, cx, batch));
-    LR_TRY(check_ct(pl, level, p0, batch));
-    LR_TRY(check_ct(pl, level, p1, batch));
-    LR_TRY(same_stream(pl->cQ, pl->cP));
-    LR_HIP(hipSetDevice(pl->cQ->device));
-    return switch_keys_core(pl, level, batch, cx->d, cx->stride(), evk, p0->d, p0->stride(), p1->d, p1->stride());
+    LR_TRY(check_call(pl, level, batch, {cx, p0, p1}));
+    LR_TRY(begin_pipeline(pl));
+    return switch_keys_core(pl, level, batch, cx->d, cx->stride(), evk, {{p0->d, p1->d}, {p0->stride(), p1->stride()}});
     });
 }
 
-// permuteNTT (ckks/evaluator.go:1448-1468): RotateColumns with a specific rotation key / Conjugate.
-// gen = the Galois element (ring.PermuteNTTIndex's `gen^power`); the two trailing Context calls (:1466-1467)
-// ride on the last ModDown pass.
 // bfv.evaluator.switchKeys (bfv/evaluator.go:736-812): cx in the coefficient domain over all of Q, evk over Q||P in the NTT +
 // Montgomery domain like the reference's SwitchingKey; p0 / p1 <- the two key-switched polys over Q, coefficient domain.  Same
 // machinery as the CKKS key switch (one plan over contextQ / contextP serves both), with the transforms the other way round.
-static int bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, u64 *p0,
-                                long long p0_stride, u64 *p1, long long p1_stride) {
+static int bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc) {
     const int level = pl->cQ->h.L() - 1;
-    LR_TRY(ks_decompose(pl, level, batch, cx, cx_stride, false, true));
+    LR_TRY(ks_decompose(pl, level, batch, cx, cx_stride, KsInput::Coeff));
     const long long sQ = (long long)pl->cQ->h.L() * (long long)pl->cQ->h.N;
-    return ks_accumulate(pl, level, batch, pl->c2QiQ.d, pl->c2QiP.d, pl->c2.d, sQ, evk, p0, p0_stride, p1, p1_stride, nullptr, true);
+    LR_TRY(ks_inner_product(pl, level, batch, KsDigits::in_place(pl, pl->c2.d, sQ), evk, acc));
+    return ks_coeff_tail(pl, level, batch, acc);
 }
 
 extern "C" int lr_bfv_switch_keys(lr_ckks_plan *pl, const lr_poly *cx, const lr_poly *evk, lr_poly *p0, lr_poly *p1) {
@@ -539,13 +550,10 @@ extern "C" int lr_bfv_switch_keys(lr_ckks_plan *pl, const lr_poly *cx, const lr_
     if (!pl || !cx || !evk || !p0 || !p1) return fail(LR_ERR_ARG, "null argument");
     const int level = pl->cQ->h.L() - 1;
     if (cx == p0 || cx == p1 || p0 == p1) return fail(LR_ERR_ARG, "bfv switch keys: cx, p0 and p1 must be distinct polys");
-    LR_TRY(check_ct(pl, level, cx, cx->batch));
-    LR_TRY(check_ct(pl, level, p0, cx->batch));
-    LR_TRY(check_ct(pl, level, p1, cx->batch));
-    if (cx->batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    LR_TRY(same_stream(pl->cQ, pl->cP));
-    LR_HIP(hipSetDevice(pl->device));
-    return bfv_switch_keys_core(pl, cx->batch, cx->d, cx->stride(), evk, p0->d, p0->stride(), p1->d, p1->stride());
+    LR_TRY(check_cts(pl, level, cx->batch, {cx, p0, p1}));
+    LR_TRY(check_batch(pl, cx->batch));
+    LR_TRY(begin_pipeline(pl));
+    return bfv_switch_keys_core(pl, cx->batch, cx->d, cx->stride(), evk, {{p0->d, p1->d}, {p0->stride(), p1->stride()}});
     });
 }
 
@@ -557,19 +565,19 @@ extern "C" int lr_bfv_relinearize(lr_ckks_plan *pl, const lr_poly *c0, const lr_
     if (!pl || !c0 || !c1 || !c2 || !evk || !out0 || !out1) return fail(LR_ERR_ARG, "null argument");
     lr_context *cQ = pl->cQ;
     const int level = cQ->h.L() - 1, batch = c2->batch;
-    for (const lr_poly *p : {c0, c1, c2, (const lr_poly *)out0, (const lr_poly *)out1}) LR_TRY(check_ct(pl, level, p, batch));
+    LR_TRY(check_cts(pl, level, batch, {c0, c1, c2, out0, out1}));
     if (out0 == out1 || c2 == out0 || c2 == out1) return fail(LR_ERR_ARG, "bfv relinearize: out0, out1 and c2 must be distinct polys");
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    LR_TRY(same_stream(pl->cQ, pl->cP));
-    LR_HIP(hipSetDevice(pl->device));
+    LR_TRY(check_batch(pl, batch));
+    LR_TRY(begin_pipeline(pl));
     const long long sQ = (long long)cQ->h.L() * (long long)cQ->h.N;
     LR_TRY(pl->bfvP.ensure(cQ, (size_t)2 * batch * sQ));        // keyswitchpool[2], [3] (:489-490)
     u64 *p0 = pl->bfvP.d, *p1 = pl->bfvP.d + (long long)batch * sQ;
-    LR_TRY(bfv_switch_keys_core(pl, batch, c2->d, c2->stride(), evk, p0, sQ, p1, sQ));
-    if (batch == 1 && !pl->opt.no_pair && c0->d != c1->d && out0->d != out1->d && out0->d != c1->d && out1->d != c0->d) {
+    LR_TRY(bfv_switch_keys_core(pl, batch, c2->d, c2->stride(), evk, {{p0, p1}, {sQ, sQ}}));
+    const ComponentPair ins = component_pair(c0->d, c0->stride(), c1->d, c1->stride(), batch);
+    const ComponentPair outs = component_pair(out0->d, out0->stride(), out1->d, out1->stride(), batch);
+    if (batch == 1 && !pl->opt.no_pair && ins && outs && out0->d != c1->d && out1->d != c0->d) {
         // one ciphertext: the two additions as one launch over two "polys" at the distances between the components
-        auto words = [](const u64 *a, const u64 *b) { return (long long)(((intptr_t)b - (intptr_t)a) / (intptr_t)sizeof(u64)); };
-        return run_ewise(cQ, LR_ADD, level + 1, 2, c0->d, words(c0->d, c1->d), p0, sQ, out0->d, words(out0->d, out1->d), nullptr);   // :494-495
+        return run_ewise(cQ, LR_ADD, level + 1, 2, c0->d, ins.stride, p0, sQ, out0->d, outs.stride, nullptr);   // :494-495
     }
     LR_TRY(run_ewise(cQ, LR_ADD, level + 1, batch, c0->d, c0->stride(), p0, sQ, out0->d, out0->stride(), nullptr));   // :494
     return run_ewise(cQ, LR_ADD, level + 1, batch, c1->d, c1->stride(), p1, sQ, out1->d, out1->stride(), nullptr);    // :495
@@ -586,12 +594,10 @@ extern "C" int lr_bfv_rotate(lr_ckks_plan *pl, const lr_poly *c0, const lr_poly 
     if (!pl || !c0 || !c1 || !rotkey || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
     lr_context *cQ = pl->cQ;
     const int level = cQ->h.L() - 1, batch = c0->batch;
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    for (const lr_poly *p : {c0, c1, (const lr_poly *)o0, (const lr_poly *)o1}) LR_TRY(check_ct(pl, level, p, batch));
+    LR_TRY(check_call(pl, level, batch, {c0, c1, o0, o1}));
     if (o0->d == o1->d) return fail(LR_ERR_ARG, "bfv rotate: the two output polys must be distinct");
     if (cQ->h.N < 2 || cQ->h.logN > 31) return fail(LR_ERR_UNSUPPORTED, "ring degree");
-    LR_TRY(same_stream(pl->cQ, pl->cP));
-    LR_HIP(hipSetDevice(pl->device));
+    LR_TRY(begin_pipeline(pl));
     const int n = (int)cQ->h.N, L1 = level + 1;
     const long long s = (long long)L1 * n;
     for (Pool *p : {&pl->c0, &pl->c2x}) LR_TRY(p->ensure(cQ, (size_t)batch * s));
@@ -601,10 +607,10 @@ extern "C" int lr_bfv_rotate(lr_ckks_plan *pl, const lr_poly *c0, const lr_poly 
     G.ntt_domain = 0;
     G.gen = gen & ((cQ->h.N << 1) - 1);
     G.lp = cQ->d_lp;
-    if (batch == 1 && !pl->opt.no_pair && c0->d != c1->d) {
+    const ComponentPair ins = component_pair(c0->d, c0->stride(), c1->d, c1->stride(), batch);
+    if (batch == 1 && !pl->opt.no_pair && ins) {
         // one ciphertext: both components in one launch, the strides are the distances between them (see lr_ckks_rotate)
-        auto words = [](const u64 *a, const u64 *b) { return (long long)(((intptr_t)b - (intptr_t)a) / (intptr_t)sizeof(u64)); };
-        G.in = c0->d; G.in_stride = words(c0->d, c1->d); G.out = pl->c0.d; G.out_stride = words(pl->c0.d, pl->c2x.d);
+        G.in = c0->d; G.in_stride = ins.stride; G.out = pl->c0.d; G.out_stride = component_distance(pl->c0.d, pl->c2x.d);
         LR_HIP(launch_permute(G, L1, 2, cQ->stream));                                          // :723-724
     } else {
         G.in = c0->d; G.in_stride = c0->stride(); G.out = pl->c0.d; G.out_stride = s;
@@ -612,36 +618,36 @@ extern "C" int lr_bfv_rotate(lr_ckks_plan *pl, const lr_poly *c0, const lr_poly 
         G.in = c1->d; G.in_stride = c1->stride(); G.out = pl->c2x.d;
         LR_HIP(launch_permute(G, L1, batch, cQ->stream));                                      // :724
     }
-    LR_TRY(bfv_switch_keys_core(pl, batch, pl->c2x.d, s, rotkey, o0->d, o0->stride(), o1->d, o1->stride()));   // :729 (p1 lands in out1: :732)
+    LR_TRY(bfv_switch_keys_core(pl, batch, pl->c2x.d, s, rotkey, {{o0->d, o1->d}, {o0->stride(), o1->stride()}}));   // :729 (p1 lands in out1: :732)
     return run_ewise(cQ, LR_ADD, L1, batch, pl->c0.d, s, o0->d, o0->stride(), o0->d, o0->stride(), nullptr);   // :731
     });
 }
 
+// permuteNTT (ckks/evaluator.go:1448-1468): RotateColumns with a specific rotation key / Conjugate.
+// gen = the Galois element (ring.PermuteNTTIndex's `gen^power`); the two trailing Context calls (:1466-1467)
+// ride on the last ModDown pass.
 extern "C" int lr_ckks_rotate(lr_ckks_plan *pl, int level, const lr_poly *c0, const lr_poly *c1, uint64_t gen, const lr_poly *rotkey,
                               lr_poly *o0, lr_poly *o1) {
     return guarded([&]() -> int {
     if (!pl || !c0 || !c1 || !rotkey || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
-    if (level < 0 || level + 1 > pl->cQ->h.L()) return fail(LR_ERR_SHAPE, "level out of range");
     const int batch = c0->batch;
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    for (const lr_poly *p : {c0, c1, (const lr_poly *)o0, (const lr_poly *)o1}) LR_TRY(check_ct(pl, level, p, batch));
+    LR_TRY(check_call(pl, level, batch, {c0, c1, o0, o1}));
     if (o0->stride() != o1->stride()) return fail(LR_ERR_SHAPE, "output polys must share their stride");
     lr_context *cQ = pl->cQ;
-    LR_TRY(same_stream(pl->cQ, pl->cP));
-    LR_HIP(hipSetDevice(cQ->device));
+    LR_TRY(begin_pipeline(pl));
     const int n = (int)cQ->h.N, L1 = level + 1;
     const long long s = (long long)L1 * n;
     for (Pool *p : {&pl->c0, &pl->c2x, &pl->q1, &pl->q2}) LR_TRY(p->ensure(cQ, (size_t)batch * s));
-    if (batch == 1 && !pl->opt.no_pair && c0->d != c1->d) {
-        // one ciphertext: both components in one launch, the strides are the distances between them (see ks_accumulate)
-        auto words = [](const u64 *a, const u64 *b) { return (long long)(((intptr_t)b - (intptr_t)a) / (intptr_t)sizeof(u64)); };
-        LR_TRY(run_permute_ntt(cQ, L1, 2, c0->d, words(c0->d, c1->d), pl->c0.d, words(pl->c0.d, pl->c2x.d), gen));    // :1458-1459
+    const ComponentPair ins = component_pair(c0->d, c0->stride(), c1->d, c1->stride(), batch);
+    if (batch == 1 && !pl->opt.no_pair && ins) {
+        // one ciphertext: both components in one launch, the strides are the distances between them (see ks_ntt_tail)
+        LR_TRY(run_permute_ntt(cQ, L1, 2, c0->d, ins.stride, pl->c0.d, component_distance(pl->c0.d, pl->c2x.d), gen));    // :1458-1459
     } else {
         LR_TRY(run_permute_ntt(cQ, L1, batch, c0->d, c0->stride(), pl->c0.d, s, gen));    // :1458
         LR_TRY(run_permute_ntt(cQ, L1, batch, c1->d, c1->stride(), pl->c2x.d, s, gen));   // :1459
     }
     KeySwitchEpilogue fin{o0->d, o1->d, o0->stride(), pl->c0.d, nullptr, s};
-    return switch_keys_core(pl, level, batch, pl->c2x.d, s, rotkey, pl->q1.d, s, pl->q2.d, s, &fin);   // :1464-1467
+    return switch_keys_core(pl, level, batch, pl->c2x.d, s, rotkey, {{pl->q1.d, pl->q2.d}, {s, s}}, &fin);   // :1464-1467
     });
 }
 
@@ -653,28 +659,24 @@ extern "C" int lr_ckks_rotate_hoisted(lr_ckks_plan *pl, int level, const lr_poly
     return guarded([&]() -> int {
     if (!pl || !c0 || !c1 || !gens || !rotkeys || !outs0 || !outs1) return fail(LR_ERR_ARG, "null argument");
     if (n_rot < 0) return fail(LR_ERR_ARG, "negative rotation count");
-    if (level < 0 || level + 1 > pl->cQ->h.L()) return fail(LR_ERR_SHAPE, "level out of range");
     const int batch = c0->batch;
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    LR_TRY(check_ct(pl, level, c0, batch));
-    LR_TRY(check_ct(pl, level, c1, batch));
+    LR_TRY(check_call(pl, level, batch, {c0, c1}));
     lr_context *cQ = pl->cQ, *cP = pl->cP;
-    LR_TRY(same_stream(pl->cQ, pl->cP));
-    LR_HIP(hipSetDevice(cQ->device));
-    const int nQ = cQ->h.L(), nP = cP->h.L(), n = (int)cQ->h.N, L1 = level + 1;
-    const int alpha = pl->dec->alpha;
-    const int beta = (L1 + alpha - 1) / alpha;
-    const long long s = (long long)L1 * n, sQ = (long long)nQ * n, sP = (long long)nP * n;
+    LR_TRY(begin_pipeline(pl));
+    const int nP = cP->h.L(), n = (int)cQ->h.N, L1 = level + 1;
+    const KsSizes z = ks_sizes(pl, level, batch);
+    const int beta = z.beta;
+    const long long s = (long long)L1 * n, sQ = z.sQ, sP = z.sP;
     for (int r = 0; r < n_rot; ++r) {
         if (!rotkeys[r] || !outs0[r] || !outs1[r]) return fail(LR_ERR_ARG, "null argument");
-        LR_TRY(check_ct(pl, level, outs0[r], batch));
-        LR_TRY(check_ct(pl, level, outs1[r], batch));
+        LR_TRY(check_cts(pl, level, batch, {outs0[r], outs1[r]}));
         if (outs0[r]->stride() != outs1[r]->stride()) return fail(LR_ERR_SHAPE, "output polys must share their stride");
         if (outs0[r]->d == c0->d || outs1[r]->d == c0->d || outs0[r]->d == c1->d || outs1[r]->d == c1->d)
             return fail(LR_ERR_ARG, "hoisted rotations are not in place");
     }
-    LR_TRY(ks_decompose(pl, level, batch, c1->d, c1->stride(), true));                         // :1258-1272
+    LR_TRY(ks_decompose(pl, level, batch, c1->d, c1->stride(), KsInput::NttCopyOwn));          // :1258-1272
     for (Pool *p : {&pl->c0, &pl->q1, &pl->q2}) LR_TRY(p->ensure(cQ, (size_t)batch * s));
+    const KeySwitchAcc acc{{pl->q1.d, pl->q2.d}, {s, s}};
     if (pl->opt.no_epilogue) {
         LR_TRY(pl->permQ.ensure(cQ, (size_t)beta * batch * sQ));
         LR_TRY(pl->permP.ensure(cQ, (size_t)beta * batch * sP));
@@ -686,11 +688,11 @@ extern "C" int lr_ckks_rotate_hoisted(lr_ckks_plan *pl, int level, const lr_poly
             // the reference's shape: permuted copies of every digit (:1346-1347), then the inner product over them
             LR_TRY(run_permute_ntt(cQ, L1, beta * batch, pl->c2QiQ.d, sQ, pl->permQ.d, sQ, gens[r]));
             LR_TRY(run_permute_ntt(cP, nP, beta * batch, pl->c2QiP.d, sP, pl->permP.d, sP, gens[r]));
-            LR_TRY(ks_accumulate(pl, level, batch, pl->permQ.d, pl->permP.d, nullptr, 0, rotkeys[r], pl->q1.d, s, pl->q2.d, s, &fin));
+            LR_TRY(ks_product_and_ntt_tail(pl, level, batch, KsDigits::whole(pl->permQ.d, pl->permP.d), rotkeys[r], acc, &fin));
         } else {
             // the permutation of the digits rides on the inner product's loads (KeyMacLaunch::perm_gen): same values, 2 x beta x (|Q| + |P|)
             // rows per rotation less to write and read back
-            LR_TRY(ks_accumulate(pl, level, batch, pl->c2QiQ.d, pl->c2QiP.d, nullptr, 0, rotkeys[r], pl->q1.d, s, pl->q2.d, s, &fin, false, gens[r]));
+            LR_TRY(ks_product_and_ntt_tail(pl, level, batch, KsDigits::whole(pl->c2QiQ.d, pl->c2QiP.d, gens[r]), rotkeys[r], acc, &fin));
         }
     }
     return LR_OK;
@@ -702,8 +704,7 @@ namespace lr_host {
 // ckks/evaluator.go:1080-1104 after the argument checks: T holds the four operands (strided or through a pointer table)
 int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride) {
     lr_context *cQ = pl->cQ;
-    LR_TRY(same_stream(pl->cQ, pl->cP));
-    LR_HIP(hipSetDevice(cQ->device));
+    LR_TRY(begin_pipeline(pl));
     const int n = (int)cQ->h.N, L1 = level + 1;
     const long long s = (long long)L1 * n;
     for (Pool *p : {&pl->c0, &pl->c1, &pl->c2x, &pl->q1, &pl->q2}) LR_TRY(p->ensure(cQ, (size_t)batch * s));
@@ -715,8 +716,7 @@ int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const 
     LR_HIP(launch_tensor(T, L1, batch, cQ->stream));
     // :1101 key switch of the degree-2 part, :1103-1104 the two additions fused into its last pass
     KeySwitchEpilogue fin{o0, o1, o_stride, pl->c0.d, pl->c1.d, s};
-    LR_TRY(switch_keys_core(pl, level, batch, pl->c2x.d, s, evk, pl->q1.d, s, pl->q2.d, s, &fin));
-    return LR_OK;
+    return switch_keys_core(pl, level, batch, pl->c2x.d, s, evk, {{pl->q1.d, pl->q2.d}, {s, s}}, &fin);
 }
 
 }  // namespace lr_host
@@ -725,10 +725,8 @@ extern "C" int lr_ckks_mulrelin(lr_ckks_plan *pl, int level, const lr_poly *a0, 
                                 const lr_poly *b1, const lr_poly *evk, lr_poly *o0, lr_poly *o1) {
     return guarded([&]() -> int {
     if (!pl || !a0 || !a1 || !b0 || !b1 || !evk || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
-    if (level < 0 || level + 1 > pl->cQ->h.L()) return fail(LR_ERR_SHAPE, "level out of range");
     const int batch = a0->batch;
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    for (const lr_poly *p : {a0, a1, b0, b1, (const lr_poly *)o0, (const lr_poly *)o1}) LR_TRY(check_ct(pl, level, p, batch));
+    LR_TRY(check_call(pl, level, batch, {a0, a1, b0, b1, o0, o1}));
     if (o0->stride() != o1->stride()) return fail(LR_ERR_SHAPE, "output polys must share their stride");
     TensorLaunch T;
     T.a0 = a0->d; T.a1 = a1->d; T.b0 = b0->d; T.b1 = b1->d;
@@ -745,10 +743,8 @@ extern "C" int lr_ckks_mul_norelin(lr_ckks_plan *pl, int level, const lr_poly *a
                                    const lr_poly *b1, lr_poly *o0, lr_poly *o1, lr_poly *o2) {
     return guarded([&]() -> int {
     if (!pl || !a0 || !a1 || !b0 || !b1 || !o0 || !o1 || !o2) return fail(LR_ERR_ARG, "null argument");
-    if (level < 0 || level + 1 > pl->cQ->h.L()) return fail(LR_ERR_SHAPE, "level out of range");
     const int batch = a0->batch;
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    for (const lr_poly *p : {a0, a1, b0, b1, (const lr_poly *)o0, (const lr_poly *)o1, (const lr_poly *)o2}) LR_TRY(check_ct(pl, level, p, batch));
+    LR_TRY(check_call(pl, level, batch, {a0, a1, b0, b1, o0, o1, o2}));
     lr_context *cQ = pl->cQ;
     LR_HIP(hipSetDevice(cQ->device));
     TensorLaunch T;
@@ -768,10 +764,8 @@ extern "C" int lr_ckks_mul_plain(lr_ckks_plan *pl, int level, const lr_poly *pt,
                                  lr_poly *o0, lr_poly *o1) {
     return guarded([&]() -> int {
     if (!pl || !pt || !c0 || !c1 || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
-    if (level < 0 || level + 1 > pl->cQ->h.L()) return fail(LR_ERR_SHAPE, "level out of range");
     const int batch = c0->batch;
-    if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
-    for (const lr_poly *p : {c0, c1, (const lr_poly *)o0, (const lr_poly *)o1}) LR_TRY(check_ct(pl, level, p, batch));
+    LR_TRY(check_call(pl, level, batch, {c0, c1, o0, o1}));
     if (pt->N != pl->cQ->h.N || pt->limbs < level + 1 || (pt->batch != batch && pt->batch != 1)) return fail(LR_ERR_SHAPE, "plaintext: limbs or batch");
     lr_context *cQ = pl->cQ;
     LR_HIP(hipSetDevice(cQ->device));
@@ -916,15 +910,15 @@ extern "C" int lr_ckks_rescale(lr_ckks_plan *pl, lr_poly *c0, lr_poly *c1) {
     // reaches both, i.e. always for one poly each (stride = the distance between them) and for batches laid out back to back --
     // every launch carries both (PN15QP880, one ciphertext: 121 -> 66 us).
     lr_poly *lo = c0->d <= c1->d ? c0 : c1, *hi = lo == c0 ? c1 : c0;
-    const long long gap = hi->d - lo->d;
     const bool same_shape = c0->limbs == c1->limbs && c0->batch == c1->batch && c0->N == c1->N && c0->d != c1->d;
-    const bool one_each = same_shape && c0->batch == 1 && gap >= (long long)lo->limbs * (long long)lo->N;
-    const bool back_to_back = same_shape && c0->stride() == c1->stride() && gap == (long long)lo->batch * lo->stride();
-    if (!c->opt.rescale_unpaired && (one_each || back_to_back) && (long long)c0->batch * 2 * c0->limbs <= c->opt.pair_max_workgroups) {
+    const ComponentPair pair = component_pair(lo->d, lo->stride(), hi->d, hi->stride(), lo->batch);
+    const bool one_each = pair.kind == ComponentPair::OneEach && pair.stride >= (long long)lo->limbs * (long long)lo->N;
+    if (!c->opt.rescale_unpaired && same_shape && (one_each || pair.kind == ComponentPair::BackToBack) &&
+        (long long)c0->batch * 2 * c0->limbs <= c->opt.pair_max_workgroups) {
         lr_poly both = *lo;
         both.owned = false;
         both.batch = 2 * lo->batch;
-        if (one_each) both.stride_words = gap;
+        both.stride_words = pair.stride;
         LR_TRY(rescale_ntt_domain(c, &both, true));
         c0->limbs = c1->limbs = both.limbs;
         return LR_OK;

@@ -379,7 +379,7 @@ struct lr_ckks_plan {
     Pool encQ, encP;       // pk-encryption temporaries over Q||P (lr_ckks_encrypt_pk)
     Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q)
     Pool zerosQ;           // one poly of zeros over Q: the `plus` operand of the NTT epilogue where a caller has none
-    Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_decompose)
+    Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_plan_decomposition)
     // small batches: independent launches of one pipeline side by side (PlanFork); stream and events are created at the first fork
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -517,7 +517,50 @@ struct ExtPending {
 };
 
 
-// switchKeysInPlace, ckks/evaluator.go:1475-1558, on raw buffers: cx/p0/p1 have `q_stride` between batch polys
+// what digit `crt` of the decomposition is at a level (digit_shape, lr_abi_bext.cpp)
+struct DigitShape {
+    int d0, d1;              // its own limbs [d0, d1): d0 = crt * alpha, d1 clipped to level + 1
+    bool full;               // it owns exactly alpha limbs
+    bool extended;           // it goes through the extension kernel (false: the trivial-copy branch)
+    int index;               // of its table; the extension reads index + 2 limbs (extended digits only)
+    const DevModup *modup;   // that table, nullptr for a copied digit
+    int n_in() const { return index + 2; }
+};
+
+// how decompose_core extends a digit (all off: the plain Decompose / DecomposeAndSplit)
+struct DigitExtension {
+    bool top = false, skip_own = false, inv_top = false;
+    std::vector<ExtPending> *collect = nullptr;     // record the extension instead of launching it (flush_ext)
+};
+
+// Two components of `batch` polys each as ONE batch of 2 * batch: base + p * stride reaches both when they lie back to back with one stride
+// (a pool that holds both), or when each is one poly -- the stride is then the distance between them, of either sign.  Every launch that
+// carries both components of a small batch asks here, and adds (all but the rescale: !no_pair):
+//   ks_coeff_tail                   nothing
+//   ks_ntt_tail                     batch == 1; asked about the OUTPUTS (the addends may coincide: both the row of zeros, distance 0)
+//   lr_bfv_relinearize              batch == 1; inputs and outputs both; no output over the other component's operand
+//   lr_bfv_rotate, lr_ckks_rotate   batch == 1; (the outputs are two pools)
+//   lr_ckks_rescale                 !rescale_unpaired; the lower address first; one poly each only at a distance >= limbs * N (no overlap);
+//                                   same shapes; 2 * batch * limbs <= pair_max_workgroups
+// Only the rescale asks for a positive distance.  With the outputs of ks_ntt_tail at a negative one, N = 2^16 and Options::no_exttop, the
+// transform that carries the epilogue refuses (ntt_rows_disjoint reads a negative stride as an overlap): LR_ERR_ARG, left as it is.
+inline long long component_distance(const u64 *a, const u64 *b) { return (long long)(((intptr_t)b - (intptr_t)a) / (intptr_t)sizeof(u64)); }
+struct ComponentPair {
+    enum Kind { None, BackToBack, OneEach } kind;
+    long long stride;
+    explicit operator bool() const { return kind != None; }
+};
+inline ComponentPair component_pair(const u64 *a, long long a_stride, const u64 *b, long long b_stride, int batch) {
+    if (a_stride == b_stride && b == a + (long long)batch * a_stride) return {ComponentPair::BackToBack, a_stride};
+    if (batch == 1 && a != b) return {ComponentPair::OneEach, component_distance(a, b)};
+    return {ComponentPair::None, 0};
+}
+
+// switchKeysInPlace, ckks/evaluator.go:1475-1558, on raw buffers: the two accumulators p0 / p1, each with its stride between batch polys
+struct KeySwitchAcc {
+    u64 *p[2];
+    long long stride[2];
+};
 // `fin` (optional): the ModDown results go to fin->out0/out1 with fin->plus0/plus1 added (CRed), i.e. the two
 // Context.Add calls that follow the key switch in MulRelin (:1103-1104) ride on the last ModDown pass
 struct KeySwitchEpilogue {
@@ -554,17 +597,15 @@ int run_ext(lr_context *c, const DevModup &m, int n_in, Rows in, int batch, ExtS
 int run_submul(lr_context *c, int limbs, int batch, const u64 *a, long long a_stride, const u64 *b, long long b_stride, long long b_row_stride, u64 *out, long long out_stride, const u64 *d_consts, bool reduce_b, const LimbScalars *addend, const u64 *plus = nullptr, long long plus_stride = 0, const LimbScalars *post = nullptr, int limb0 = 0);
 int same_degree(const lr_context *a, const lr_context *b);
 int same_stream(const lr_context *a, const lr_context *b);
-bool digit_is_extended(const lr_decomposer *d, int level, int crt);
 int moddown_pq_core(lr_bext *b, int level, const u64 *p1Q, long long p1Q_stride, Rows pP, int batch, lr_poly *p2, bool ntt, const u64 *x2 = nullptr,
                     long long x2_stride = 0);
 bool moddown_epilogue_available(const lr_bext *b);
-int decompose_core(lr_decomposer *d, int level, int crt, Rows in, int batch, u64 *outQ, long long outQ_stride, u64 *outP, long long outP_stride, bool split, bool top = false, bool skip_own = false, std::vector<ExtPending> *collect = nullptr, bool inv_top = false);
+DigitShape digit_shape(const lr_decomposer *d, int level, int crt);
+int decompose_core(lr_decomposer *d, int level, int crt, Rows in, int batch, Rows outQ, const Rows *outP, DigitExtension how = DigitExtension());
 // lr_abi_ckks.cpp: the key switch and the pipelines over it
 std::atomic<int> &standalone_plans(int device);
 int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride, u64 gen, const u64 *const *in_table = nullptr);
-int ks_decompose(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, bool copy_own, bool coeff_input = false);
-int ks_accumulate(lr_ckks_plan *pl, int level, int batch, const u64 *digQ, const u64 *digP, const u64 *own, long long own_stride, const lr_poly *evk, u64 *p0, long long p0_stride, u64 *p1, long long p1_stride, const KeySwitchEpilogue *fin, bool coeff_out = false, u64 perm_gen = 0);
-int switch_keys_core(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, u64 *p0, long long p0_stride, u64 *p1, long long p1_stride, const KeySwitchEpilogue *fin = nullptr);
+int switch_keys_core(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc, const KeySwitchEpilogue *fin = nullptr);
 int check_ct(const lr_ckks_plan *pl, int level, const lr_poly *p, int batch);
 int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride);
 
