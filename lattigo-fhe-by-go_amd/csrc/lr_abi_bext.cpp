@@ -279,11 +279,9 @@ int moddown_pq_core(lr_bext *b, int level, const u64 *p1Q, long long p1Q_stride,
             LR_HIP(hipMemsetAsync(b->zerosQ.d, 0, (size_t)pool_stride * sizeof(u64), cQ->stream));
         }
         const long long n64 = (long long)cQ->h.N;
-        int l0 = 0;
-        while (l0 <= level) {
-            const bool fpc = ntt_epilogue_limb(cQ, l0);
-            int l1 = l0 + 1;
-            while (l1 <= level && ntt_epilogue_limb(cQ, l1) == fpc) ++l1;
+        for (int l0 = 0, l1; l0 <= level; l0 = l1) {
+            bool fpc;
+            l1 = epilogue_run_end(cQ, l0, level + 1, &fpc);
             Rows src{b->poolQ.d, pool_stride, l0, 1};
             if (fpc) {
                 const NttEpilogue ep{p1Q, p1Q_stride, b->zerosQ.d, 0, b->d_moddown_pq_epi};
@@ -294,7 +292,6 @@ int moddown_pq_core(lr_bext *b, int level, const u64 *p1Q, long long p1Q_stride,
                 LR_TRY(run_submul(cQ, l1 - l0, batch, p1Q + l0 * n64, p1Q_stride, b->poolQ.d + l0 * n64, pool_stride, n64, p2->d + l0 * n64,
                                   p2->stride(), b->d_moddown_pq + l0, false, nullptr, nullptr, 0, nullptr, l0));
             }
-            l0 = l1;
         }
         return LR_OK;
     }

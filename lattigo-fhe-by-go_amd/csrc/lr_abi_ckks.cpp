@@ -453,8 +453,8 @@ int ks_ntt_tail(lr_ckks_plan *pl, int level, int batch, const KeySwitchAcc &acc,
     const ComponentPair outs = component_pair(comp[0].out, comp[0].out_stride, comp[1].out, comp[1].out_stride, batch);
     const bool pair = batch == 1 && !pl->opt.no_pair && outs;
     for (int l0 = 0, l1; l0 <= level; l0 = l1) {
-        const bool fpc = ntt_epilogue_limb(cQ, l0);
-        for (l1 = l0 + 1; l1 <= level && ntt_epilogue_limb(cQ, l1) == fpc; ++l1) {}
+        bool fpc;
+        l1 = epilogue_run_end(cQ, l0, level + 1, &fpc);
         if (!fpc) {
             LR_TRY(transform_then_submul(l0, l1));
         } else if (pair) {

@@ -7,9 +7,6 @@
 // ------------------------------------------------------------------------------------------
 namespace lr_host {
 
-
-
-// N = 2^16: the input rows either carry the top stage already (`pretop`) or are disjoint from the output rows
 // The forward kernels with the subtract-multiply-add epilogue: the dual kernels "m4" (FP64 body below 2^46, integer body -- mode 2 -- for
 // the other limbs) where the context runs the dual kernels, the integer kernels "m5" where it runs mode 1 (q <= 2^60: the reference's
 // 60-bit rings).  Contexts on the other integer variants (q up to 2^61, or every modulus in [2^46, 2^57)) keep the separate pass.
@@ -34,107 +31,175 @@ EpiLimb make_epi_limb(const lr_context *c, int l, u64 cc) {
     return e;
 }
 
-// N = 2^15 transforms as two 2^14 sub-blocks (run_ntt_launch): for launches of at most Options::split15_max_workgroups (128) workgroups -- split, they still fit
-// one round on the 256 CUs.
+// Fork: launches of the calling thread that go to a plan's auxiliary stream instead of the context's (PlanFork, lr_abi_ckks.cpp): two independent
+// transforms of a small batch run side by side instead of one after the other.  Only forward transforms are forked (they lease no scratch).
+thread_local hipStream_t g_fork_stream = nullptr;
+
+// ---- launch-size policies: each is asked by the route decision (ntt_route) and nowhere else on the transform path
+// N = 2^15 transforms as two 2^14 sub-blocks: for launches of at most Options::split15_max_workgroups (128) workgroups -- split, they still fit
+// one round on the 256 CUs.  A launch too small to fill the chip with one workgroup per transform (a one-workgroup 2^15 transform takes ~42 us
+// whatever surrounds it) gets twice the workgroups at about half the latency on the "h" kernels; the stage over index bit 14 is the streaming
+// ntt_top_kernel's (forward: before; inverse: after, with the scaling).
 bool ntt_split15(const lr_context *c, long long workgroups) {
     if (c->h.logN != 15 || !c->use_asm || c->opt.timeline || !ntt_asm_available(15)) return false;
-    const int variant_f = c->asm_fwd, variant_i = c->asm_inv;
-    if (variant_f < 0 || variant_i < 0) return false;
+    if (c->asm_fwd < 0 || c->asm_inv < 0) return false;
     if (c->opt.split15 >= 0) return c->opt.split15 == 1;
     if (c->opt.persist > 0) return false;          // (LR_NTT_PERSIST asks for the persistent one-workgroup kernels: diagnostics)
     return workgroups <= c->opt.split15_max_workgroups;
 }
-
-// Fork: launches of the calling thread that go to a plan's auxiliary stream instead of the context's (PlanFork, below): two independent
-// transforms of a small batch run side by side instead of one after the other.  Only forward transforms are forked (they lease no scratch).
-thread_local hipStream_t g_fork_stream = nullptr;
-
-
-int run_ntt_launch(lr_context *c, bool inverse, Rows in, Rows out, int mod0, int mod_step, int count, int batch, int hole,
-                   int group, const NttEpilogue *epi, bool pretop, bool lazy);
-
-// Polys per workgroup of the persistent forward 2^15 kernels (0 = the one-poly kernels).  LR_NTT_PERSIST overrides; the default keeps
-// at least four rounds of workgroups on the 256 CUs (the dispatcher balances limbs of different cost -- FP64 and integer bodies in one
-// dual launch -- by rounds) and at most kPersistMax polys per workgroup.
-constexpr int kPersistDefault = 0;
-int ntt_persist(const lr_context *c, const NttLaunch &a, unsigned logn, bool inverse) {
-    if (logn != 15 || inverse) return 0;
-    const int polys = a.hole > 0 ? a.group : a.batch;
-    int p = c->opt.persist >= 0 ? c->opt.persist : kPersistDefault;
-    if (p > polys) p = polys;
+// N = 2^14: 512 threads per transform put two workgroups on a CU (best throughput); a launch that does not fill the chip anyway takes
+// the 1024-thread plan, whose one workgroup is done sooner (PN14QP438, one ciphertext: MulRelin 115 -> 102 us, BFV Mul 136 -> 125 us)
+static bool ntt_wide14(const lr_context *c, long long transforms) {
+    return c->opt.asm14_1024 || (c->h.logN == 14 && !c->opt.no_wide14_small && transforms <= c->opt.wide14_max_items);
+}
+// Polys per workgroup of the persistent forward 2^15 kernels (0 = the one-poly kernels, the default): Options::persist, at most the polys of
+// a digit group (diagnostics builds)
+static int ntt_persist(const lr_context *c, bool inverse, int polys) {
+    if (c->h.logN != 15 || inverse) return 0;
+    const int p = std::min(c->opt.persist, polys);
     return p >= 2 ? p : 0;
 }
 
-// The assembly kernels of the integer variants put the polynomial on grid.y (limit 65535): longer plain launches are cut into
-// chunks along the batch on the same kernel (no silent change of code path).  Grouped launches (key-switch digits) beyond
-// the limit are refused: 65536 ciphertexts in one key switch exceed the device memory by orders of magnitude.
-// pretop (N = 2^16, forward, assembly kernels): the producer of the input rows has already applied the stage over index bit 15
-// (ext_sum_kernel<.., true>); the launch goes straight to the plain sub-block kernels, which read their own half only.
+// One launch's worth of run_ntt's arguments (the batch is already cut into chunks).
+// pretop (forward, N = 2^15 / 2^16 on the assembly kernels): the producer of the input rows has already applied the stage over the top index
+// bit (ext_sum_kernel<.., true>, the rescale's streaming pass); the launch goes straight to the plain sub-block kernels, which read their own
+// half only.  At N = 2^15 the caller has thereby decided for the split itself.
 // lazy (inverse, N = 2^15 / 2^16 on the assembly sub-block kernels): the rows are left as the two halves of every limb before the last
 // Gentleman-Sande stage and the scaling -- for a consumer that applies them itself (the top-stage basis extension, ExtLaunch::inv_top)
-int run_ntt(lr_context *c, bool inverse, Rows in, Rows out, int mod0, int mod_step, int count, int batch, int hole,
-            int group, const NttEpilogue *epi, bool pretop, bool lazy) {
-    if (count <= 0 || batch <= 0) return LR_OK;
-    if (hole > 0 && (group <= 0 || batch % group != 0)) return fail(LR_ERR_ARG, "digit groups must divide the batch");
-    // N = 2^16: the streaming top-stage kernel carries poly * limbs on grid.y
-    const int kChunk = c->h.logN == 16 || (c->h.logN == 15 && c->opt.split15 == 1) ? std::max(1, 65535 / count) : 65535;
-    if (hole > 0) {
-        if (group > kChunk || batch / group > 65535) return fail(LR_ERR_UNSUPPORTED, "grouped NTT launch: more than 65535 polys per digit group");
-        return run_ntt_launch(c, inverse, in, out, mod0, mod_step, count, batch, hole, group, epi, pretop, lazy);
+struct NttRequest {
+    bool inverse;
+    Rows in, out;
+    int mod0, mod_step, count, batch, hole, group;
+    const NttEpilogue *epi;
+    bool pretop, lazy;
+};
+
+// the launch struct of a request: addressing, the direction's tables, and for the dual kernels ("m3" / "m4") the FP64 tables beside them
+static NttLaunch ntt_launch_args(const lr_context *c, const NttRequest &q) {
+    NttLaunch a{};
+    a.in = q.in.base;
+    a.out = q.out.base;
+    a.in_poly_stride = q.in.stride;
+    a.out_poly_stride = q.out.stride;
+    a.in_limb0 = q.in.limb0;
+    a.in_limb_step = q.in.step;
+    a.out_limb0 = q.out.limb0;
+    a.out_limb_step = q.out.step;
+    a.mod0 = q.mod0;
+    a.mod_step = q.mod_step;
+    a.n_items = q.count;
+    a.batch = q.batch;
+    a.hole = q.hole;
+    a.group = q.group;
+    a.lp = c->d_lp;
+    a.tw = q.inverse ? c->d_inv : c->d_fwd;
+    a.tw_fin = q.inverse ? c->d_inv_fin : c->d_fwd_fin;
+    if ((q.inverse ? c->asm_inv : c->asm_fwd) == 3) {
+        a.fp_tw_delta = (const char *)(q.inverse ? c->d_inv_fp : c->d_fwd_fp) - (const char *)a.tw;
+        a.fp_fin_delta = (const char *)(q.inverse ? c->d_inv_fin_fp : c->d_fwd_fin_fp) - (const char *)a.tw_fin;
+        a.fp_lp = c->d_fp_lp;
     }
-    for (int b0 = 0; b0 < batch; b0 += kChunk) {
-        const int nb = std::min(kChunk, batch - b0);
-        Rows ci = in, co = out;
-        ci.base = in.base + (long long)b0 * in.stride;
-        co.base = out.base + (long long)b0 * out.stride;
-        NttEpilogue e2;
-        if (epi) {
-            e2 = *epi;
-            e2.x = epi->x + (long long)b0 * epi->x_stride;
-            e2.plus = epi->plus + (long long)b0 * epi->plus_stride;
-        }
-        LR_TRY(run_ntt_launch(c, inverse, ci, co, mod0, mod_step, count, nb, 0, 0, epi ? &e2 : nullptr, pretop, lazy));
+    return a;
+}
+// the next kernel continues in place on the output rows
+static void continue_on_output(NttLaunch &a) {
+    a.in = a.out;
+    a.in_poly_stride = a.out_poly_stride;
+    a.in_limb0 = a.out_limb0;
+    a.in_limb_step = a.out_limb_step;
+}
+static void with_epilogue(NttLaunch &a, const NttEpilogue &epi) {
+    a.epi_x = epi.x;
+    a.epi_x_stride = epi.x_stride;
+    a.epi_plus = epi.plus;
+    a.epi_plus_stride = epi.plus_stride;
+    a.epi_consts = epi.consts;
+}
+
+// Which kernels a request takes.  "asm": the context runs the assembly kernels of the request's direction at its degree (variant >= 0);
+// "disjoint": no input row is an output row (ntt_rows_disjoint).  An epilogue selects the variant (4 on the dual kernels, 5 on the integer
+// ones), never the route's shape; it comes with the forward routes marked (e).
+//   N            asm   direction   asked for / launch size                     route
+//   any          no    either      --                                          Cxx             the C++ kernels (2^16: their own two passes)
+//   <= 2^14      yes   either      --                                          Whole (e)       one kernel per transform (2^14: ntt_wide14 picks the plan)
+//   2^15         yes   either      no epilogue, ntt_split15 says no            Whole           (ntt_timeline: Stamped, plain launches of variant 1 / 3)
+//   2^15         yes   forward     epilogue without pretop                     Whole (e)       whatever the launch size
+//   2^15         yes   forward     pretop                                      Split15Pretop (e)   the 2^14 sub-blocks alone
+//   2^15         yes   forward     ntt_split15 says yes                        Split15Top      top pass, then the sub-blocks on the output rows
+//   2^15         yes   inverse     lazy                                        Split15InvLazy  the sub-blocks alone
+//   2^15         yes   inverse     ntt_split15 says yes (or pretop)            Split15InvTop   the sub-blocks, then the top pass with the scaling
+//   2^16         yes   forward     pretop                                      Fwd16Pretop (e) the 2^15 sub-blocks alone
+//   2^16         yes   forward     disjoint                                    Fwd16Fused (e)  the top stage inside the sub-blocks' loads
+//   2^16         yes   forward     otherwise (no epilogue)                     Fwd16Top        top pass, then the sub-blocks on the output rows
+//   2^16         yes   inverse     lazy                                        Inv16Lazy       the sub-blocks alone
+//   2^16         yes   inverse     plain launch, not no_invfuse                Inv16PairFlags  the second finisher of a limb's two sub-blocks does the last stage
+//   2^16         yes   inverse     otherwise                                   Inv16Top        the sub-blocks, then the top pass with the scaling
+// Refused (LR_ERR_ARG): lazy unless inverse, without epilogue, N = 2^15 / 2^16, asm; pretop without epilogue unless N = 2^15 / 2^16, asm (an
+// inverse launch ignores it); an epilogue unless forward, plain launch (no digit groups), ntt_epilogue_ok, and at N = 2^16 pretop or disjoint.
+struct NttRoute {
+    enum Kind { Refused, Cxx, Whole, Stamped, Split15Top, Split15Pretop, Split15InvTop, Split15InvLazy,
+                Fwd16Pretop, Fwd16Fused, Fwd16Top, Inv16Lazy, Inv16PairFlags, Inv16Top } kind;
+    int variant;             // of the assembly kernels
+    bool wide14;             // Whole
+    int persist;             // Whole, Stamped
+    int code;                // Refused
+    const char *why;
+};
+static NttRoute ntt_route(const lr_context *c, const NttRequest &q) {
+    const unsigned logn = c->h.logN;
+    const auto refuse = [](int code, const char *why) { return NttRoute{NttRoute::Refused, -1, false, 0, code, why}; };
+    if (logn < 1 || logn > 16) return refuse(LR_ERR_UNSUPPORTED, "NTT kernels cover 2 <= N <= 2^16");
+    const int own = q.inverse ? c->asm_inv : c->asm_fwd;
+    const bool assembly = own >= 0 && c->use_asm && ntt_asm_available((int)logn), sub_blocks = assembly && (logn == 15 || logn == 16);
+    const bool disjoint16 = logn == 16 && !q.inverse && !q.pretop && ntt_rows_disjoint(ntt_launch_args(c, q), 16);
+    if (q.lazy && !(q.inverse && !q.epi && sub_blocks))
+        return refuse(LR_ERR_ARG, "lazy inverse outputs: assembly sub-block kernels of N = 2^15 / 2^16 only");
+    if (q.pretop && !q.epi && !sub_blocks)       // (with an epilogue, the epilogue's own conditions decide: ntt_epilogue_ok asks for the assembly kernels)
+        return refuse(LR_ERR_ARG, "pre-applied top stage: assembly sub-block kernels of N = 2^15 / 2^16 only");
+    if (q.epi && (q.inverse || q.hole > 0 || !ntt_epilogue_ok(c) || (logn == 16 && !q.pretop && !disjoint16)))
+        return refuse(LR_ERR_ARG, "NTT epilogue: not available for this launch");
+    const auto route = [&](NttRoute::Kind kind) { return NttRoute{kind, q.epi ? (c->asm_fwd == 3 ? 4 : 5) : own, false, 0, LR_OK, nullptr}; };
+    const long long transforms = (long long)q.count * q.batch;
+    if (logn == 15 && (q.pretop || q.lazy || (!q.epi && ntt_split15(c, transforms)))) {
+        if (!q.inverse) return route(q.pretop ? NttRoute::Split15Pretop : NttRoute::Split15Top);
+        return route(q.lazy ? NttRoute::Split15InvLazy : NttRoute::Split15InvTop);
     }
+    if (logn == 16 && assembly) {
+        if (!q.inverse) return route(q.pretop ? NttRoute::Fwd16Pretop : disjoint16 ? NttRoute::Fwd16Fused : NttRoute::Fwd16Top);
+        return route(q.lazy ? NttRoute::Inv16Lazy : !c->opt.no_invfuse && q.hole == 0 ? NttRoute::Inv16PairFlags : NttRoute::Inv16Top);
+    }
+    if (!assembly) return route(NttRoute::Cxx);
+    NttRoute r = route(NttRoute::Whole);
+    if (q.epi) {
+        r.wide14 = ntt_wide14(c, transforms);
+        return r;
+    }
+    r.persist = ntt_persist(c, q.inverse, q.hole > 0 ? q.group : q.batch);
+    if (c->opt.timeline && logn == 15 && (own == 1 || own == 3) && q.hole == 0) r.kind = NttRoute::Stamped;   // (the stamped build of the same kernel)
+    else r.wide14 = ntt_wide14(c, transforms);
+    return r;
+}
+
+// diagnostics: the stamps of a Stamped launch land in the context's buffer (lr_context_timeline), which grows to the launch
+static int grow_stamps(lr_context *c, size_t words) {
+    if (words > c->stamp_words) {
+        LR_HIP(hipStreamSynchronize(stream_of(c)));
+        if (c->d_stamps) LR_HIP(hipFree(c->d_stamps));
+        c->d_stamps = nullptr;
+        c->stamp_words = 0;
+        LR_HIP(hipMalloc((void **)&c->d_stamps, words * sizeof(u32)));
+        c->stamp_words = words;
+    }
+    c->stamp_used = words;
     return LR_OK;
 }
 
-int run_ntt_launch(lr_context *c, bool inverse, Rows in, Rows out, int mod0, int mod_step, int count, int batch, int hole,
-                   int group, const NttEpilogue *epi, bool pretop, bool lazy) {
-    const unsigned logn = c->h.logN;
-    if (logn < 1 || logn > 16)
-        return fail(LR_ERR_UNSUPPORTED, "NTT kernels cover 2 <= N <= 2^16");
-    NttLaunch a;
-    a.in = in.base;
-    a.out = out.base;
-    a.in_poly_stride = in.stride;
-    a.out_poly_stride = out.stride;
-    a.in_limb0 = in.limb0;
-    a.in_limb_step = in.step;
-    a.out_limb0 = out.limb0;
-    a.out_limb_step = out.step;
-    a.mod0 = mod0;
-    a.mod_step = mod_step;
-    a.n_items = count;
-    a.sub_log = 0;
-    a.hole = hole;
-    a.group = group;
-    a.fuse_top = 0;
-    a.batch = batch;
-    a.lp = c->d_lp;
-    a.tw = inverse ? c->d_inv : c->d_fwd;
-    a.tw_fin = inverse ? c->d_inv_fin : c->d_fwd_fin;
-    const int variant = inverse ? c->asm_inv : c->asm_fwd;
-    a.fp_tw_delta = a.fp_fin_delta = 0;
-    a.fp_lp = nullptr;
-    a.epi_x = a.epi_plus = nullptr;
-    a.epi_x_stride = a.epi_plus_stride = 0;
-    a.epi_consts = nullptr;
-    a.stagger_gx = a.stagger_unit = 0;
-    if (variant == 3) {
-        a.fp_tw_delta = (const char *)(inverse ? c->d_inv_fp : c->d_fwd_fp) - (const char *)a.tw;
-        a.fp_fin_delta = (const char *)(inverse ? c->d_inv_fin_fp : c->d_fwd_fin_fp) - (const char *)a.tw_fin;
-        a.fp_lp = c->d_fp_lp;
-    }
+// one request: the route, then its one or two launches
+static int run_ntt_launch(lr_context *c, const NttRequest &q) {
+    const NttRoute r = ntt_route(c, q);
+    if (r.kind == NttRoute::Refused) return fail(r.code, r.why);
+    NttLaunch a = ntt_launch_args(c, q);
+    if (q.epi) with_epilogue(a, *q.epi);
     // the launcher writes the kernel's name into a local buffer; it reaches the context under its diagnostics mutex on every way out
     struct KernelNote {
         lr_context *c;
@@ -146,130 +211,97 @@ int run_ntt_launch(lr_context *c, bool inverse, Rows in, Rows out, int mod0, int
         }
     } note{c, ""};
     char *kn = note.buf;
-    // N = 2^14: 512 threads per transform put two workgroups on a CU (best throughput); a launch that does not fill the chip anyway takes
-    // the 1024-thread plan, whose one workgroup is done sooner (PN14QP438, one ciphertext: MulRelin 115 -> 102 us, BFV Mul 136 -> 125 us)
-    const bool wide14 = c->opt.asm14_1024 || (logn == 14 && !c->opt.no_wide14_small && (long long)count * batch <= c->opt.wide14_max_items);
-    // N = 2^15, a launch too small to fill the chip with one workgroup per transform (a one-workgroup 2^15 transform takes ~42 us whatever
-    // surrounds it): two 2^14 sub-blocks per limb on the "h" kernels, twice the workgroups at about half the latency.  The stage over
-    // index bit 14 is the streaming ntt_top_kernel's (forward: before, unless the caller's basis extension has applied it -- pretop;
-    // inverse: after, with the scaling).  A caller that passes pretop has decided for the split itself (ntt_split15).
-    if (lazy && !(inverse && !epi && (logn == 15 || logn == 16) && variant >= 0 && c->use_asm && ntt_asm_available((int)logn)))
-        return fail(LR_ERR_ARG, "lazy inverse outputs: assembly sub-block kernels of N = 2^15 / 2^16 only");
-    if (logn == 15 && (pretop || lazy || (ntt_split15(c, (long long)count * batch) && !(epi && !pretop)))) {
-        if (variant < 0 || !c->use_asm || !ntt_asm_available(15)) return fail(LR_ERR_ARG, "pre-applied top stage: assembly kernels only");
+    const hipStream_t s = stream_of(c);
+    const int logn = (int)c->h.logN, stagger = c->opt.stagger;
+    const bool pad = !c->opt.no_grid_padding;
+    switch (r.kind) {
+    case NttRoute::Cxx:
+        std::snprintf(note.buf, sizeof note.buf, "ntt_%s_kernel<%d>", q.inverse ? "inv" : "fwd", logn);
+        LR_HIP(launch_ntt(a, logn, q.inverse, c->ntt_mode, s));
+        break;
+    case NttRoute::Whole:
+        LR_HIP(launch_ntt_asm(a, logn, q.inverse, r.variant, s, r.wide14, kn, false, stagger, r.persist, pad));
+        break;
+    case NttRoute::Stamped: {
+        const size_t words = (size_t)q.batch * (size_t)q.count * 16 * 16;
+        LR_TRY(grow_stamps(c, words));
+        a.epi_x = reinterpret_cast<const u64 *>(c->d_stamps);
+        LR_HIP(launch_ntt_asm(a, logn, q.inverse, r.variant, s, false, kn, true, stagger, r.persist, pad));
+        break;
+    }
+    case NttRoute::Split15Top:
+        LR_HIP(launch_ntt_top(a, 0, s, 15));
+        continue_on_output(a);
+        LR_HIP(launch_ntt_asm16(a, 0, 'h', r.variant, s, kn, stagger, 15));
+        break;
+    case NttRoute::Split15Pretop:
+    case NttRoute::Split15InvLazy:
+        LR_HIP(launch_ntt_asm16(a, q.inverse, 'h', r.variant, s, kn, stagger, 15));
+        break;
+    case NttRoute::Split15InvTop:
+        LR_HIP(launch_ntt_asm16(a, 1, 'h', r.variant, s, kn, stagger, 15));
+        continue_on_output(a);
+        LR_HIP(launch_ntt_top(a, 1, s, 15));
+        break;
+    case NttRoute::Fwd16Pretop:
+        LR_HIP(launch_ntt_asm16(a, 0, 'p', r.variant, s, kn, stagger));
+        break;
+    case NttRoute::Fwd16Fused:
+    case NttRoute::Inv16Lazy:
+        LR_HIP(launch_ntt_asm16(a, q.inverse, 's', r.variant, s, kn, stagger));
+        break;
+    case NttRoute::Fwd16Top:
+        LR_HIP(launch_ntt_top(a, 0, s));
+        continue_on_output(a);
+        LR_HIP(launch_ntt_asm16(a, 0, 'p', r.variant, s, kn, stagger));
+        break;
+    case NttRoute::Inv16PairFlags: {
+        // the wave that finishes second of a limb's two sub-blocks combines both halves (gen_intt.py: fused_last); one u32 flag per wave
+        // pair, zeroed here, addressed through NttLaunch::epi_x
+        ScratchLease flags;
+        const size_t flag_bytes = (size_t)q.batch * (size_t)q.count * 16 * sizeof(u32);
+        LR_TRY(flags.take(&c->scratch, (flag_bytes + 7) / 8));
+        LR_HIP(hipMemsetAsync(flags.d(), 0, flag_bytes, s));
+        a.epi_x = flags.d();
+        LR_HIP(launch_ntt_asm16(a, 1, 'f', r.variant, s, kn, stagger));
+        break;
+    }
+    case NttRoute::Inv16Top:
+        LR_HIP(launch_ntt_asm16(a, 1, 's', r.variant, s, kn, stagger));
+        continue_on_output(a);
+        LR_HIP(launch_ntt_top(a, 1, s));
+        break;
+    case NttRoute::Refused: break;
+    }
+    return LR_OK;
+}
+
+// The assembly kernels of the integer variants put the polynomial on grid.y (limit 65535): longer plain launches are cut into
+// chunks along the batch on the same kernel (no silent change of code path).  Grouped launches (key-switch digits) beyond
+// the limit are refused: 65536 ciphertexts in one key switch exceed the device memory by orders of magnitude.
+int run_ntt(lr_context *c, bool inverse, Rows in, Rows out, int mod0, int mod_step, int count, int batch, int hole,
+            int group, const NttEpilogue *epi, bool pretop, bool lazy) {
+    if (count <= 0 || batch <= 0) return LR_OK;
+    if (hole > 0 && (group <= 0 || batch % group != 0)) return fail(LR_ERR_ARG, "digit groups must divide the batch");
+    // N = 2^16: the streaming top-stage kernel carries poly * limbs on grid.y
+    const int kChunk = c->h.logN == 16 || (c->h.logN == 15 && c->opt.split15 == 1) ? std::max(1, 65535 / count) : 65535;
+    if (hole > 0) {
+        if (group > kChunk || batch / group > 65535) return fail(LR_ERR_UNSUPPORTED, "grouped NTT launch: more than 65535 polys per digit group");
+        return run_ntt_launch(c, NttRequest{inverse, in, out, mod0, mod_step, count, batch, hole, group, epi, pretop, lazy});
+    }
+    for (int b0 = 0; b0 < batch; b0 += kChunk) {
+        NttRequest q{inverse, in, out, mod0, mod_step, count, std::min(kChunk, batch - b0), 0, 0, epi, pretop, lazy};
+        q.in.base = in.base + (long long)b0 * in.stride;
+        q.out.base = out.base + (long long)b0 * out.stride;
+        NttEpilogue e2;
         if (epi) {
-            if (inverse || hole > 0 || !ntt_epilogue_ok(c)) return fail(LR_ERR_ARG, "NTT epilogue: not available for this launch");
-            a.epi_x = epi->x;
-            a.epi_x_stride = epi->x_stride;
-            a.epi_plus = epi->plus;
-            a.epi_plus_stride = epi->plus_stride;
-            a.epi_consts = epi->consts;
-            LR_HIP(launch_ntt_asm16(a, 0, 'h', c->asm_fwd == 3 ? 4 : 5, stream_of(c), kn, c->opt.stagger, 15));
-            return LR_OK;
+            e2 = *epi;
+            e2.x = epi->x + (long long)b0 * epi->x_stride;
+            e2.plus = epi->plus + (long long)b0 * epi->plus_stride;
+            q.epi = &e2;
         }
-        if (!inverse) {
-            NttLaunch sub = a;
-            if (!pretop) {
-                LR_HIP(launch_ntt_top(a, 0, stream_of(c), 15));
-                sub.in = a.out;                  // continue in place on the output rows
-                sub.in_poly_stride = a.out_poly_stride;
-                sub.in_limb0 = a.out_limb0;
-                sub.in_limb_step = a.out_limb_step;
-            }
-            LR_HIP(launch_ntt_asm16(sub, 0, 'h', variant, stream_of(c), kn, c->opt.stagger, 15));
-            return LR_OK;
-        }
-        LR_HIP(launch_ntt_asm16(a, 1, 'h', variant, stream_of(c), kn, c->opt.stagger, 15));
-        if (lazy) return LR_OK;
-        NttLaunch top = a;
-        top.in = a.out;
-        top.in_poly_stride = a.out_poly_stride;
-        top.in_limb0 = a.out_limb0;
-        top.in_limb_step = a.out_limb_step;
-        LR_HIP(launch_ntt_top(top, 1, stream_of(c), 15));
-        return LR_OK;
+        LR_TRY(run_ntt_launch(c, q));
     }
-    if (epi) {
-        if (inverse || hole > 0 || !ntt_epilogue_ok(c) || (logn == 16 && !pretop && !ntt_rows_disjoint(a, 16)))
-            return fail(LR_ERR_ARG, "NTT epilogue: not available for this launch");
-        a.epi_x = epi->x;
-        a.epi_x_stride = epi->x_stride;
-        a.epi_plus = epi->plus;
-        a.epi_plus_stride = epi->plus_stride;
-        a.epi_consts = epi->consts;
-        if (logn == 16)
-            LR_HIP(launch_ntt_asm16(a, 0, pretop ? 'p' : 's', c->asm_fwd == 3 ? 4 : 5, stream_of(c), kn, c->opt.stagger));
-        else
-            LR_HIP(launch_ntt_asm(a, (int)logn, 0, c->asm_fwd == 3 ? 4 : 5, stream_of(c), wide14, kn, false, c->opt.stagger, 0, !c->opt.no_grid_padding));
-        return LR_OK;
-    }
-    if (logn == 16 && variant >= 0 && c->use_asm && ntt_asm_available(16)) {
-        // two 2^15 sub-blocks per limb on the assembly kernels + the streaming stage over bit 15
-        if (!inverse) {
-            if (pretop) {
-                LR_HIP(launch_ntt_asm16(a, 0, 'p', variant, stream_of(c), kn, c->opt.stagger));
-                return LR_OK;
-            }
-            if (ntt_rows_disjoint(a, 16)) {
-                LR_HIP(launch_ntt_asm16(a, 0, 's', variant, stream_of(c), kn, c->opt.stagger));     // top stage fused into the loads
-                return LR_OK;
-            }
-            LR_HIP(launch_ntt_top(a, 0, stream_of(c)));
-            NttLaunch sub = a;
-            sub.in = a.out;                      // continue in place on the output rows
-            sub.in_poly_stride = a.out_poly_stride;
-            sub.in_limb0 = a.out_limb0;
-            sub.in_limb_step = a.out_limb_step;
-            LR_HIP(launch_ntt_asm16(sub, 0, 'p', variant, stream_of(c), kn, c->opt.stagger));
-            return LR_OK;
-        }
-        if (lazy) {
-            LR_HIP(launch_ntt_asm16(a, 1, 's', variant, stream_of(c), kn, c->opt.stagger));
-            return LR_OK;
-        }
-        if (!c->opt.no_invfuse && hole == 0) {
-            // the last stage inside the sub-block kernels: the wave that finishes second of a limb's two sub-blocks combines both
-            // halves (gen_intt.py: fused_last); one u32 flag per wave pair, zeroed here, addressed through NttLaunch::epi_x
-            ScratchLease flags;
-            const size_t flag_bytes = (size_t)batch * (size_t)count * 16 * sizeof(u32);
-            LR_TRY(flags.take(&c->scratch, (flag_bytes + 7) / 8));
-            LR_HIP(hipMemsetAsync(flags.d(), 0, flag_bytes, stream_of(c)));
-            a.epi_x = flags.d();
-            LR_HIP(launch_ntt_asm16(a, 1, 'f', variant, stream_of(c), kn, c->opt.stagger));
-            return LR_OK;
-        }
-        LR_HIP(launch_ntt_asm16(a, 1, 's', variant, stream_of(c), kn, c->opt.stagger));
-        NttLaunch top = a;
-        top.in = a.out;
-        top.in_poly_stride = a.out_poly_stride;
-        top.in_limb0 = a.out_limb0;
-        top.in_limb_step = a.out_limb_step;
-        LR_HIP(launch_ntt_top(top, 1, stream_of(c)));
-        return LR_OK;
-    }
-    if (pretop) return fail(LR_ERR_ARG, "pre-applied top stage: only for forward N = 2^16 launches on the assembly kernels");
-    if (logn != 16 && variant >= 0 && c->use_asm && ntt_asm_available((int)logn)) {
-        if (c->opt.timeline && logn == 15 && (variant == 1 || variant == 3) && hole == 0) {
-            // diagnostics: the stamped build of the same kernel; stamps land in the context's buffer (lr_context_timeline)
-            const size_t words = (size_t)batch * (size_t)count * 16 * 16;
-            if (words > c->stamp_words) {
-                LR_HIP(hipStreamSynchronize(stream_of(c)));
-                if (c->d_stamps) LR_HIP(hipFree(c->d_stamps));
-                c->d_stamps = nullptr;
-                c->stamp_words = 0;
-                LR_HIP(hipMalloc((void **)&c->d_stamps, words * sizeof(u32)));
-                c->stamp_words = words;
-            }
-            c->stamp_used = words;
-            a.epi_x = reinterpret_cast<const u64 *>(c->d_stamps);
-            LR_HIP(launch_ntt_asm(a, (int)logn, inverse, variant, stream_of(c), false, kn, true, c->opt.stagger, ntt_persist(c, a, logn, inverse), !c->opt.no_grid_padding));
-            return LR_OK;
-        }
-        LR_HIP(launch_ntt_asm(a, (int)logn, inverse, variant, stream_of(c), wide14, kn, false, c->opt.stagger, ntt_persist(c, a, logn, inverse), !c->opt.no_grid_padding));
-        return LR_OK;
-    }
-    std::snprintf(note.buf, sizeof note.buf, "ntt_%s_kernel<%u>", inverse ? "inv" : "fwd", logn);
-    LR_HIP(launch_ntt(a, (int)logn, inverse, c->ntt_mode, stream_of(c)));
     return LR_OK;
 }
 
@@ -370,7 +402,6 @@ extern "C" int lr_intt_host(lr_context *c, int level, const uint64_t *const *in_
     return ntt_host(c, true, level, in_limbs, out_limbs);
     });
 }
-
 
 // ------------------------------------------------------------------------------------------
 // coefficient-wise
@@ -477,24 +508,42 @@ extern "C" int lr_half_scalar_op(lr_context *c, int op, int level, const lr_poly
 // ------------------------------------------------------------------------------------------
 // Galois automorphisms (ring/ring_galois.go)
 // ------------------------------------------------------------------------------------------
+// the launch of an automorphism or a monomial product: only gen mod 2N matters in either domain (indices are taken mod 2N resp. mod N
+// with the sign from bit logN; MultByMonomial reduces its degree the same way, ring/ring.go:667)
+static GaloisLaunch galois_launch(const lr_context *c, const u64 *in, long long in_stride, lr_poly *out, u64 gen, bool ntt_domain) {
+    GaloisLaunch L;
+    L.in = in;
+    L.out = out->d;
+    L.in_stride = in_stride;
+    L.out_stride = out->stride();
+    L.n = (int)c->h.N;
+    L.logn = (int)c->h.logN;
+    L.ntt_domain = ntt_domain ? 1 : 0;
+    L.gen = gen & ((c->h.N << 1) - 1);
+    L.lp = c->d_lp;
+    return L;
+}
+// an operation that may not read what it writes, called in place: the input goes through a temporary (as the reference's tmpx,
+// ring/ring.go:682-693); *src is the rows to read
+static int unaliased_input(lr_context *c, const lr_poly *in, const lr_poly *out, ScratchLease *tmp, const u64 **src) {
+    *src = in->d;
+    if (in->d != out->d) return LR_OK;
+    const size_t words = (size_t)out->batch * (size_t)in->stride();
+    LR_TRY(tmp->take(&c->scratch, words));
+    LR_HIP(hipMemcpyAsync(tmp->d(), in->d, words * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+    *src = tmp->d();
+    return LR_OK;
+}
+// Shift's and Rotate's n as Go evaluates n & ((1 << N) - 1): the mask is all ones for N >= 64 and 2^N - 1 below
+static u64 mask_shift_count(u64 n, u64 N) { return N >= 64 ? n : (n & (((u64)1 << N) - 1)); }
+
 static int permute_common(lr_context *c, int level, const lr_poly *in, u64 gen, lr_poly *out, bool ntt_domain) {
     LR_TRY(check_pair(c, level, in, out));
     if (in->batch != out->batch) return fail(LR_ERR_SHAPE, "batch mismatch");
     if (in->d == out->d) return fail(LR_ERR_ARG, "Permute is not in place (ring/ring_galois.go:54)");
     if (c->h.N < 2 || c->h.logN > 31) return fail(LR_ERR_UNSUPPORTED, "ring degree");
     LR_HIP(hipSetDevice(c->device));
-    GaloisLaunch L;
-    L.in = in->d;
-    L.out = out->d;
-    L.in_stride = in->stride();
-    L.out_stride = out->stride();
-    L.n = (int)c->h.N;
-    L.logn = (int)c->h.logN;
-    L.ntt_domain = ntt_domain ? 1 : 0;
-    // only gen mod 2N matters in either domain (indices are taken mod 2N resp. mod N with the sign from bit logN)
-    L.gen = gen & ((c->h.N << 1) - 1);
-    L.lp = c->d_lp;
-    LR_HIP(launch_permute(L, level + 1, out->batch, c->stream));
+    LR_HIP(launch_permute(galois_launch(c, in->d, in->stride(), out, gen, ntt_domain), level + 1, out->batch, c->stream));
     return LR_OK;
 }
 
@@ -519,25 +568,10 @@ extern "C" int lr_mult_by_monomial(lr_context *c, const lr_poly *in, uint64_t mo
     LR_TRY(check_pair(c, level, in, out));
     if (in->batch != out->batch) return fail(LR_ERR_SHAPE, "batch mismatch");
     LR_HIP(hipSetDevice(c->device));
-    GaloisLaunch L;
-    L.in = in->d;
-    L.out = out->d;
-    L.in_stride = in->stride();
-    L.out_stride = out->stride();
-    // in place: through a temporary, as the reference does for every call (tmpx, ring/ring.go:682-693)
     ScratchLease tmp;
-    const bool alias = in->d == out->d;
-    if (alias) {
-        LR_TRY(tmp.take(&c->scratch, (size_t)out->batch * (size_t)in->stride()));
-        LR_HIP(hipMemcpyAsync(tmp.d(), in->d, (size_t)out->batch * (size_t)in->stride() * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
-        L.in = tmp.d();
-    }
-    L.n = (int)c->h.N;
-    L.logn = (int)c->h.logN;
-    L.ntt_domain = 0;
-    L.gen = monomial_deg % (c->h.N << 1);      // ring/ring.go:667
-    L.lp = c->d_lp;
-    LR_HIP(launch_monomial(L, level + 1, out->batch, c->stream));
+    const u64 *src = nullptr;
+    LR_TRY(unaliased_input(c, in, out, &tmp, &src));
+    LR_HIP(launch_monomial(galois_launch(c, src, in->stride(), out, monomial_deg, false), level + 1, out->batch, c->stream));
     return LR_OK;
     });
 }
@@ -551,16 +585,12 @@ extern "C" int lr_shift(lr_context *c, const lr_poly *in, uint64_t n, lr_poly *o
     LR_TRY(check_pair(c, level, in, out));
     if (in->batch != out->batch) return fail(LR_ERR_SHAPE, "batch mismatch");
     const u64 N = c->h.N;
-    const u64 m = N >= 64 ? n : (n & (((u64)1 << N) - 1));
+    const u64 m = mask_shift_count(n, N);
     if (m > N) return fail(LR_ERR_ARG, "Shift: n exceeds the ring degree (the reference's slice expression panics)");
     LR_HIP(hipSetDevice(c->device));
-    const u64 *src = in->d;
     ScratchLease tmp;
-    if (in->d == out->d) {
-        LR_TRY(tmp.take(&c->scratch, (size_t)out->batch * (size_t)in->stride()));
-        LR_HIP(hipMemcpyAsync(tmp.d(), in->d, (size_t)out->batch * (size_t)in->stride() * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
-        src = tmp.d();
-    }
+    const u64 *src = nullptr;
+    LR_TRY(unaliased_input(c, in, out, &tmp, &src));
     const size_t pitch = (size_t)N * sizeof(u64), rows = (size_t)(level + 1);
     for (int b = 0; b < out->batch; ++b) {
         const u64 *s = src + (long long)b * in->stride();
@@ -584,7 +614,7 @@ extern "C" int lr_rotate(lr_context *c, lr_poly *p1, uint64_t n) {
     LR_TRY(check_pair(c, level, p1, p1));
     const u64 N = c->h.N;
     if (N < 2) return fail(LR_ERR_UNSUPPORTED, "N must be at least 2");
-    const u64 m = N >= 64 ? n : (n & (((u64)1 << N) - 1));
+    const u64 m = mask_shift_count(n, N);
     LR_HIP(hipSetDevice(c->device));
     const int L = level + 1;
     std::vector<u64> gal((size_t)L * N);
@@ -642,10 +672,6 @@ extern "C" int lr_permute_ntt_index(uint64_t gen, uint64_t power, uint64_t N, ui
     });
 }
 
-
-// ------------------------------------------------------------------------------------------
-// Decomposer
-// ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // SimpleScaler (ring/ring_scaling.go:166-300)
 // ------------------------------------------------------------------------------------------
@@ -723,7 +749,6 @@ extern "C" int lr_simple_scale(lr_simple_scaler *s, const lr_poly *p1, lr_poly *
     });
 }
 
-
 // ------------------------------------------------------------------------------------------
 // RNS rescale (ring/ring_scaling.go:9-164)
 // ------------------------------------------------------------------------------------------
@@ -737,25 +762,33 @@ int check_rescale(lr_context *c, lr_poly *p0) {
     return LR_OK;
 }
 
-// round == true adds the pHalf centring of :83-89 / :125-129
+// pHalf = (p_j - 1) / 2 of the last modulus p_j = q[level], and pHalfNegQi[i] = q_i - (pHalf mod q_i) for the limbs below it (:83-89 / :125-129)
+static u64 rescale_phalf(const lr_context *c, int level) { return (c->h.q[level] - 1) >> 1; }
+static LimbScalars phalf_neg_qi(const lr_context *c, int level) {
+    LimbScalars s{};
+    for (int i = 0; i < level; ++i) s.v[i] = c->h.q[i] - bred_add(rescale_phalf(c, level), c->h.q[i], c->h.bred[i].hi);
+    return s;
+}
+// the centring: pHalf is added to the last limb, in place (:87-89)
+static int add_phalf_to_last(lr_context *c, lr_poly *p0) {
+    const int level = p0->limbs - 1;
+    RowAddLaunch L;
+    L.in = L.out = p0->d + (long long)level * (long long)c->h.N;
+    L.in_stride = L.out_stride = p0->stride();
+    L.n = (int)c->h.N;
+    L.q = c->h.q[level];
+    L.adds = LimbScalars{};
+    L.adds.v[0] = rescale_phalf(c, level);
+    LR_HIP(launch_rowadd(L, 1, p0->batch, c->stream));
+    return LR_OK;
+}
+
+// round == true adds the pHalf centring
 int rescale_coeff_domain(lr_context *c, lr_poly *p0, bool round) {
-    const int level = p0->limbs - 1, n = (int)c->h.N, batch = p0->batch;
-    u64 *last = p0->d + (long long)level * n;
-    LimbScalars add;
-    std::memset(&add, 0, sizeof(add));
-    if (round) {
-        const u64 pj = c->h.q[level], phalf = (pj - 1) >> 1;
-        RowAddLaunch L;
-        L.in = last;
-        L.out = last;
-        L.in_stride = L.out_stride = p0->stride();
-        L.n = n;
-        L.q = pj;
-        std::memset(&L.adds, 0, sizeof(L.adds));
-        L.adds.v[0] = phalf;
-        LR_HIP(launch_rowadd(L, 1, batch, c->stream));
-        for (int i = 0; i < level; ++i) add.v[i] = c->h.q[i] - bred_add(phalf, c->h.q[i], c->h.bred[i].hi);  // pHalfNegQi
-    }
+    const int level = p0->limbs - 1, batch = p0->batch;
+    const u64 *last = p0->d + (long long)level * (long long)c->h.N;
+    if (round) LR_TRY(add_phalf_to_last(c, p0));
+    const LimbScalars add = round ? phalf_neg_qi(c, level) : LimbScalars{};
     LR_TRY(run_submul(c, level, batch, p0->d, p0->stride(), last, p0->stride(), 0, p0->d, p0->stride(),
                       c->d_rescale + (size_t)(level - 1) * c->h.L(), true, &add));
     p0->limbs = level;
@@ -767,13 +800,11 @@ int rescale_coeff_domain(lr_context *c, lr_poly *p0, bool round) {
 // polynomial is transformed as it is (one source row for all limbs, like the floor variant) and the constant vector joins
 // the subtract-multiply as its `plus` operand, already multiplied by -rescaleParams[i]: the same canonical residue without the
 // pass that writes `level` shifted copies of the row.  The table depends on the level only and is built once.
-int rescale_round_table(lr_context *c, int level, const u64 **out, const EpiLimb **epi_out, const u64 **zeros_out) {
+int rescale_round_table(lr_context *c, int level, const lr_context::RoundTable **out) {
     std::lock_guard<std::mutex> lock(c->rescale_mu);
     auto it = c->rescale_round.find(level);
     if (it != c->rescale_round.end()) {
-        *out = it->second.plus;
-        *epi_out = it->second.epi;
-        if (zeros_out) *zeros_out = it->second.zeros;
+        *out = &it->second;
         return LR_OK;
     }
     // built into locals; the cache only ever holds complete tables (a failure below leaves no entry behind)
@@ -795,7 +826,6 @@ int rescale_round_table(lr_context *c, int level, const u64 **out, const EpiLimb
     // the flooring division (DivFloorByLastModulusNTT) takes the same epilogue with nothing to add: rows of zeros in the same layout
     LR_HIP(hipMalloc((void **)&g.zeros, (size_t)words * sizeof(u64)));
     LR_HIP(hipMemsetAsync(g.zeros, 0, (size_t)words * sizeof(u64), c->stream));
-    const u64 pj = c->h.q[level], phalf = (pj - 1) >> 1;
     RowAddLaunch M;
     M.in = g.table;                     // a row of zeros
     M.in_stride = 0;
@@ -803,8 +833,7 @@ int rescale_round_table(lr_context *c, int level, const u64 **out, const EpiLimb
     M.out_stride = words;
     M.n = n;
     M.q = 0;
-    std::memset(&M.adds, 0, sizeof(M.adds));
-    for (int i = 0; i < level; ++i) M.adds.v[i] = c->h.q[i] - bred_add(phalf, c->h.q[i], c->h.bred[i].hi);   // pHalfNegQi
+    M.adds = phalf_neg_qi(c, level);
     LR_HIP(launch_rowadd(M, level, 1, c->stream));
     Rows tmp{tmpbuf.d(), words, 0, 1};
     LR_TRY(run_ntt(c, false, tmp, tmp, 0, 1, level, 1));
@@ -819,148 +848,126 @@ int rescale_round_table(lr_context *c, int level, const u64 **out, const EpiLimb
         }
         LR_TRY(to_device(&g.epi, ec.data(), ec.size()));
     }
-    c->rescale_round[level] = lr_context::RoundTable{g.table, g.epi, g.zeros};
-    *out = g.table;
-    *epi_out = g.epi;
-    if (zeros_out) *zeros_out = g.zeros;
+    *out = &(c->rescale_round[level] = lr_context::RoundTable{g.table, g.epi, g.zeros});
     g.table = nullptr;
     g.zeros = nullptr;
     g.epi = nullptr;
     return LR_OK;
 }
 
+// What one division in the NTT domain does, decided before its first launch.
+//   tables     the level's tables (rescale_round_table), unless rescale_unfused; the flooring division needs them for the epilogue only
+//   epilogue   (x - NTT_i(t)) * rescaleParams[i] + addend inside the forward transforms' copy-out, for every run of limbs that takes it
+//              (epilogue_run_end); the addend is the rounding's table or, flooring, the rows of zeros.  Otherwise the transforms go to
+//              scratch rows and one submul follows
+//   plus       the rounding's addend outside the epilogue: the table, or nothing (flooring; unfused rounding shifts the row first instead)
+//   fuse_mid   N = 2^15, a small launch whose every target limb takes the epilogue: the last limb's inverse sub-blocks stay lazy and ONE
+//              streaming kernel does what lies between them and the targets' forward sub-blocks (last inverse stage + scaling, + pHalf,
+//              forward top stage)
+struct RescalePlan {
+    const lr_context::RoundTable *tables = nullptr;
+    bool epilogue = false, fuse_mid = false;
+    const u64 *plus = nullptr, *epi_plus = nullptr;
+};
+static int rescale_plan(lr_context *c, int level, int batch, bool round, RescalePlan *out) {
+    RescalePlan p;
+    if (!c->opt.rescale_unfused && (round || ntt_epilogue_ok(c))) LR_TRY(rescale_round_table(c, level, &p.tables));
+    p.epilogue = p.tables && ntt_epilogue_ok(c);
+    if (p.tables) {
+        p.plus = round ? p.tables->plus : nullptr;
+        p.epi_plus = round ? p.tables->plus : p.tables->zeros;
+    }
+    p.fuse_mid = round && p.epilogue && c->h.logN == 15 && !c->opt.no_invtop && c->asm_inv >= 0 && ntt_split15(c, (long long)level * batch);
+    for (int l = 0; l < level && p.fuse_mid; ++l) p.fuse_mid = ntt_epilogue_limb(c, l);
+    *out = p;
+    return LR_OK;
+}
+
+// the forward transforms of one run of limbs [l0, l1) that takes the epilogue: the last limb's row under each of their moduli, into p0's rows
+static int rescale_epilogue_run(lr_context *c, lr_poly *p0, const RescalePlan &plan, u64 *scratch, int l0, int l1) {
+    const int level = p0->limbs - 1, batch = p0->batch;
+    const long long tmp_stride = (long long)level * (long long)c->h.N;
+    const NttEpilogue ep{p0->d, p0->stride(), plan.epi_plus, 0, plan.tables->epi};
+    const Rows last{p0->d, p0->stride(), level, 0}, dst{p0->d, p0->stride(), l0, 1};
+    if (!ntt_split15(c, (long long)(l1 - l0) * batch)) return run_ntt(c, false, last, dst, l0, 1, l1 - l0, batch, 0, 0, &ep);
+    // N = 2^15, a small launch: the transforms with the epilogue on two workgroups each (2^14 sub-blocks).  Every target
+    // limb has its own top-stage twiddle, so the stage over bit 14 goes to the scratch rows first (the streaming kernel,
+    // the last limb's row broadcast to one row per target limb); the sub-blocks read those and write p0's rows.
+    const Rows src{scratch, tmp_stride, l0, 1};
+    NttLaunch t = ntt_launch_args(c, NttRequest{false, last, src, l0, 1, l1 - l0, batch, 0, 0, nullptr, false, false});
+    t.tw_fin = nullptr;                 // (the streaming kernels read lp and tw alone: their argument block stays as it has been)
+    t.fp_tw_delta = t.fp_fin_delta = 0;
+    t.fp_lp = nullptr;
+    if (plan.fuse_mid) LR_HIP(launch_rescale_mid(t, c->d_inv, level, rescale_phalf(c, level), 15, stream_of(c)));
+    else LR_HIP(launch_ntt_top(t, 0, stream_of(c), 15));
+    return run_ntt(c, false, src, dst, l0, 1, l1 - l0, batch, 0, 0, &ep, true);
+}
+
 int rescale_ntt_domain(lr_context *c, lr_poly *p0, bool round) {
-    const int level = p0->limbs - 1, n = (int)c->h.N, batch = p0->batch;
-    const long long tmp_stride = (long long)level * n;
-    const u64 *plus = nullptr, *zeros = nullptr;
-    const EpiLimb *ec = nullptr;
-    if (!c->opt.rescale_unfused && (round || ntt_epilogue_ok(c))) LR_TRY(rescale_round_table(c, level, &plus, &ec, &zeros));
-    if (!round) plus = nullptr;       // (the rounding's addend; the flooring division adds the rows of zeros in the epilogue, nothing elsewhere)
-    const u64 *const epi_plus = round ? plus : zeros;
+    const int level = p0->limbs - 1, batch = p0->batch;
+    const long long n = (long long)c->h.N, tmp_stride = level * n;
+    RescalePlan plan;
+    LR_TRY(rescale_plan(c, level, batch, round, &plan));
     ScratchLease scratch;
     LR_TRY(scratch.take(&c->scratch, (size_t)batch * tmp_stride));
-    Rows last{p0->d, p0->stride(), level, 0};
-    // N = 2^15, a small launch whose every target limb takes the epilogue: the last limb's inverse sub-blocks stay lazy and ONE streaming
-    // kernel does what lies between them and the targets' forward sub-blocks (last inverse stage + scaling, + pHalf, forward top stage)
-    bool fuse_mid = round && plus && ntt_epilogue_ok(c) && c->h.logN == 15 && !c->opt.no_invtop && c->asm_inv >= 0 &&
-                    ntt_split15(c, (long long)level * batch);
-    for (int l = 0; l < level && fuse_mid; ++l) fuse_mid = ntt_epilogue_limb(c, l);
-    LR_TRY(run_ntt(c, true, last, last, level, 0, 1, batch, 0, 0, nullptr, false, fuse_mid));  // :15 / :80
-    Rows tmp{scratch.d(), tmp_stride, 0, 1};
-    if (round && !fuse_mid) {
-        const u64 pj = c->h.q[level], phalf = (pj - 1) >> 1;
-        RowAddLaunch L;
-        L.in = p0->d + (long long)level * n;
-        L.out = p0->d + (long long)level * n;
-        L.in_stride = L.out_stride = p0->stride();
-        L.n = n;
-        L.q = pj;
-        std::memset(&L.adds, 0, sizeof(L.adds));
-        L.adds.v[0] = phalf;
-        LR_HIP(launch_rowadd(L, 1, batch, c->stream));            // :87-89
-    }
-    if (epi_plus && ntt_epilogue_ok(c)) {
-        // (x - NTT_i(t)) * rescaleParams[i] + plus inside the forward transform's copy-out for the runs of limbs below 2^46
-        const long long n64 = (long long)n;
-        int l0 = 0;
-        while (l0 < level) {
-            const bool fpc = ntt_epilogue_limb(c, l0);
-            int l1 = l0 + 1;
-            while (l1 < level && ntt_epilogue_limb(c, l1) == fpc) ++l1;
-            if (fpc && ntt_split15(c, (long long)(l1 - l0) * batch)) {
-                // N = 2^15, a small launch: the transforms with the epilogue on two workgroups each (2^14 sub-blocks).  Every target
-                // limb has its own top-stage twiddle, so the stage over bit 14 goes to the scratch rows first (the streaming kernel,
-                // the last limb's row broadcast to one row per target limb); the sub-blocks read those and write p0's rows.
-                NttLaunch t;
-                std::memset(&t, 0, sizeof t);
-                t.in = p0->d;
-                t.in_poly_stride = p0->stride();
-                t.in_limb0 = level;
-                t.in_limb_step = 0;
-                t.out = scratch.d();
-                t.out_poly_stride = tmp_stride;
-                t.out_limb0 = l0;
-                t.out_limb_step = 1;
-                t.mod0 = l0;
-                t.mod_step = 1;
-                t.n_items = l1 - l0;
-                t.batch = batch;
-                t.lp = c->d_lp;
-                t.tw = c->d_fwd;
-                if (fuse_mid) LR_HIP(launch_rescale_mid(t, c->d_inv, level, (c->h.q[level] - 1) >> 1, 15, stream_of(c)));
-                else LR_HIP(launch_ntt_top(t, 0, stream_of(c), 15));
-                const NttEpilogue ep{p0->d, p0->stride(), epi_plus, 0, ec};
-                Rows src{scratch.d(), tmp_stride, l0, 1}, dst{p0->d, p0->stride(), l0, 1};
-                LR_TRY(run_ntt(c, false, src, dst, l0, 1, l1 - l0, batch, 0, 0, &ep, true));
-            } else if (fpc) {
-                const NttEpilogue ep{p0->d, p0->stride(), epi_plus, 0, ec};
-                Rows dst{p0->d, p0->stride(), l0, 1};
-                LR_TRY(run_ntt(c, false, last, dst, l0, 1, l1 - l0, batch, 0, 0, &ep));
-            } else {
-                Rows dst{scratch.d(), tmp_stride, l0, 1};
-                LR_TRY(run_ntt(c, false, last, dst, l0, 1, l1 - l0, batch));
-                LR_TRY(run_submul(c, l1 - l0, batch, p0->d + l0 * n64, p0->stride(), scratch.d() + l0 * n64, tmp_stride, n64,
-                                  p0->d + l0 * n64, p0->stride(), c->d_rescale + (size_t)(level - 1) * c->h.L() + l0, false, nullptr,
-                                  plus ? plus + l0 * n64 : nullptr, 0, nullptr, l0));
+    const Rows last{p0->d, p0->stride(), level, 0}, tmp{scratch.d(), tmp_stride, 0, 1};
+    const u64 *const consts = c->d_rescale + (size_t)(level - 1) * c->h.L();
+    // the last limb back to the coefficient domain (:15 / :80), centred (:87-89) unless the streaming kernel between the sub-blocks does both
+    LR_TRY(run_ntt(c, true, last, last, level, 0, 1, batch, 0, 0, nullptr, false, plan.fuse_mid));
+    if (round && !plan.fuse_mid) LR_TRY(add_phalf_to_last(c, p0));
+    if (plan.epilogue) {
+        for (int l0 = 0, l1; l0 < level; l0 = l1) {
+            bool takes;
+            l1 = epilogue_run_end(c, l0, level, &takes);
+            if (takes) {
+                LR_TRY(rescale_epilogue_run(c, p0, plan, scratch.d(), l0, l1));
+                continue;
             }
-            l0 = l1;
+            LR_TRY(run_ntt(c, false, last, Rows{scratch.d(), tmp_stride, l0, 1}, l0, 1, l1 - l0, batch));
+            LR_TRY(run_submul(c, l1 - l0, batch, p0->d + l0 * n, p0->stride(), scratch.d() + l0 * n, tmp_stride, n, p0->d + l0 * n, p0->stride(),
+                              consts + l0, false, nullptr, plan.plus ? plan.plus + l0 * n : nullptr, 0, nullptr, l0));
         }
         p0->limbs = level;
         return LR_OK;
     }
-    if (round && plus) {
-        LR_TRY(run_ntt(c, false, last, tmp, 0, 1, level, batch));  // NTT_i(t); the shift by pHalfNegQi[i] rides in `plus`
-    } else if (round) {
-        const u64 pj = c->h.q[level], phalf = (pj - 1) >> 1;
+    // NTT_i(t) for every limb below the last (:19), then ONE submul; the rounding's shift by pHalfNegQi[i] rides in `plus`, or -- unfused --
+    // goes into `level` shifted copies of the row before the transforms (:101-105)
+    if (round && !plan.plus) {
         RowAddLaunch M;
-        M.in = p0->d + (long long)level * n;
+        M.in = p0->d + level * n;
         M.in_stride = p0->stride();
         M.out = scratch.d();
         M.out_stride = tmp_stride;
-        M.n = n;
+        M.n = (int)n;
         M.q = 0;
-        std::memset(&M.adds, 0, sizeof(M.adds));
-        for (int i = 0; i < level; ++i) M.adds.v[i] = c->h.q[i] - bred_add(phalf, c->h.q[i], c->h.bred[i].hi);
-        LR_HIP(launch_rowadd(M, level, batch, c->stream));        // :101-103
-        LR_TRY(run_ntt(c, false, tmp, tmp, 0, 1, level, batch));  // :105
-    } else {
-        LR_TRY(run_ntt(c, false, last, tmp, 0, 1, level, batch));  // :19: NTT of the last limb under modulus i
+        M.adds = phalf_neg_qi(c, level);
+        LR_HIP(launch_rowadd(M, level, batch, c->stream));
     }
-    LR_TRY(run_submul(c, level, batch, p0->d, p0->stride(), scratch.d(), tmp_stride, (long long)n, p0->d, p0->stride(),
-                      c->d_rescale + (size_t)(level - 1) * c->h.L(), false, nullptr, plus, 0));
+    LR_TRY(run_ntt(c, false, round && !plan.plus ? tmp : last, tmp, 0, 1, level, batch));
+    LR_TRY(run_submul(c, level, batch, p0->d, p0->stride(), scratch.d(), tmp_stride, n, p0->d, p0->stride(), consts, false, nullptr, plan.plus, 0));
     p0->limbs = level;
     return LR_OK;
 }
 
 }  // namespace lr_host
 
-extern "C" int lr_div_floor_by_last_modulus_ntt(lr_context *c, lr_poly *p0) {
-    return guarded([&]() -> int {
+// the four single divisions: DivFloor / DivRound ByLastModulus (NTT)
+static int rescale_one(lr_context *c, lr_poly *p0, bool ntt_domain, bool round) {
     LR_TRY(check_rescale(c, p0));
     LR_HIP(hipSetDevice(c->device));
-    return rescale_ntt_domain(c, p0, false);
-    });
+    return ntt_domain ? rescale_ntt_domain(c, p0, round) : rescale_coeff_domain(c, p0, round);
+}
+extern "C" int lr_div_floor_by_last_modulus_ntt(lr_context *c, lr_poly *p0) {
+    return guarded([&]() -> int { return rescale_one(c, p0, true, false); });
 }
 extern "C" int lr_div_floor_by_last_modulus(lr_context *c, lr_poly *p0) {
-    return guarded([&]() -> int {
-    LR_TRY(check_rescale(c, p0));
-    LR_HIP(hipSetDevice(c->device));
-    return rescale_coeff_domain(c, p0, false);
-    });
+    return guarded([&]() -> int { return rescale_one(c, p0, false, false); });
 }
 extern "C" int lr_div_round_by_last_modulus_ntt(lr_context *c, lr_poly *p0) {
-    return guarded([&]() -> int {
-    LR_TRY(check_rescale(c, p0));
-    LR_HIP(hipSetDevice(c->device));
-    return rescale_ntt_domain(c, p0, true);
-    });
+    return guarded([&]() -> int { return rescale_one(c, p0, true, true); });
 }
 extern "C" int lr_div_round_by_last_modulus(lr_context *c, lr_poly *p0) {
-    return guarded([&]() -> int {
-    LR_TRY(check_rescale(c, p0));
-    LR_HIP(hipSetDevice(c->device));
-    return rescale_coeff_domain(c, p0, true);
-    });
+    return guarded([&]() -> int { return rescale_one(c, p0, false, true); });
 }
 
 static int rescale_many(lr_context *c, lr_poly *p0, int nb, int ntt_domain, bool round) {
@@ -983,7 +990,6 @@ extern "C" int lr_div_round_by_last_modulus_many(lr_context *c, lr_poly *p0, int
     return rescale_many(c, p0, nb, ntt_domain, true);
     });
 }
-
 
 // diagnostics: the basis extension's division by a table constant (lr_bext.hip: div_by_const) against the IEEE division of
 // ring/ring_basis_extension.go:372 on `samples` pseudo-random and adversarial operand pairs; *mismatches must come back 0

@@ -583,12 +583,19 @@ bool ntt_epilogue_ok(const lr_context *c);
 bool ntt_epilogue_limb(const lr_context *c, int l);
 EpiLimb make_epi_limb(const lr_context *c, int l, u64 cc);
 bool ntt_split15(const lr_context *c, long long workgroups);
+// the limbs [l0, end) in runs that agree on ntt_epilogue_limb: the end of the run that starts at l0, and whether it takes the epilogue
+inline int epilogue_run_end(const lr_context *c, int l0, int end, bool *takes) {
+    *takes = ntt_epilogue_limb(c, l0);
+    int l1 = l0 + 1;
+    while (l1 < end && ntt_epilogue_limb(c, l1) == *takes) ++l1;
+    return l1;
+}
 int run_ntt(lr_context *c, bool inverse, Rows in, Rows out, int mod0, int mod_step, int count, int batch, int hole = 0, int group = 0, const NttEpilogue *epi = nullptr, bool pretop = false, bool lazy = false);
 int check_pair(const lr_context *c, int level, const lr_poly *in, const lr_poly *out);
 Rows rows_of(const lr_poly *p, int limb0 = 0, int step = 1, bool broadcast_ok = false, int target_batch = 0);
 int run_ewise(lr_context *c, int op, int limbs, int batch, const u64 *a, long long a_stride, const u64 *b, long long b_stride, u64 *out, long long out_stride, const LimbScalars *sc, int lp_offset = 0);
 int rescale_ntt_domain(lr_context *c, lr_poly *p0, bool round);
-int rescale_round_table(lr_context *c, int level, const u64 **out, const EpiLimb **epi_out, const u64 **zeros_out = nullptr);
+int rescale_round_table(lr_context *c, int level, const lr_context::RoundTable **out);
 int check_rescale(lr_context *c, lr_poly *p0);
 // lr_abi_bext.cpp: basis extension and decomposition on raw rows
 ExtSegment segment(u64 *out, long long stride, int limb0, int col0, int count);

@@ -85,16 +85,6 @@ hipError_t launch_ntt_asm16(const NttLaunch &a, int inverse, char kind, int vari
 }
 hipError_t launch_ntt_top(const NttLaunch &a, int, hipStream_t, int logn) { return ntt_like(a, 1ll << logn, false); }
 hipError_t launch_rescale_mid(const NttLaunch &a, const Twiddle *, int, u64, int logn, hipStream_t) { return ntt_like(a, 1ll << logn, false); }
-bool ntt_rows_disjoint(const NttLaunch &a, int logn) {          // (the predicate of lr_ntt.hip, host arithmetic only)
-    const long long n_full = 1ll << logn;
-    const long long last = (long long)(a.n_items - 1 + (a.hole > 0 ? a.hole : 0));
-    const u64 *in_lo = a.in + (long long)a.in_limb0 * n_full;
-    const u64 *in_hi = a.in + (long long)(a.batch - 1) * a.in_poly_stride + ((long long)a.in_limb0 + last * a.in_limb_step + 1) * n_full;
-    const u64 *out_lo = a.out + (long long)a.out_limb0 * n_full;
-    const u64 *out_hi = a.out + (long long)(a.batch - 1) * a.out_poly_stride + ((long long)a.out_limb0 + last * a.out_limb_step + 1) * n_full;
-    if (a.in_poly_stride < 0 || a.out_poly_stride < 0 || a.in_limb_step < 0 || a.out_limb_step < 0) return false;
-    return in_hi <= out_lo || out_hi <= in_lo;
-}
 
 hipError_t launch_ewise(int op, const EwiseLaunch &L, int limbs, int batch, hipStream_t) {
     g_stub_launches.fetch_add(1);

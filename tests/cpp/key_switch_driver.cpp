@@ -5,7 +5,7 @@
 // lr_ckks_rotate_hoisted (two rotations), lr_ckks_rescale, lr_bfv_switch_keys, lr_bfv_relinearize and lr_bfv_rotate over
 //   * N = 2^12 (|Q| = 5, |P| = 3: digits of 3 + 2 limbs), 2^15 (|Q| = 5, |P| = 2: 2 + 2 + 1) and 2^16 (|Q| = 4, |P| = 2, the six primes there are:
 //     the top-stage extensions, the staging buffers and the forks of a lone plan), every level from 0 to |Q| - 1 -- full digits, partial last
-//     digits, single-limb digits, the trivial-copy branch (the stand-in has no 2^16 rescale kernels: lr_ckks_rescale at the two others);
+//     digits, single-limb digits, the trivial-copy branch;
 //   * batches 1, 2 and 5, and once more with pair_max_workgroups and fork_below_workgroups lowered to 4 (both sides of each threshold);
 //   * every launch-shape option of the plan;
 //   * outputs written over operands and over each other where the entry point allows it (the paired launches' refusal side);
@@ -151,7 +151,7 @@ static void calls(const Plan &P, int batch) {
             RUN(lr_ckks_mulrelin(P.pl, level, a0, a1, b0, b1, P.key, o1, o0));
             RUN(lr_ckks_rotate(P.pl, level, a0, a1, 5, P.key, o1, o0));
         }
-        if (level > 0 && P.r.N < (1u << 16)) {
+        if (level > 0) {
             // (rescale drops a limb: the handles get their limb count back)
             lr_poly *r0 = poly(q, level + 1, batch), *r1 = poly(q, level + 1, batch), *both = poly(q, level + 1, 2 * batch);
             RUN(lr_ckks_rescale(P.pl, r0, r1));

@@ -22,9 +22,9 @@ def test_key_switch_host_side_under_asan_ubsan(tmp_path):
     assert "failures 0" in res.stdout, res.stdout
     calls = int(res.stdout.split("calls ")[1].split(",")[0])
     refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
-    # per plan (3 rings x 10 option sets) and batch (1, 2, 5): 17 CKKS calls at each of the |Q| levels, 11 BFV calls, and below N = 2^16
-    # 3 more CKKS calls per level (descending outputs) and 4 rescales at each level above 0 (3 at level 1); |Q| = 5, 5 and 4
-    per_batch = lambda nq, below16: 17 * nq + 11 + (3 * nq + 4 * (nq - 1) - 1 if below16 else 0)
+    # per plan (3 rings x 10 option sets) and batch (1, 2, 5): 17 CKKS calls at each of the |Q| levels, 11 BFV calls, 4 rescales at each level
+    # above 0 (3 at level 1), and below N = 2^16 3 more CKKS calls per level (descending outputs); |Q| = 5, 5 and 4
+    per_batch = lambda nq, below16: 17 * nq + 11 + 4 * (nq - 1) - 1 + (3 * nq if below16 else 0)
     # ... and per plan, each of the 7 entry points twice on a plan of its own
     assert calls == 10 * 3 * (2 * per_batch(5, True) + per_batch(4, False)) + 3 * 10 * 7 * 2, res.stdout
     assert refusals == 3 * 10 * REFUSALS_PER_PLAN, res.stdout

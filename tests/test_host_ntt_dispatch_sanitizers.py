@@ -1,0 +1,60 @@
+"""The transform dispatch (lr_abi_ring.cpp: the route decision ntt_route and the launch switch behind run_ntt), the RNS rescale's plan and stages
+and the epilogue-run iterator with its three users, under AddressSanitizer + UBSan (CPU build only).  The product's host code is compiled with
+g++ against the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/ (host_stub_build.py) and driven by
+tests/cpp/ntt_dispatch_driver.cpp through the public ABI: N = 2^10 .. 2^16, moduli sets for the forward variants 0 .. 3, every option that
+changes a route, batches 1 and 3 and one launch that crosses run_ntt's chunking, in place and out of place, and every refusal.  After each
+call the driver reads the name of the kernel the context dispatched; the set of names per (ring, moduli, options) is compared with
+tests/golden/ntt_dispatch_routes.txt, which was recorded from the dispatcher as it was before it was split into decision and launches."""
+import os
+import subprocess
+
+from conftest import ROOT
+from host_stub_build import build_host_driver
+
+# one name per route of NttRoute::Kind that a public call can end on ("xK": a plain transform call of K launches; without: the last
+# transform of a compound call).  The lazy inverse routes are always followed by another transform inside the call that asks for them, and
+# the stamped route needs a diagnostics build: the GPU suite covers those.
+ROUTE_WITNESSES = {
+    "Cxx": ["ntt_fwd_kernel<10>x1", "ntt_inv_kernel<16>x1"],
+    "Whole": ["stub_fwd12_m1x1", "stub_fwd14_m3x1", "stub_inv15_m3x1", "stub_fwd14_m4", "stub_fwd12_m5", "stub_fwd15_m4"],
+    "Split15Top": ["stub_fwd15h_m3x2", "stub_fwd15h_m0x2"],
+    "Split15Pretop": ["stub_fwd15h_m4", "stub_fwd15h_m5"],
+    "Split15InvTop": ["stub_inv15h_m3x2"],
+    "Fwd16Pretop": ["stub_fwd16p_m4", "stub_fwd16p_m5"],
+    "Fwd16Fused": ["stub_fwd16s_m3x1", "stub_fwd16s_m4", "stub_fwd16s_m5"],
+    "Fwd16Top": ["stub_fwd16p_m3x2", "stub_fwd16p_m3x4"],
+    "Inv16PairFlags": ["stub_inv16f_m3x1", "stub_inv16f_m3x2"],
+    "Inv16Top": ["stub_inv16s_m3x2"],
+}
+
+
+def test_ntt_dispatch_host_side_under_asan_ubsan(tmp_path):
+    exe = build_host_driver(str(tmp_path), "ntt_dispatch_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan")
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the contexts' options decide the routes, not the caller's env
+    env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
+    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
+    assert "failures 0" in res.stdout, res.stdout[-2000:]
+    calls = int(res.stdout.split("calls ")[1].split(",")[0])
+    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
+    # 5 rings x 4 moduli sets x 10 option sets, one more option set at N = 2^14 and three more at N = 2^15
+    configs = 4 * (5 * 10 + 1 + 3)
+    # per batch (1 and 3): 18 + 10 transforms, 4 x 5 + 2 x 5 divisions, 3 x 3 rescales of a ciphertext, 3 x 3 ModDowns, 4 x 3 monomial products,
+    # 3 x 4 permutations, 2 key switches; the six host-slice transforms at batch 1 only; the three calls of the chunked launch once
+    assert calls == configs * (2 * (28 + 30 + 9 + 9 + 12 + 12 + 2) + 6) + 3, res.stdout[-300:]
+    assert refusals == configs * REFUSALS_PER_CONFIG, res.stdout[-300:]
+    got = [ln for ln in res.stdout.splitlines() if ln.startswith("routes ")]
+    want = open(os.path.join(ROOT, "tests", "golden", "ntt_dispatch_routes.txt")).read().splitlines()
+    assert len(got) == configs
+    for g, w in zip(got, want):
+        assert g == w
+    assert len(got) == len(want)
+    names = {n for ln in got for n in ln.split(":", 1)[1].split()}
+    for route, witnesses in ROUTE_WITNESSES.items():
+        for w in witnesses:
+            assert w in names, (route, w)
+
+
+# lr_ntt / lr_intt 9 each, lr_ntt_limb / lr_intt_limb 8 each, lr_ntt_host / lr_intt_host 5 each, lr_ntt_host_limb 4, the four single divisions 4 each,
+# the two ...Many 4 in either domain, lr_ckks_rescale 3, the ModDowns 4, lr_mult_by_monomial 4, lr_shift 5, lr_permute 4, lr_permute_ntt 4
+REFUSALS_PER_CONFIG = 2 * 9 + 2 * 8 + 2 * 5 + 4 + 4 * 4 + 2 * 2 * 4 + 3 + 4 + 4 + 5 + 4 + 4
