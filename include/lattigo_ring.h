@@ -117,6 +117,8 @@ typedef struct lr_options {
     int32_t bfv_no_ext_epilogue;    /* SubScalarBigint / MulScalar as separate passes                                                 */
     int32_t bfv_no_gather;          /* never gather the four operand polys of a small batch into one buffer                           */
     int64_t bfv_gather_below;       /* gather while the joint transform has fewer workgroups than this (1536)                         */
+    /* --- bfv Encoder (lr_bfv_encoder) */
+    int32_t bfv_encoder_unfused;    /* scatter / InvNTT / lift and scale / NTT / gather as separate launches where the fused kernels would run */
 } lr_options;
 /* fills *opt with the defaults (struct_size = sizeof(lr_options) of THIS library, version = LR_OPTIONS_VERSION) */
 int lr_options_init(lr_options *opt);
@@ -499,6 +501,36 @@ int lr_bfv_batcher_mul(lr_bfv_batcher *batcher, const lr_poly *ct0_c0, const lr_
 int lr_bfv_batcher_relinearize(lr_bfv_batcher *batcher, const lr_poly *c0, const lr_poly *c1, const lr_poly *c2, const lr_poly *evk,
                                lr_poly *out0, lr_poly *out1);
 int lr_bfv_batcher_stats(lr_bfv_batcher *batcher, uint64_t *batches, uint64_t *products, int *largest);
+
+/* bfv.Encoder (bfv/encoder.go:10-182) for a batch of plaintexts, device-resident.  lr_bfv_encoder owns what bfv.NewEncoder builds (:28-68):
+ * contextT = (N, [t]) with the reference's psi, indexMatrix (:36-58, GaloisGen = 5), deltaMont = GenLiftParams(contextQ, t)
+ * (bfv/utils.go:9-23), NewSimpleScaler(t, contextQ) and the one-limb polypool, for up to max_batch plaintexts per call.  A t that does not
+ * allow an NTT at N is LR_ERR_NOT_NTT_FRIENDLY with lr_context_create's message; t == 0 and max_batch outside 1 .. 65535 are LR_ERR_ARG.
+ * Two routes, the same bits, chosen once at creation: for 2^11 <= N <= 2^15 and t < 2^31 one kernel per direction with one workgroup per
+ * plaintext and the transform over Z_t in LDS; otherwise (or with lr_options::bfv_encoder_unfused) the transform of contextT between
+ * small scatter / lift / gather kernels.  The work is ordered on ctxQ's stream. */
+typedef struct lr_bfv_encoder lr_bfv_encoder;
+int lr_bfv_encoder_create(lr_context *ctxQ, uint64_t t, int max_batch, lr_bfv_encoder **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_bfv_encoder_create_ex(lr_context *ctxQ, uint64_t t, int max_batch, const lr_options *opt, lr_bfv_encoder **out);
+int lr_bfv_encoder_destroy(lr_bfv_encoder *enc);
+/* host copies of indexMatrix[N] and deltaMont[|Q|], for parity tests */
+int lr_bfv_encoder_tables(const lr_bfv_encoder *enc, uint64_t *index_matrix, uint64_t *delta_mont);
+/* diagnostics: *fused = 1 when the handle runs the fused kernels, 0 on the composed route */
+int lr_bfv_encoder_route(const lr_bfv_encoder *enc, int *fused);
+/* EncodeUint / EncodeInt (:70-119): values = host [batch][n_values], n_values <= N (more: LR_ERR_SHAPE, the reference panics); slot i goes
+ * to coefficient indexMatrix[i], the slots from n_values on are zero; pt over all of Q, coefficient domain, of the same batch
+ * (batch != the poly's or > max_batch, or fewer than |Q| limbs: LR_ERR_SHAPE; a poly of another context: LR_ERR_ARG).  Uint values are
+ * taken modulo t, Int values map to their residue in [0, t) (the reference's t + c for -t <= c < 0).  The values are staged through a
+ * pinned buffer of the handle: the caller's array is free on return, the encoding is asynchronous. */
+int lr_bfv_encode_uint(lr_bfv_encoder *enc, const uint64_t *values, size_t n_values, int batch, lr_poly *pt);
+int lr_bfv_encode_int(lr_bfv_encoder *enc, const int64_t *values, size_t n_values, int batch, lr_poly *pt);
+/* DecodeUint / DecodeInt (:139-182): values = host [batch][N]; DecodeInt subtracts t from the slots above t >> 1.  Synchronises. */
+int lr_bfv_decode_uint(lr_bfv_encoder *enc, const lr_poly *pt, int batch, uint64_t *values);
+int lr_bfv_decode_int(lr_bfv_encoder *enc, const lr_poly *pt, int batch, int64_t *values);
+/* the same on slots in device memory ([batch][n_values] / [batch][N] words, uint64 or, with is_signed, int64): stream-ordered, no host copy */
+int lr_bfv_encode_device(lr_bfv_encoder *enc, const void *device_values, size_t n_values, int batch, int is_signed, lr_poly *pt);
+int lr_bfv_decode_device(lr_bfv_encoder *enc, const lr_poly *pt, int batch, int is_signed, void *device_values);
 
 /* ------------------------------------------------------------------ multi-device ------ */
 /* a batch of independent ciphertexts shards across the GPUs of a node by contiguous blocks (replicated contexts, tables

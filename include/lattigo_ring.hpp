@@ -187,4 +187,40 @@ class SimpleScaler {
     lr_simple_scaler *h_ = nullptr;
 };
 
+// bfv.Encoder (bfv/encoder.go:10-182) for batches of plaintexts; slots are [batch][n] host arrays, plaintexts Polys over contextQ
+class BfvEncoder {
+  public:
+    BfvEncoder(const Context *contextQ, uint64_t t, int max_batch = 1, const lr_options *options = nullptr) : N_(contextQ->N) {   // NewEncoder :28
+        check(lr_bfv_encoder_create_ex(contextQ->handle(), t, max_batch, options, &h_));
+    }
+    ~BfvEncoder() { lr_bfv_encoder_destroy(h_); }
+    BfvEncoder(const BfvEncoder &) = delete;
+    BfvEncoder &operator=(const BfvEncoder &) = delete;
+    void EncodeUint(const std::vector<uint64_t> &coeffs, int batch, Poly *plaintext) {                                            // :71
+        check(lr_bfv_encode_uint(h_, coeffs.data(), coeffs.size() / (size_t)batch, batch, plaintext->handle()));
+    }
+    void EncodeInt(const std::vector<int64_t> &coeffs, int batch, Poly *plaintext) {                                              // :95
+        check(lr_bfv_encode_int(h_, coeffs.data(), coeffs.size() / (size_t)batch, batch, plaintext->handle()));
+    }
+    std::vector<uint64_t> DecodeUint(const Poly *plaintext, int batch) {                                                          // :140
+        std::vector<uint64_t> coeffs((size_t)batch * N_);
+        check(lr_bfv_decode_uint(h_, plaintext->handle(), batch, coeffs.data()));
+        return coeffs;
+    }
+    std::vector<int64_t> DecodeInt(const Poly *plaintext, int batch) {                                                            // :158
+        std::vector<int64_t> coeffs((size_t)batch * N_);
+        check(lr_bfv_decode_int(h_, plaintext->handle(), batch, coeffs.data()));
+        return coeffs;
+    }
+    bool Fused() const {
+        int f = 0;
+        check(lr_bfv_encoder_route(h_, &f));
+        return f != 0;
+    }
+
+  private:
+    uint64_t N_;
+    lr_bfv_encoder *h_ = nullptr;
+};
+
 }  // namespace ring

@@ -24,7 +24,7 @@ class Options(C.Structure):
         "no_asm", "no_fp", "ntt_mode", "asm_variant", "asm14_1024", "no_wide14_small", "wide14_max_items", "ntt_split15", "split15_max_workgroups",
         "no_invfuse", "no_grid_padding", "ntt_stagger", "ntt_persist", "ntt_timeline", "no_epilogue", "no_int_epilogue", "rescale_unfused",
         "rescale_unpaired", "pair_max_workgroups", "ext_narrow", "ext_ieee_div", "no_ext_chunks", "no_staging", "no_exttop", "no_invtop",
-        "no_ext_group", "keymac_narrow", "no_pair", "no_fork", "fork_below_workgroups", "bfv_no_ext_epilogue", "bfv_no_gather")] + [("bfv_gather_below", C.c_int64)]
+        "no_ext_group", "keymac_narrow", "no_pair", "no_fork", "fork_below_workgroups", "bfv_no_ext_epilogue", "bfv_no_gather")] + [("bfv_gather_below", C.c_int64), ("bfv_encoder_unfused", C.c_int32)]
 
     def __init__(self, **fields):
         super().__init__()
@@ -141,6 +141,17 @@ SYMBOLS = {
     "lr_bfv_batcher_mul": [vp, vp, vp, vp, vp, vp, vp, vp],
     "lr_bfv_batcher_relinearize": [vp, vp, vp, vp, vp, vp, vp],
     "lr_bfv_batcher_stats": [vp, vp, vp, vp],
+    "lr_bfv_encoder_create": [vp, u64, i32, C.POINTER(vp)],
+    "lr_bfv_encoder_create_ex": [vp, u64, i32, vp, C.POINTER(vp)],
+    "lr_bfv_encoder_destroy": [vp],
+    "lr_bfv_encoder_tables": [vp, u64p, u64p],
+    "lr_bfv_encoder_route": [vp, C.POINTER(i32)],
+    "lr_bfv_encode_uint": [vp, vp, C.c_size_t, i32, vp],
+    "lr_bfv_encode_int": [vp, vp, C.c_size_t, i32, vp],
+    "lr_bfv_decode_uint": [vp, vp, i32, vp],
+    "lr_bfv_decode_int": [vp, vp, i32, vp],
+    "lr_bfv_encode_device": [vp, vp, C.c_size_t, i32, i32, vp],
+    "lr_bfv_decode_device": [vp, vp, i32, i32, vp],
     "lr_poly_copy_peer": [vp, vp, i32, vp, vp, i32, i32],
     "lr_context_wait_peer_copies": [vp],
     "lr_gather_blocks": [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32],

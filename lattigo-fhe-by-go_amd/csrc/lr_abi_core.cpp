@@ -71,6 +71,7 @@ void lr::Options::apply_env() {
     flag("LR_BFV_NO_EXT_EPILOGUE", bfv_no_ext_epilogue);
     flag("LR_BFV_NO_GATHER", bfv_no_gather);
     if (const char *gb = std::getenv("LR_BFV_GATHER_BELOW")) bfv_gather_below = std::atoll(gb);
+    flag("LR_BFV_ENCODER_UNFUSED", bfv_encoder_unfused);
     num("LR_NTT_SPLIT15_BELOW", split15_max_workgroups);
     num("LR_FORK_BELOW", fork_below_workgroups);
 }
@@ -120,6 +121,7 @@ int options_from_public(const lr_options *pub, Options *out) {
         o.bfv_no_ext_epilogue = p.bfv_no_ext_epilogue != 0;
         o.bfv_no_gather = p.bfv_no_gather != 0;
         if (p.bfv_gather_below > 0) o.bfv_gather_below = p.bfv_gather_below;
+        o.bfv_encoder_unfused = p.bfv_encoder_unfused != 0;
     }
     o.apply_env();
 #ifndef LR_BUILD_DIAG
@@ -142,7 +144,7 @@ void options_to_public(const Options &o, lr_options *p) {
     p->no_ext_chunks = o.no_ext_chunks; p->no_staging = o.no_staging; p->no_exttop = o.no_exttop; p->no_invtop = o.no_invtop;
     p->no_ext_group = o.no_ext_group; p->keymac_narrow = o.keymac_narrow; p->no_pair = o.no_pair; p->no_fork = o.no_fork;
     p->fork_below_workgroups = o.fork_below_workgroups; p->bfv_no_ext_epilogue = o.bfv_no_ext_epilogue; p->bfv_no_gather = o.bfv_no_gather;
-    p->bfv_gather_below = o.bfv_gather_below;
+    p->bfv_gather_below = o.bfv_gather_below; p->bfv_encoder_unfused = o.bfv_encoder_unfused;
 }
 
 }  // namespace lr_host

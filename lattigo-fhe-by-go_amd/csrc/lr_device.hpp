@@ -63,6 +63,7 @@ struct Options {
     int pair_max_workgroups = 256;      // two components of one ciphertext / the Q and P parts of one inner product as one launch up to here
     int fork_below_workgroups = 256;    // LR_FORK_BELOW: a lone plan forks a launch below this many workgroups
     long long bfv_gather_below = 1536;  // LR_BFV_GATHER_BELOW
+    bool bfv_encoder_unfused = false;   // LR_BFV_ENCODER_UNFUSED: the encoder's composed route where the fused kernels would run
     void apply_env();              // the test-only override: the ONE place that reads LR_* variables
     static Options from_env() {    // defaults + the override: what the plain *_create entry points use
         Options o;
@@ -340,6 +341,46 @@ struct ScaleLaunch {
     int pow2, limbs_in, limbs_out, n;
 };
 hipError_t launch_simple_scale(const ScaleLaunch &L, int batch, hipStream_t stream);
+
+// ---- bfv.Encoder (lr_bfv_encode.hip): EncodeUint / EncodeInt / DecodeUint / DecodeInt of bfv/encoder.go for a batch of plaintexts ----
+// a power of psi modulo a plaintext modulus t < 2^31 in 32-bit Shoup form: w plain, ws = floor(w 2^32 / t)
+struct Tw32 { u32 w, ws; };
+// what both routes share: indexMatrix (bfv/encoder.go:36-58) and the plaintext modulus with floor(2^64 / t) (BRedParams(t)[0])
+struct EncoderTables {
+    const u32 *index;      // [N]
+    u64 t, t_bred_hi;
+    int n, logn;
+};
+// fused routes, one workgroup per plaintext, the transform over Z_t in LDS (N <= 2^15, t < 2^31)
+struct EncodeLaunch {
+    EncoderTables tab;
+    const void *values;    // device [batch][n_values] uint64 or int64
+    long long n_values;
+    int is_signed;
+    const Tw32 *tw_inv;    // [N]: the [t] context's nttPsiInv out of Montgomery form
+    Tw32 n_inv;
+    u64 *out;              // plaintext polys over Q, coefficient domain
+    long long out_stride;
+    int limbs;
+    const LimbParams *lp;  // of contextQ
+    const u64 *delta_mont; // [limbs] MForm(floor(Q / t) mod q_i), bfv/utils.go:9-23
+};
+hipError_t launch_bfv_encode_fused(const EncodeLaunch &L, int batch, hipStream_t stream);
+struct DecodeLaunch {
+    EncoderTables tab;
+    const u64 *in;         // [batch][N]: SimpleScaler's one-limb output, values below t
+    const Tw32 *tw_fwd;    // [N]: nttPsi out of Montgomery form
+    void *values;          // device [batch][N] uint64, or int64 centred around 0 (is_signed)
+    int is_signed;
+};
+hipError_t launch_bfv_decode_fused(const DecodeLaunch &L, int batch, hipStream_t stream);
+// composed routes (any t the [t] context takes): the steps around lr_intt / lr_ntt of that context on rows of [batch][N] words
+// row[indexMatrix[i]] = values[i] mod t (the residue in [0, t) of a negative value), zero from n_values on
+hipError_t launch_bfv_slot_scatter(const EncoderTables &tab, const void *values, long long n_values, int is_signed, u64 *row, int batch, hipStream_t stream);
+// out[b][i][j] = MRed(row[b][j], delta_mont[i], q_i): encodePlaintext's loop (bfv/encoder.go:127-136)
+hipError_t launch_bfv_lift(const u64 *row, int n, u64 *out, long long out_stride, int limbs, const LimbParams *lp, const u64 *delta_mont, int batch, hipStream_t stream);
+// values[b][i] = row[b][indexMatrix[i]], minus t above t >> 1 for the signed form (bfv/encoder.go:148-150, 170-178)
+hipError_t launch_bfv_slot_gather(const EncoderTables &tab, const u64 *row, void *values, int is_signed, int batch, hipStream_t stream);
 
 // ---- basis extension (lr_bext.hip) ----
 struct ExtTables {        // device pointers; modupParams of ring_basis_extension.go:19-37

@@ -330,4 +330,44 @@ bool build_simple_scaler(u64 t, const std::vector<u64> &moduli, HostSimpleScaler
     return true;
 }
 
+std::vector<u64> build_lift_params(const HostContext &ctx, u64 t) {
+    // Q as little-endian words, then delta = floor(Q / t) by schoolbook division from the top word down (big.Int Quo, bfv/utils.go:11)
+    std::vector<u64> big(1, 1);
+    for (u64 m : ctx.q) {
+        u64 carry = 0;
+        for (size_t i = 0; i < big.size(); ++i) {
+            const u128 p = (u128)big[i] * m + carry;
+            big[i] = (u64)p;
+            carry = (u64)(p >> 64);
+        }
+        if (carry) big.push_back(carry);
+    }
+    u64 rem = 0;
+    for (size_t i = big.size(); i-- > 0;) {
+        const u128 cur = ((u128)rem << 64) | big[i];
+        big[i] = (u64)(cur / t);
+        rem = (u64)(cur % t);
+    }
+    std::vector<u64> r(ctx.L());
+    for (int k = 0; k < ctx.L(); ++k) {
+        const u64 q = ctx.q[k];
+        u64 d = 0;
+        for (size_t i = big.size(); i-- > 0;) d = (u64)((((u128)d << 64) | big[i]) % q);       // :18
+        r[k] = mform(d, q, ctx.bred[k].hi, ctx.bred[k].lo);                                      // :19
+    }
+    return r;
+}
+
+std::vector<u64> build_index_matrix(u64 N, unsigned logN) {
+    std::vector<u64> index(N);
+    const u64 row = N >> 1, m = N << 1;
+    u64 pos = 1;
+    for (u64 i = 0; i < row; ++i) {
+        index[i] = bit_reverse((pos - 1) >> 1, logN);
+        index[i | row] = bit_reverse((m - pos - 1) >> 1, logN);
+        pos = (pos * 5) & (m - 1);                                   // GaloisGen = 5
+    }
+    return index;
+}
+
 }  // namespace lr

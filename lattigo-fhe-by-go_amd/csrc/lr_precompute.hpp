@@ -65,4 +65,9 @@ struct HostSimpleScaler {
 // returns false when t == 0 (the reference divides by zero in BRedParams)
 bool build_simple_scaler(u64 t, const std::vector<u64> &moduli, HostSimpleScaler &out);
 
+// bfv.GenLiftParams(context, t), bfv/utils.go:9-23: MForm(floor(Q / t) mod q_i) for every modulus of the context; t != 0
+std::vector<u64> build_lift_params(const HostContext &ctx, u64 t);
+// bfv.NewEncoder's indexMatrix, bfv/encoder.go:36-58: slot i of a plaintext is coefficient index[i] of its NTT-domain image
+std::vector<u64> build_index_matrix(u64 N, unsigned logN);
+
 }  // namespace lr

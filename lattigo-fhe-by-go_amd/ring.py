@@ -764,6 +764,84 @@ class BfvPlan:
         return CkksPlan(self.contextQ, contextP, max_batch)
 
 
+class BfvEncoder:
+    """bfv.Encoder (bfv/encoder.go:10-182) for a batch of plaintexts on the device (lr_bfv_encoder): what bfv.NewEncoder builds --
+    contextT = (N, [t]), indexMatrix, deltaMont, the SimpleScaler, the one-limb pool -- for up to max_batch plaintexts per call.
+    Slots are numpy arrays [batch, n] (or [n] for one plaintext); plaintexts are Poly over contextQ in the coefficient domain."""
+
+    def __init__(self, contextQ, t, max_batch=1, options=None):
+        self.contextQ, self.t, self.max_batch = contextQ, int(t), int(max_batch)
+        h = C.c_void_p()
+        if options is None:
+            check(lib().lr_bfv_encoder_create(contextQ.h, self.t, max_batch, C.byref(h)))
+        else:
+            check(lib().lr_bfv_encoder_create_ex(contextQ.h, self.t, max_batch, C.byref(options), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().lr_bfv_encoder_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def tables(self):
+        """(indexMatrix[N], deltaMont[|Q|]) as computed on the host by NewEncoder / GenLiftParams"""
+        index = np.zeros(self.contextQ.N, dtype=np.uint64)
+        delta = np.zeros(len(self.contextQ.Modulus), dtype=np.uint64)
+        check(lib().lr_bfv_encoder_tables(self.h, index.ctypes.data_as(nat.u64p), delta.ctypes.data_as(nat.u64p)))
+        return index, delta
+
+    def fused(self):
+        """True when the handle runs the fused kernels, False on the composed route (lr_bfv_encoder_route)"""
+        f = C.c_int(0)
+        check(lib().lr_bfv_encoder_route(self.h, C.byref(f)))
+        return bool(f.value)
+
+    def NewPlaintext(self, batch=1):
+        return self.contextQ.NewPoly(batch)
+
+    def _encode(self, fn, dtype, coeffs, plaintext):
+        a = np.ascontiguousarray(coeffs, dtype=dtype)
+        if a.ndim == 1:
+            a = a[None]
+        if a.ndim != 2:
+            raise LatticeRingError(3, "expected slots of shape [batch, n], got %s" % (a.shape,))      # LR_ERR_SHAPE
+        check(fn(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0], plaintext.h))
+        return plaintext
+
+    def EncodeUint(self, coeffs, plaintext):  # bfv/encoder.go:71
+        return self._encode(lib().lr_bfv_encode_uint, np.uint64, coeffs, plaintext)
+
+    def EncodeInt(self, coeffs, plaintext):  # :95
+        return self._encode(lib().lr_bfv_encode_int, np.int64, coeffs, plaintext)
+
+    def _decode(self, fn, dtype, plaintext):
+        out = np.empty((plaintext.batch, self.contextQ.N), dtype=dtype)
+        check(fn(self.h, plaintext.h, plaintext.batch, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def DecodeUint(self, plaintext):  # :140
+        return self._decode(lib().lr_bfv_decode_uint, np.uint64, plaintext)
+
+    def DecodeInt(self, plaintext):  # :158
+        return self._decode(lib().lr_bfv_decode_int, np.int64, plaintext)
+
+    def EncodeDevice(self, device_ptr, n_values, batch, signed, plaintext):
+        """slots already on the device, [batch][n_values] uint64 / int64 (e.g. a torch tensor's data_ptr()); stream-ordered"""
+        check(lib().lr_bfv_encode_device(self.h, C.c_void_p(device_ptr), n_values, batch, 1 if signed else 0, plaintext.h))
+        return plaintext
+
+    def DecodeDevice(self, plaintext, signed, device_ptr):
+        """the slots to device memory of [batch][N] words; stream-ordered, no synchronisation"""
+        check(lib().lr_bfv_decode_device(self.h, plaintext.h, plaintext.batch, 1 if signed else 0, C.c_void_p(device_ptr)))
+
+
+def NewBfvEncoder(contextQ, t, max_batch=1, options=None):  # bfv.NewEncoder, bfv/encoder.go:28
+    return BfvEncoder(contextQ, t, max_batch, options)
+
+
 class BfvBatcher:
     """Merges the Mul and Relinearize calls of concurrent BFV evaluators -- the reference's own pooled workload: every task of
     examples/dbfv/psi/psi.go:215-233 calls evaluator.Mul and evaluator.Relinearize on one ciphertext pair -- into batched launches
