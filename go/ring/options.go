@@ -8,7 +8,7 @@ import "C"
 // A nil *Options anywhere means the defaults.  The LR_* environment variables are a test-only override of the same fields.
 type Options struct{ c C.lr_options }
 
-// DefaultOptions, when set, is what NewContextWithParams, NewCkksPlan, NewBfvPlan and NewBfvEncoder create their handles with.
+// DefaultOptions, when set, is what NewContextWithParams, NewCkksPlan, NewBfvPlan, NewBfvEncoder and NewCkksEncoder create their handles with.
 var DefaultOptions *Options
 
 func NewOptions() *Options {
@@ -88,6 +88,8 @@ func (o *Options) Set(field string, value int64) *Options {
 		o.c.bfv_gather_below = C.int64_t(value)
 	case "bfv_encoder_unfused":
 		o.c.bfv_encoder_unfused = C.int32_t(value)
+	case "ckks_encoder_tiled":
+		o.c.ckks_encoder_tiled = C.int32_t(value)
 	default:
 		panic("lr_options has no field " + field)
 	}

@@ -119,6 +119,8 @@ typedef struct lr_options {
     int64_t bfv_gather_below;       /* gather while the joint transform has fewer workgroups than this (1536)                         */
     /* --- bfv Encoder (lr_bfv_encoder) */
     int32_t bfv_encoder_unfused;    /* scatter / InvNTT / lift and scale / NTT / gather as separate launches where the fused kernels would run */
+    /* --- ckks Encoder (lr_ckks_encoder) */
+    int32_t ckks_encoder_tiled;     /* the tiled route (streaming stages + LDS tiles) where the fused kernels would run (slots <= 2^13) */
 } lr_options;
 /* fills *opt with the defaults (struct_size = sizeof(lr_options) of THIS library, version = LR_OPTIONS_VERSION) */
 int lr_options_init(lr_options *opt);
@@ -531,6 +533,42 @@ int lr_bfv_decode_int(lr_bfv_encoder *enc, const lr_poly *pt, int batch, int64_t
 /* the same on slots in device memory ([batch][n_values] / [batch][N] words, uint64 or, with is_signed, int64): stream-ordered, no host copy */
 int lr_bfv_encode_device(lr_bfv_encoder *enc, const void *device_values, size_t n_values, int batch, int is_signed, lr_poly *pt);
 int lr_bfv_decode_device(lr_bfv_encoder *enc, const lr_poly *pt, int batch, int is_signed, void *device_values);
+
+/* ckks.Encoder (ckks/encoder.go:10-226) for a batch of plaintexts, device-resident, bit for bit the reference compiled for amd64 (no
+ * multiply-add fused, a complex product is (ac - bd, ad + bc)).  lr_ckks_encoder owns what ckks.NewEncoder builds (:31-69): rotGroup
+ * (5^j mod m for j < m / 4, m = 2 N; the upper half of its m / 2 entries stays zero as in the reference) and the root table
+ * roots[0 .. m] -- the caller's (cos, sin) pairs, 2 (m + 1) doubles, so that a Go caller passes the table Go's math.Cos / math.Sin gave
+ * it; NULL = filled with the host libm from the reference's expression 2 * 3.141592653589793 * i / m, roots[m] = roots[0] -- plus the
+ * per-level CRT tables of Decode, a pool of max_batch polys and a pinned staging buffer.  max_batch outside 1 .. 65535 is LR_ERR_ARG, and
+ * so is a Q of more than 2048 bits (32 words in the decoder's multi-word CRT).
+ * Two routes, the same bits: slots <= 2^13 run one workgroup per plaintext with the special FFT in LDS (Encode's scale-up in the same
+ * kernel from batch 256 on, as a grid-wide kernel of its own below); larger slot counts, and every
+ * slot count with lr_options::ckks_encoder_tiled, run the wide stages as streaming kernels and the others in LDS tiles.
+ * values = [batch][slots] complex128 as (re, im) pairs; slots a power of two in 1 .. N / 2 (else LR_ERR_ARG: the reference's own check
+ * at :84 is vacuous); scale finite and positive (else LR_ERR_ARG).  pt = a poly of ctxQ in the NTT domain with at least level + 1 limbs
+ * and the given batch (what lr_ckks_encrypt_pk takes and lr_ckks_decrypt returns); limbs above level are not touched.  batch != the
+ * poly's or > max_batch, too few limbs or a level outside 0 .. |Q| - 1: LR_ERR_SHAPE; a poly of another context: LR_ERR_ARG.
+ * Encode (:78-116): invfft, scatter with gap = (N / 2) / slots, scaleUpVecExact (ckks/utils.go:51-98), NTTLvl(level).  Outside the
+ * reference's defined domain the device does this: a coefficient x with scale x == 2^64 encodes as 0; a negative x with
+ * |scale x| + 0.5 >= 2^64 as q_j minus the low 64 bits of the truncated integer, reduced; NaN and +-Inf coefficients as 0 (q_j for -Inf).
+ * Decode (:119-168): InvNTTLvl(level), CRT over limbs 0 .. level, centring at Q_level >> 1, the exact integer to double as
+ * big.Float.SetInt(..).Float64() (nearest-even, +-Inf from 2^1024), an IEEE division by scale, fft.
+ * The work is ordered on ctxQ's stream.  The host-value calls stage through the pinned buffer: Encode is asynchronous and the
+ * caller's array is free on return; Decode synchronises. */
+typedef struct lr_ckks_encoder lr_ckks_encoder;
+int lr_ckks_encoder_create(lr_context *ctxQ, int max_batch, const double *roots, lr_ckks_encoder **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_ckks_encoder_create_ex(lr_context *ctxQ, int max_batch, const double *roots, const lr_options *opt, lr_ckks_encoder **out);
+int lr_ckks_encoder_destroy(lr_ckks_encoder *enc);
+/* host copies of rotGroup[m / 2] and roots[2 (m + 1)], for parity tests */
+int lr_ckks_encoder_tables(const lr_ckks_encoder *enc, uint64_t *rot_group, double *roots);
+/* diagnostics: *fused = 1 when a call with this slot count runs the fused kernels, 0 on the tiled route */
+int lr_ckks_encoder_route(const lr_ckks_encoder *enc, int slots, int *fused);
+int lr_ckks_encode(lr_ckks_encoder *enc, const double *values, int slots, int level, double scale, int batch, lr_poly *pt);
+int lr_ckks_decode(lr_ckks_encoder *enc, const lr_poly *pt, int slots, int level, double scale, int batch, double *values);
+/* the same on slot values in device memory ([batch][slots] complex128): stream-ordered, no host copy, no synchronisation */
+int lr_ckks_encode_device(lr_ckks_encoder *enc, const void *device_values, int slots, int level, double scale, int batch, lr_poly *pt);
+int lr_ckks_decode_device(lr_ckks_encoder *enc, const lr_poly *pt, int slots, int level, double scale, int batch, void *device_values);
 
 /* ------------------------------------------------------------------ multi-device ------ */
 /* a batch of independent ciphertexts shards across the GPUs of a node by contiguous blocks (replicated contexts, tables

@@ -5,6 +5,7 @@
 // order and meaning follow the reference (github.com/ldsec/lattigo/ring v1.3.1); where Go panics, these
 // throw ring::Error.  Header-only; link with -llattigo_ring_hip.
 #pragma once
+#include <complex>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -221,6 +222,34 @@ class BfvEncoder {
   private:
     uint64_t N_;
     lr_bfv_encoder *h_ = nullptr;
+};
+
+// ckks.Encoder (ckks/encoder.go:10-226) for batches of plaintexts; slot values are [batch][slots] host arrays, plaintexts Polys over
+// contextQ in the NTT domain; roots = the reference's table roots[0 .. 2N] (empty: the library's own)
+class CkksEncoder {
+  public:
+    CkksEncoder(const Context *contextQ, int max_batch = 1, const std::vector<std::complex<double>> &roots = {}, const lr_options *options = nullptr) {   // NewEncoder :31
+        check(lr_ckks_encoder_create_ex(contextQ->handle(), max_batch, roots.empty() ? nullptr : reinterpret_cast<const double *>(roots.data()), options, &h_));
+    }
+    ~CkksEncoder() { lr_ckks_encoder_destroy(h_); }
+    CkksEncoder(const CkksEncoder &) = delete;
+    CkksEncoder &operator=(const CkksEncoder &) = delete;
+    void Encode(Poly *plaintext, const std::vector<std::complex<double>> &values, int slots, int level, double scale) {                              // :78
+        check(lr_ckks_encode(h_, reinterpret_cast<const double *>(values.data()), slots, level, scale, (int)(values.size() / (size_t)slots), plaintext->handle()));
+    }
+    std::vector<std::complex<double>> Decode(const Poly *plaintext, int slots, int level, double scale, int batch) {                                 // :119
+        std::vector<std::complex<double>> res((size_t)batch * (size_t)slots);
+        check(lr_ckks_decode(h_, plaintext->handle(), slots, level, scale, batch, reinterpret_cast<double *>(res.data())));
+        return res;
+    }
+    bool Fused(int slots) const {
+        int f = 0;
+        check(lr_ckks_encoder_route(h_, slots, &f));
+        return f != 0;
+    }
+
+  private:
+    lr_ckks_encoder *h_ = nullptr;
 };
 
 }  // namespace ring

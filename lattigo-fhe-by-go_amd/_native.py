@@ -24,7 +24,7 @@ class Options(C.Structure):
         "no_asm", "no_fp", "ntt_mode", "asm_variant", "asm14_1024", "no_wide14_small", "wide14_max_items", "ntt_split15", "split15_max_workgroups",
         "no_invfuse", "no_grid_padding", "ntt_stagger", "ntt_persist", "ntt_timeline", "no_epilogue", "no_int_epilogue", "rescale_unfused",
         "rescale_unpaired", "pair_max_workgroups", "ext_narrow", "ext_ieee_div", "no_ext_chunks", "no_staging", "no_exttop", "no_invtop",
-        "no_ext_group", "keymac_narrow", "no_pair", "no_fork", "fork_below_workgroups", "bfv_no_ext_epilogue", "bfv_no_gather")] + [("bfv_gather_below", C.c_int64), ("bfv_encoder_unfused", C.c_int32)]
+        "no_ext_group", "keymac_narrow", "no_pair", "no_fork", "fork_below_workgroups", "bfv_no_ext_epilogue", "bfv_no_gather")] + [("bfv_gather_below", C.c_int64), ("bfv_encoder_unfused", C.c_int32), ("ckks_encoder_tiled", C.c_int32)]
 
     def __init__(self, **fields):
         super().__init__()
@@ -152,6 +152,15 @@ SYMBOLS = {
     "lr_bfv_decode_int": [vp, vp, i32, vp],
     "lr_bfv_encode_device": [vp, vp, C.c_size_t, i32, i32, vp],
     "lr_bfv_decode_device": [vp, vp, i32, i32, vp],
+    "lr_ckks_encoder_create": [vp, i32, vp, C.POINTER(vp)],
+    "lr_ckks_encoder_create_ex": [vp, i32, vp, vp, C.POINTER(vp)],
+    "lr_ckks_encoder_destroy": [vp],
+    "lr_ckks_encoder_tables": [vp, u64p, vp],
+    "lr_ckks_encoder_route": [vp, i32, C.POINTER(i32)],
+    "lr_ckks_encode": [vp, vp, i32, i32, C.c_double, i32, vp],
+    "lr_ckks_decode": [vp, vp, i32, i32, C.c_double, i32, vp],
+    "lr_ckks_encode_device": [vp, vp, i32, i32, C.c_double, i32, vp],
+    "lr_ckks_decode_device": [vp, vp, i32, i32, C.c_double, i32, vp],
     "lr_poly_copy_peer": [vp, vp, i32, vp, vp, i32, i32],
     "lr_context_wait_peer_copies": [vp],
     "lr_gather_blocks": [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32],

@@ -72,6 +72,7 @@ void lr::Options::apply_env() {
     flag("LR_BFV_NO_GATHER", bfv_no_gather);
     if (const char *gb = std::getenv("LR_BFV_GATHER_BELOW")) bfv_gather_below = std::atoll(gb);
     flag("LR_BFV_ENCODER_UNFUSED", bfv_encoder_unfused);
+    flag("LR_CKKS_ENCODER_TILED", ckks_encoder_tiled);
     num("LR_NTT_SPLIT15_BELOW", split15_max_workgroups);
     num("LR_FORK_BELOW", fork_below_workgroups);
 }
@@ -122,6 +123,7 @@ int options_from_public(const lr_options *pub, Options *out) {
         o.bfv_no_gather = p.bfv_no_gather != 0;
         if (p.bfv_gather_below > 0) o.bfv_gather_below = p.bfv_gather_below;
         o.bfv_encoder_unfused = p.bfv_encoder_unfused != 0;
+        o.ckks_encoder_tiled = p.ckks_encoder_tiled != 0;
     }
     o.apply_env();
 #ifndef LR_BUILD_DIAG
@@ -145,6 +147,7 @@ void options_to_public(const Options &o, lr_options *p) {
     p->no_ext_group = o.no_ext_group; p->keymac_narrow = o.keymac_narrow; p->no_pair = o.no_pair; p->no_fork = o.no_fork;
     p->fork_below_workgroups = o.fork_below_workgroups; p->bfv_no_ext_epilogue = o.bfv_no_ext_epilogue; p->bfv_no_gather = o.bfv_no_gather;
     p->bfv_gather_below = o.bfv_gather_below; p->bfv_encoder_unfused = o.bfv_encoder_unfused;
+    p->ckks_encoder_tiled = o.ckks_encoder_tiled;
 }
 
 }  // namespace lr_host

@@ -64,6 +64,7 @@ struct Options {
     int fork_below_workgroups = 256;    // LR_FORK_BELOW: a lone plan forks a launch below this many workgroups
     long long bfv_gather_below = 1536;  // LR_BFV_GATHER_BELOW
     bool bfv_encoder_unfused = false;   // LR_BFV_ENCODER_UNFUSED: the encoder's composed route where the fused kernels would run
+    bool ckks_encoder_tiled = false;    // LR_CKKS_ENCODER_TILED: the CKKS encoder's tiled route where the fused kernels would run
     void apply_env();              // the test-only override: the ONE place that reads LR_* variables
     static Options from_env() {    // defaults + the override: what the plain *_create entry points use
         Options o;
@@ -381,6 +382,57 @@ hipError_t launch_bfv_slot_scatter(const EncoderTables &tab, const void *values,
 hipError_t launch_bfv_lift(const u64 *row, int n, u64 *out, long long out_stride, int limbs, const LimbParams *lp, const u64 *delta_mont, int batch, hipStream_t stream);
 // values[b][i] = row[b][indexMatrix[i]], minus t above t >> 1 for the signed form (bfv/encoder.go:148-150, 170-178)
 hipError_t launch_bfv_slot_gather(const EncoderTables &tab, const u64 *row, void *values, int is_signed, int batch, hipStream_t stream);
+
+// ---- ckks.Encoder (lr_ckks_encode.hip): Encode / Decode of ckks/encoder.go for a batch of plaintexts ----
+struct Cplx { double re, im; };                 // a complex128 as Go lays it out
+constexpr int kCkksFusedMaxLogSlots = 13;       // the fused kernels hold 16 * slots bytes in one CU's LDS: 128 KiB of the 160
+constexpr int kCkksOneKernelBatch = 256;        // fused Encode as ONE kernel from this batch on: a workgroup per CU of the MI355X (below)
+constexpr int kCkksTileMaxLog = 11;             // the tiled route's LDS tile, at most 2^11 slots (32 KiB)
+constexpr int kCkksCrtMaxWords = 32;            // 64-bit words of the largest Q the decoder's CRT takes (2048 bits)
+// NewEncoder's tables (ckks/encoder.go:37-53): roots[0 .. m] with m = 2 N, rotGroup[j] = 5^j mod m for j < N / 2
+struct CkksEncTables {
+    const Cplx *roots;     // [2 N + 1]
+    const u32 *rot;        // [N / 2]
+    int n, logn;
+};
+// scaleUpVecExact's target (ckks/utils.go:51-98): limbs 0 .. limbs - 1 of a plaintext poly, coefficient domain
+struct CkksScaleUp {
+    u64 *out;
+    long long out_stride;
+    int limbs;
+    const LimbParams *lp;  // of contextQ
+    double scale;
+};
+// the tile of the tiled route for 2^logslots slots: a quarter of the slots, so that streaming stages run at every size, up to the LDS tile
+inline int ckks_tile_log(int logslots) { return logslots < 2 ? 0 : (logslots - 2 < kCkksTileMaxLog ? logslots - 2 : kCkksTileMaxLog); }
+// fused Encode, one workgroup per plaintext: values [batch][slots] -> invfft in LDS -> scale-up into the limbs; slots <= 2^13.  A workgroup
+// writes all (level + 1) N words of its plaintext, so the host uses it once the batch fills the chip (kCkksOneKernelBatch); a smaller batch
+// runs invfft in LDS through launch_ckks_dif_tile with the whole slot vector as the tile, then launch_ckks_scale_up over the whole grid
+hipError_t launch_ckks_encode_fused(const CkksEncTables &tab, const Cplx *values, int logslots, const CkksScaleUp &S, int batch, hipStream_t stream);
+// tiled Encode: the stage len = 2^loglen of invfftlazy (:170-190) over [batch][slots] in global memory (src == dst allowed) ...
+hipError_t launch_ckks_dif_stage(const CkksEncTables &tab, const Cplx *src, Cplx *dst, int logslots, int loglen, int batch, hipStream_t stream);
+// ... the stages len = 2^logtile .. 2 in LDS, one tile per workgroup ...
+hipError_t launch_ckks_dif_tile(const CkksEncTables &tab, const Cplx *src, Cplx *dst, int logslots, int logtile, int batch, hipStream_t stream);
+// ... and the bit reversal, the division by slots and the scale-up from the stages' output
+hipError_t launch_ckks_scale_up(const CkksEncTables &tab, const Cplx *src, int logslots, const CkksScaleUp &S, int batch, hipStream_t stream);
+// Decode's coefficients (:122-152): CRT of limbs 0 .. limbs - 1 at the used coefficients, centred, to double exactly as
+// big.Float.SetInt(..).Float64() rounds, divided by scale; dbuf = [batch][2 slots] (real parts, then imaginary parts)
+struct CkksCrt {
+    const u64 *pool;       // [batch][limbs][N], coefficient domain, canonical residues
+    long long pool_stride;
+    int limbs, words;      // words of Q_level
+    const LimbParams *lp;
+    const u64 *qhat;       // [limbs][qhat_stride]: Q_level / q_i, little-endian words
+    long long qhat_stride;
+    const u64 *inv;        // [limbs]: (Q_level / q_i)^-1 mod q_i
+    const u64 *Q, *Qhalf;  // [words]: Q_level and Q_level >> 1
+    double scale;
+};
+hipError_t launch_ckks_crt_to_double(const CkksEncTables &tab, const CkksCrt &P, int logslots, double *dbuf, int batch, hipStream_t stream);
+// fft (:204-226): the bit reversal folded into the load and the stages len = 2 .. 2^logtile in LDS; logtile == logslots is the fused Decode
+hipError_t launch_ckks_dit_tile(const CkksEncTables &tab, const double *dbuf, Cplx *dst, int logslots, int logtile, int batch, hipStream_t stream);
+// the stage len = 2^loglen over [batch][slots] in global memory (src == dst allowed)
+hipError_t launch_ckks_dit_stage(const CkksEncTables &tab, const Cplx *src, Cplx *dst, int logslots, int loglen, int batch, hipStream_t stream);
 
 // ---- basis extension (lr_bext.hip) ----
 struct ExtTables {        // device pointers; modupParams of ring_basis_extension.go:19-37

@@ -330,18 +330,31 @@ bool build_simple_scaler(u64 t, const std::vector<u64> &moduli, HostSimpleScaler
     return true;
 }
 
+namespace {
+
+// little-endian multi-word integers: big *= m (big.Int Mul) and big mod q (big.Int Mod)
+void words_mul(std::vector<u64> &big, u64 m) {
+    u64 carry = 0;
+    for (size_t i = 0; i < big.size(); ++i) {
+        const u128 p = (u128)big[i] * m + carry;
+        big[i] = (u64)p;
+        carry = (u64)(p >> 64);
+    }
+    if (carry) big.push_back(carry);
+}
+
+u64 words_mod(const std::vector<u64> &big, u64 q) {
+    u64 d = 0;
+    for (size_t i = big.size(); i-- > 0;) d = (u64)((((u128)d << 64) | big[i]) % q);
+    return d;
+}
+
+}  // namespace
+
 std::vector<u64> build_lift_params(const HostContext &ctx, u64 t) {
     // Q as little-endian words, then delta = floor(Q / t) by schoolbook division from the top word down (big.Int Quo, bfv/utils.go:11)
     std::vector<u64> big(1, 1);
-    for (u64 m : ctx.q) {
-        u64 carry = 0;
-        for (size_t i = 0; i < big.size(); ++i) {
-            const u128 p = (u128)big[i] * m + carry;
-            big[i] = (u64)p;
-            carry = (u64)(p >> 64);
-        }
-        if (carry) big.push_back(carry);
-    }
+    for (u64 m : ctx.q) words_mul(big, m);
     u64 rem = 0;
     for (size_t i = big.size(); i-- > 0;) {
         const u128 cur = ((u128)rem << 64) | big[i];
@@ -351,11 +364,41 @@ std::vector<u64> build_lift_params(const HostContext &ctx, u64 t) {
     std::vector<u64> r(ctx.L());
     for (int k = 0; k < ctx.L(); ++k) {
         const u64 q = ctx.q[k];
-        u64 d = 0;
-        for (size_t i = big.size(); i-- > 0;) d = (u64)((((u128)d << 64) | big[i]) % q);       // :18
-        r[k] = mform(d, q, ctx.bred[k].hi, ctx.bred[k].lo);                                      // :19
+        r[k] = mform(words_mod(big, q), q, ctx.bred[k].hi, ctx.bred[k].lo);                      // :18-19
     }
     return r;
+}
+
+bool build_ckks_crt(const HostContext &ctx, int max_words, HostCkksCrt &out) {
+    const int L = ctx.L();
+    std::vector<u64> top(1, 1);
+    for (u64 m : ctx.q) words_mul(top, m);
+    if ((int)top.size() > max_words) return false;
+    out.limbs = L;
+    out.stride = (int)top.size();
+    out.words.assign(L, 0);
+    out.qhat.assign((size_t)L * L * out.stride, 0);
+    out.inv.assign((size_t)L * L, 0);
+    out.Q.assign((size_t)L * out.stride, 0);
+    out.Qhalf.assign((size_t)L * out.stride, 0);
+    std::vector<u64> Q(1, 1);
+    for (int l = 0; l < L; ++l) {
+        words_mul(Q, ctx.q[l]);                                        // bigintChain[l], ckks/utils.go:116-125
+        const int W = (int)Q.size();
+        out.words[l] = W;
+        for (int w = 0; w < W; ++w) {
+            out.Q[(size_t)l * out.stride + w] = Q[w];
+            out.Qhalf[(size_t)l * out.stride + w] = (Q[w] >> 1) | (w + 1 < W ? Q[w + 1] << 63 : 0);
+        }
+        for (int i = 0; i <= l; ++i) {
+            std::vector<u64> hat(1, 1);
+            for (int k = 0; k <= l; ++k)
+                if (k != i) words_mul(hat, ctx.q[k]);
+            std::copy(hat.begin(), hat.end(), out.qhat.begin() + ((size_t)l * L + i) * out.stride);
+            out.inv[(size_t)l * L + i] = mod_exp(words_mod(hat, ctx.q[i]), ctx.q[i] - 2, ctx.q[i]);
+        }
+    }
+    return true;
 }
 
 std::vector<u64> build_index_matrix(u64 N, unsigned logN) {

@@ -70,4 +70,15 @@ std::vector<u64> build_lift_params(const HostContext &ctx, u64 t);
 // bfv.NewEncoder's indexMatrix, bfv/encoder.go:36-58: slot i of a plaintext is coefficient index[i] of its NTT-domain image
 std::vector<u64> build_index_matrix(u64 N, unsigned logN);
 
+// the CRT tables of the CKKS decoder (ckks/encoder.go:122-141), per level l and limb i <= l, as little-endian 64-bit words
+struct HostCkksCrt {
+    int limbs = 0, stride = 0;      // stride = the words of the full Q
+    std::vector<int> words;         // [limbs]: the words of Q_l = q_0 ... q_l
+    std::vector<u64> qhat;          // [limbs][limbs][stride]: Q_l / q_i
+    std::vector<u64> inv;           // [limbs][limbs]: (Q_l / q_i)^-1 mod q_i
+    std::vector<u64> Q, Qhalf;      // [limbs][stride]: Q_l and Q_l >> 1
+};
+// false when the full Q needs more than max_words words
+bool build_ckks_crt(const HostContext &ctx, int max_words, HostCkksCrt &out);
+
 }  // namespace lr

@@ -842,6 +842,77 @@ def NewBfvEncoder(contextQ, t, max_batch=1, options=None):  # bfv.NewEncoder, bf
     return BfvEncoder(contextQ, t, max_batch, options)
 
 
+class CkksEncoder:
+    """ckks.Encoder (ckks/encoder.go:10-226) for a batch of plaintexts on the device (lr_ckks_encoder): rotGroup, the root table, the
+    decoder's CRT tables and a pool for up to max_batch plaintexts per call.  roots = the reference's roots[0 .. m], m = 2 N, as a
+    complex128 array of m + 1 entries (None: the library fills it with the host libm).  Slot values are complex128 arrays
+    [batch, slots] (or [slots] for one plaintext); plaintexts are Poly over contextQ in the NTT domain."""
+
+    def __init__(self, contextQ, max_batch=1, roots=None, options=None):
+        self.contextQ, self.max_batch = contextQ, int(max_batch)
+        rp = None
+        if roots is not None:
+            r = np.ascontiguousarray(roots, dtype=np.complex128)
+            if r.shape != (2 * contextQ.N + 1,):
+                raise LatticeRingError(3, "expected 2 N + 1 roots, got %s" % (r.shape,))                # LR_ERR_SHAPE
+            rp = r.ctypes.data_as(C.c_void_p)
+        h = C.c_void_p()
+        if options is None:
+            check(lib().lr_ckks_encoder_create(contextQ.h, max_batch, rp, C.byref(h)))
+        else:
+            check(lib().lr_ckks_encoder_create_ex(contextQ.h, max_batch, rp, C.byref(options), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().lr_ckks_encoder_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def tables(self):
+        """(rotGroup[m / 2], roots[m + 1] complex128) as NewEncoder holds them"""
+        m = 2 * self.contextQ.N
+        rot = np.zeros(m // 2, dtype=np.uint64)
+        roots = np.zeros(m + 1, dtype=np.complex128)
+        check(lib().lr_ckks_encoder_tables(self.h, rot.ctypes.data_as(nat.u64p), roots.ctypes.data_as(C.c_void_p)))
+        return rot, roots
+
+    def fused(self, slots):
+        """True when a call with this slot count runs the fused kernels, False on the tiled route (lr_ckks_encoder_route)"""
+        f = C.c_int(0)
+        check(lib().lr_ckks_encoder_route(self.h, slots, C.byref(f)))
+        return bool(f.value)
+
+    def Encode(self, plaintext, values, level, scale):  # ckks/encoder.go:78; slots = values.shape[-1]
+        a = np.ascontiguousarray(values, dtype=np.complex128)
+        if a.ndim == 1:
+            a = a[None]
+        if a.ndim != 2:
+            raise LatticeRingError(3, "expected slot values of shape [batch, slots], got %s" % (a.shape,))    # LR_ERR_SHAPE
+        check(lib().lr_ckks_encode(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], level, float(scale), a.shape[0], plaintext.h))
+        return plaintext
+
+    def Decode(self, plaintext, slots, level, scale):  # :119
+        out = np.empty((plaintext.batch, max(int(slots), 0)), dtype=np.complex128)
+        check(lib().lr_ckks_decode(self.h, plaintext.h, slots, level, float(scale), plaintext.batch, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def EncodeDevice(self, plaintext, device_ptr, slots, level, scale, batch):
+        """slot values already on the device, [batch][slots] complex128 (e.g. a torch tensor's data_ptr()); stream-ordered"""
+        check(lib().lr_ckks_encode_device(self.h, C.c_void_p(device_ptr), slots, level, float(scale), batch, plaintext.h))
+        return plaintext
+
+    def DecodeDevice(self, plaintext, slots, level, scale, device_ptr):
+        """the slot values to device memory of [batch][slots] complex128; stream-ordered, no synchronisation"""
+        check(lib().lr_ckks_decode_device(self.h, plaintext.h, slots, level, float(scale), plaintext.batch, C.c_void_p(device_ptr)))
+
+
+def NewCkksEncoder(contextQ, max_batch=1, roots=None, options=None):  # ckks.NewEncoder, ckks/encoder.go:31
+    return CkksEncoder(contextQ, max_batch, roots, options)
+
+
 class BfvBatcher:
     """Merges the Mul and Relinearize calls of concurrent BFV evaluators -- the reference's own pooled workload: every task of
     examples/dbfv/psi/psi.go:215-233 calls evaluator.Mul and evaluator.Relinearize on one ciphertext pair -- into batched launches
