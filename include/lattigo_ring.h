@@ -534,6 +534,55 @@ int lr_bfv_decode_int(lr_bfv_encoder *enc, const lr_poly *pt, int batch, int64_t
 int lr_bfv_encode_device(lr_bfv_encoder *enc, const void *device_values, size_t n_values, int batch, int is_signed, lr_poly *pt);
 int lr_bfv_decode_device(lr_bfv_encoder *enc, const lr_poly *pt, int batch, int is_signed, void *device_values);
 
+/* bfv.Encryptor (bfv/encryptor.go:100-345) for a batch of ciphertexts, device-resident, after the sampling.  lr_bfv_encryptor owns what
+ * newEncryptor builds (:100-119): NewFastBasisExtender(contextQ, contextP), three pool polys over Q||P for max_batch ciphertexts, the
+ * matrixTernaryMontgomery rows of every limb (ring/ring_context.go:119-122) and a pinned staging buffer.  ctxP == NULL is the reference's
+ * "modulus P is empty": only the fast forms work (fast = 0 is LR_ERR_ARG).  max_batch outside 1 .. 65535, N < 8 (a bit plane is N / 8
+ * bytes) and a ctxP on another device or of another N are LR_ERR_ARG.  The work is ordered on ctxQ's stream.
+ * The randomness is the samplers' decisions in compact form, N / 4 + 2 N bytes per public-key ciphertext instead of three polys:
+ *   u_coeff_bits, u_sign_bits  [batch][N / 8]: randomBytesCoeffs / randomBytesSign of sampleTernary at p = 0.5
+ *                              (ring/ternarySampler.go:157-177); coefficient i uses bit i & 7 of byte i >> 3, and
+ *                              index = (coeff & (sign ^ 1)) | ((sign & coeff) << 1) selects {0, MForm(1), MForm(q_j - 1)};
+ *   e0, e1, e                  [batch][N]: per coefficient the Gaussian sampler's magnitude in the low 7 bits and its sign in bit 7; the
+ *                              residue is the reference's (ring/gaussianSampler.go:247): sign 1 -> coeff, sign 0 -> q_j - coeff.
+ * Keys are per-call arguments: polys of ctxQ in NTT + Montgomery form with |Q| + |P| limbs in contextQP's order (fast: |Q| suffice), of
+ * the call's batch or of batch 1.  pt, out_c0, out_c1: over all of Q, coefficient domain, of the call's batch (pt may have batch 1);
+ * out_c0 == out_c1 is LR_ERR_ARG, pt is not an output.  batch < 1, > max_batch or != the polys': LR_ERR_SHAPE; too few limbs:
+ * LR_ERR_SHAPE; a poly of another context: LR_ERR_ARG.
+ * lr_bfv_encrypt_pk = pkEncryptor.encrypt: fast = 0 is :194-216 (u -> NTT over Q||P, the two products with the key, InvNTT, Add of the
+ * sampled polys, ModDownPQ(|Q| - 1), + pt on component 0), fast = 1 is :173-190 over Q alone without the ModDown (the reference leaves
+ * that result in its pool, v1.3.1; here it is the ciphertext).
+ * lr_bfv_encrypt_sk = skEncryptor.encrypt (:306-345) with crp the uniform poly in the NTT domain (over Q||P, fast: over Q), which is read
+ * only: Neg(MulCoeffsMontgomery(crp, sk)), InvNTT of that and of crp, SampleAndAdd on the first, (fast = 0) ModDownPQ of both, + pt.
+ * The host forms stage the bytes through the pinned buffer: the caller's arrays are free on return, the call is asynchronous.  The
+ * _device forms take the same bytes in device memory: stream-ordered, no host copy, no synchronisation.
+ * lr_options::no_epilogue selects the reference's call-by-call shape (the samplers expand into pool polys, then one launch per Context
+ * call); both shapes give the same bits. */
+typedef struct lr_bfv_encryptor lr_bfv_encryptor;
+int lr_bfv_encryptor_create(lr_context *ctxQ, lr_context *ctxP, int max_batch, lr_bfv_encryptor **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_bfv_encryptor_create_ex(lr_context *ctxQ, lr_context *ctxP, int max_batch, const lr_options *opt, lr_bfv_encryptor **out);
+int lr_bfv_encryptor_destroy(lr_bfv_encryptor *enc);
+int lr_bfv_encrypt_pk(lr_bfv_encryptor *enc, int fast, const lr_poly *pk0, const lr_poly *pk1, const uint8_t *u_coeff_bits,
+                      const uint8_t *u_sign_bits, const uint8_t *e0, const uint8_t *e1, const lr_poly *pt, int batch, lr_poly *out_c0,
+                      lr_poly *out_c1);
+int lr_bfv_encrypt_sk(lr_bfv_encryptor *enc, int fast, const lr_poly *sk, const lr_poly *crp, const uint8_t *e, const lr_poly *pt, int batch,
+                      lr_poly *out_c0, lr_poly *out_c1);
+int lr_bfv_encrypt_pk_device(lr_bfv_encryptor *enc, int fast, const lr_poly *pk0, const lr_poly *pk1, const void *u_coeff_bits,
+                             const void *u_sign_bits, const void *e0, const void *e1, const lr_poly *pt, int batch, lr_poly *out_c0,
+                             lr_poly *out_c1);
+int lr_bfv_encrypt_sk_device(lr_bfv_encryptor *enc, int fast, const lr_poly *sk, const lr_poly *crp, const void *e, const lr_poly *pt,
+                             int batch, lr_poly *out_c0, lr_poly *out_c1);
+/* bfv.Decryptor (bfv/decryptor.go:28-75).  lr_bfv_decrypt = decryptor.Decrypt of ct[0 .. degree] (degree >= 0; negative: LR_ERR_ARG):
+ * NTT of every component (components that lie back to back in memory share a launch), Horner at sk with the reference's i & 7 == 7
+ * reduction cadence, InvNTT.  ct[i] and pt_out: over all of Q, coefficient domain, of the given batch -- what lr_bfv_mul writes and
+ * lr_bfv_decode_uint reads; sk in NTT + Montgomery form, its first |Q| limbs are read (a key over Q||P works), batch 1 or the call's.
+ * pt_out may be ct[degree]; the inputs are not modified otherwise.  Refusals as above.  The handle's options are ctxQ's. */
+typedef struct lr_bfv_decryptor lr_bfv_decryptor;
+int lr_bfv_decryptor_create(lr_context *ctxQ, int max_batch, lr_bfv_decryptor **out);
+int lr_bfv_decryptor_destroy(lr_bfv_decryptor *dec);
+int lr_bfv_decrypt(lr_bfv_decryptor *dec, const lr_poly *const *ct, int degree, const lr_poly *sk, lr_poly *pt_out, int batch);
+
 /* ckks.Encoder (ckks/encoder.go:10-226) for a batch of plaintexts, device-resident, bit for bit the reference compiled for amd64 (no
  * multiply-add fused, a complex product is (ac - bd, ad + bc)).  lr_ckks_encoder owns what ckks.NewEncoder builds (:31-69): rotGroup
  * (5^j mod m for j < m / 4, m = 2 N; the upper half of its m / 2 entries stays zero as in the reference) and the root table

@@ -224,6 +224,58 @@ class BfvEncoder {
     lr_bfv_encoder *h_ = nullptr;
 };
 
+// bfv.Encryptor (bfv/encryptor.go:100-345) for batches of ciphertexts, after the sampling: the randomness is the samplers' decisions in
+// compact form -- bit planes of [batch][N / 8] bytes for u, [batch][N] (magnitude | sign << 7) bytes per Gaussian poly.  contextP == nullptr:
+// "modulus P is empty", only the fast forms
+class BfvEncryptor {
+  public:
+    BfvEncryptor(const Context *contextQ, const Context *contextP, int max_batch = 1, const lr_options *options = nullptr) {       // newEncryptor :100
+        check(lr_bfv_encryptor_create_ex(contextQ->handle(), contextP ? contextP->handle() : nullptr, max_batch, options, &h_));
+    }
+    ~BfvEncryptor() { lr_bfv_encryptor_destroy(h_); }
+    BfvEncryptor(const BfvEncryptor &) = delete;
+    BfvEncryptor &operator=(const BfvEncryptor &) = delete;
+    void EncryptPk(const Poly *pk0, const Poly *pk1, const std::vector<uint8_t> &u_coeff_bits, const std::vector<uint8_t> &u_sign_bits,
+                   const std::vector<uint8_t> &e0, const std::vector<uint8_t> &e1, const Poly *plaintext, int batch, Poly *c0, Poly *c1,
+                   bool fast = false) {                                                                                                // :169
+        check(lr_bfv_encrypt_pk(h_, fast ? 1 : 0, pk0->handle(), pk1->handle(), u_coeff_bits.data(), u_sign_bits.data(), e0.data(), e1.data(),
+                                plaintext->handle(), batch, c0->handle(), c1->handle()));
+    }
+    void EncryptSk(const Poly *sk, const Poly *crp, const std::vector<uint8_t> &e, const Poly *plaintext, int batch, Poly *c0, Poly *c1,
+                   bool fast = false) {                                                                                                // :306
+        check(lr_bfv_encrypt_sk(h_, fast ? 1 : 0, sk->handle(), crp->handle(), e.data(), plaintext->handle(), batch, c0->handle(), c1->handle()));
+    }
+    // the same bytes in device memory: stream-ordered, no host copy
+    void EncryptPkDevice(const Poly *pk0, const Poly *pk1, const void *u_coeff_bits, const void *u_sign_bits, const void *e0, const void *e1,
+                         const Poly *plaintext, int batch, Poly *c0, Poly *c1, bool fast = false) {
+        check(lr_bfv_encrypt_pk_device(h_, fast ? 1 : 0, pk0->handle(), pk1->handle(), u_coeff_bits, u_sign_bits, e0, e1, plaintext->handle(), batch,
+                                       c0->handle(), c1->handle()));
+    }
+    void EncryptSkDevice(const Poly *sk, const Poly *crp, const void *e, const Poly *plaintext, int batch, Poly *c0, Poly *c1, bool fast = false) {
+        check(lr_bfv_encrypt_sk_device(h_, fast ? 1 : 0, sk->handle(), crp->handle(), e, plaintext->handle(), batch, c0->handle(), c1->handle()));
+    }
+
+  private:
+    lr_bfv_encryptor *h_ = nullptr;
+};
+
+// bfv.Decryptor (bfv/decryptor.go:28-75): ct = the components of the ciphertext, degree ct.size() - 1; pt_out may be the top component
+class BfvDecryptor {
+  public:
+    BfvDecryptor(const Context *contextQ, int max_batch = 1) { check(lr_bfv_decryptor_create(contextQ->handle(), max_batch, &h_)); }   // NewDecryptor :28
+    ~BfvDecryptor() { lr_bfv_decryptor_destroy(h_); }
+    BfvDecryptor(const BfvDecryptor &) = delete;
+    BfvDecryptor &operator=(const BfvDecryptor &) = delete;
+    void Decrypt(const std::vector<const Poly *> &ct, const Poly *sk, Poly *pt_out, int batch) {                                       // :55
+        std::vector<const lr_poly *> raw;
+        for (const Poly *p : ct) raw.push_back(p->handle());
+        check(lr_bfv_decrypt(h_, raw.data(), (int)ct.size() - 1, sk->handle(), pt_out->handle(), batch));
+    }
+
+  private:
+    lr_bfv_decryptor *h_ = nullptr;
+};
+
 // ckks.Encoder (ckks/encoder.go:10-226) for batches of plaintexts; slot values are [batch][slots] host arrays, plaintexts Polys over
 // contextQ in the NTT domain; roots = the reference's table roots[0 .. 2N] (empty: the library's own)
 class CkksEncoder {

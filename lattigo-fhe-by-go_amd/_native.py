@@ -152,6 +152,16 @@ SYMBOLS = {
     "lr_bfv_decode_int": [vp, vp, i32, vp],
     "lr_bfv_encode_device": [vp, vp, C.c_size_t, i32, i32, vp],
     "lr_bfv_decode_device": [vp, vp, i32, i32, vp],
+    "lr_bfv_encryptor_create": [vp, vp, i32, C.POINTER(vp)],
+    "lr_bfv_encryptor_create_ex": [vp, vp, i32, vp, C.POINTER(vp)],
+    "lr_bfv_encryptor_destroy": [vp],
+    "lr_bfv_encrypt_pk": [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_bfv_encrypt_sk": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
+    "lr_bfv_encrypt_pk_device": [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_bfv_encrypt_sk_device": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
+    "lr_bfv_decryptor_create": [vp, i32, C.POINTER(vp)],
+    "lr_bfv_decryptor_destroy": [vp],
+    "lr_bfv_decrypt": [vp, C.POINTER(vp), i32, vp, vp, i32],
     "lr_ckks_encoder_create": [vp, i32, vp, C.POINTER(vp)],
     "lr_ckks_encoder_create_ex": [vp, i32, vp, vp, C.POINTER(vp)],
     "lr_ckks_encoder_destroy": [vp],

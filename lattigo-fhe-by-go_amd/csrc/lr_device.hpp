@@ -383,6 +383,43 @@ hipError_t launch_bfv_lift(const u64 *row, int n, u64 *out, long long out_stride
 // values[b][i] = row[b][indexMatrix[i]], minus t above t >> 1 for the signed form (bfv/encoder.go:148-150, 170-178)
 hipError_t launch_bfv_slot_gather(const EncoderTables &tab, const u64 *row, void *values, int is_signed, int batch, hipStream_t stream);
 
+// ---- bfv.Encryptor (lr_bfv_encrypt.hip): the samplers' compact decisions expanded on the device, and the sk product ----
+// sampleTernary at p = 0.5 (ring/ternarySampler.go:157-177) from its two bit planes: coefficient i takes bit i & 7 of byte i >> 3 of each
+// plane, index = (coeff & (sign ^ 1)) | ((sign & coeff) << 1) into matrixTernaryMontgomery[limb] = {0, MForm(1), MForm(q - 1)}
+// (ring/ring_context.go:119-122); one pass writes every limb of the launch
+struct TernaryLaunch {
+    const unsigned char *coeff_bits, *sign_bits;   // device [batch][n / 8]
+    u64 *out;
+    long long out_stride;
+    int n;
+    LimbScalars one, minus_one;                    // rows 1 and 2 of the matrix, per limb of the launch
+};
+hipError_t launch_bfv_ternary(const TernaryLaunch &L, int limbs, int batch, hipStream_t stream);
+// the Gaussian samplers' (magnitude, sign) bytes: low 7 bits the magnitude c, bit 7 the sign; the residue is the reference's
+// (ring/gaussianSampler.go:247,271): sign 1 -> c, sign 0 -> q - c (so (0, sign 0) is q).  add = 1: out = CRed(x + residue) (Context.Add,
+// SampleAndAdd), then CRed(. + plus) where a component has a `plus` (the Context.Add of the plaintext that ends encrypt); add = 0: out =
+// residue (KYSampler.Sample into a pool poly).  Up to two components of `batch` polys each in one launch.
+struct NoiseLaunch {
+    const u64 *x[2];
+    u64 *out[2];
+    const unsigned char *e[2];                     // device [batch][n]
+    const u64 *plus[2];                            // nullptr: none
+    long long x_stride[2], out_stride[2], plus_stride[2];
+    int n, add;
+    const LimbParams *lp;
+};
+hipError_t launch_bfv_noise(const NoiseLaunch &L, int comps, int limbs, int batch, hipStream_t stream);
+// out = q - MRed(a, b): Neg(MulCoeffsMontgomery(crp, sk)) of skEncryptor.encrypt (bfv/encryptor.go:314-315, 326-327) in one pass; a zero
+// product gives q, as Context.Neg does
+struct NegMulLaunch {
+    const u64 *a, *b;
+    u64 *out;
+    long long a_stride, b_stride, out_stride;      // between batch polys (0 = broadcast)
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_bfv_negmul(const NegMulLaunch &L, int limbs, int batch, hipStream_t stream);
+
 // ---- ckks.Encoder (lr_ckks_encode.hip): Encode / Decode of ckks/encoder.go for a batch of plaintexts ----
 struct Cplx { double re, im; };                 // a complex128 as Go lays it out
 constexpr int kCkksFusedMaxLogSlots = 13;       // the fused kernels hold 16 * slots bytes in one CU's LDS: 128 KiB of the 160

@@ -842,6 +842,97 @@ def NewBfvEncoder(contextQ, t, max_batch=1, options=None):  # bfv.NewEncoder, bf
     return BfvEncoder(contextQ, t, max_batch, options)
 
 
+class BfvEncryptor:
+    """bfv.Encryptor (bfv/encryptor.go:100-345) for a batch of ciphertexts on the device (lr_bfv_encryptor), after the sampling: the
+    randomness arrives as the samplers' compact decisions.  u_bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each
+    (ring/ternarySampler.go:157-177); e = uint8 [batch, N] per sampled poly, magnitude in the low 7 bits and sign in bit 7
+    (ring/gaussianSampler.go:247).  Keys are Poly of contextQ over Q||P (fast: over Q) in NTT + Montgomery form, batch 1 or the
+    call's; plaintext and ctOut are Poly over Q in the coefficient domain.  contextP None: only the fast forms."""
+
+    def __init__(self, contextQ, contextP, max_batch=1, options=None):
+        self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
+        h = C.c_void_p()
+        hP = None if contextP is None else contextP.h
+        if options is None:
+            check(lib().lr_bfv_encryptor_create(contextQ.h, hP, max_batch, C.byref(h)))
+        else:
+            check(lib().lr_bfv_encryptor_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().lr_bfv_encryptor_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _bytes(self, a, batch, per_poly):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.size != batch * per_poly:
+            raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
+        return a
+
+    def EncryptPk(self, pk, u_bits, e, plaintext, ctOut, fast=False):  # pkEncryptor.encrypt, bfv/encryptor.go:169
+        batch, N = ctOut[0].batch, self.contextQ.N
+        uc, us = self._bytes(u_bits[0], batch, N // 8), self._bytes(u_bits[1], batch, N // 8)
+        e0, e1 = self._bytes(e[0], batch, N), self._bytes(e[1], batch, N)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().lr_bfv_encrypt_pk(self.h, 1 if fast else 0, pk[0].h, pk[1].h, p(uc), p(us), p(e0), p(e1), plaintext.h, batch,
+                                      ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+    def EncryptSk(self, sk, crp, e, plaintext, ctOut, fast=False):  # skEncryptor.encrypt, :306
+        batch = ctOut[0].batch
+        eb = self._bytes(e, batch, self.contextQ.N)
+        check(lib().lr_bfv_encrypt_sk(self.h, 1 if fast else 0, sk.h, crp.h, eb.ctypes.data_as(C.c_void_p), plaintext.h, batch,
+                                      ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+    def EncryptPkDevice(self, pk, u_bits_ptrs, e_ptrs, plaintext, ctOut, fast=False):
+        """the same with the randomness in device memory (pointers, e.g. a torch uint8 tensor's data_ptr()); stream-ordered"""
+        v = C.c_void_p
+        check(lib().lr_bfv_encrypt_pk_device(self.h, 1 if fast else 0, pk[0].h, pk[1].h, v(u_bits_ptrs[0]), v(u_bits_ptrs[1]), v(e_ptrs[0]),
+                                             v(e_ptrs[1]), plaintext.h, ctOut[0].batch, ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+    def EncryptSkDevice(self, sk, crp, e_ptr, plaintext, ctOut, fast=False):
+        check(lib().lr_bfv_encrypt_sk_device(self.h, 1 if fast else 0, sk.h, crp.h, C.c_void_p(e_ptr), plaintext.h, ctOut[0].batch,
+                                             ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+
+class BfvDecryptor:
+    """bfv.Decryptor (bfv/decryptor.go:28-75) for a batch of ciphertexts on the device (lr_bfv_decryptor)."""
+
+    def __init__(self, contextQ, max_batch=1):
+        self.contextQ, self.max_batch = contextQ, int(max_batch)
+        h = C.c_void_p()
+        check(lib().lr_bfv_decryptor_create(contextQ.h, max_batch, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().lr_bfv_decryptor_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def Decrypt(self, ct, sk, ptOut):  # decryptor.Decrypt, bfv/decryptor.go:55; ct = the components, degree = len(ct) - 1
+        arr = (C.c_void_p * max(len(ct), 1))(*[None if p is None else p.h.value for p in ct])
+        check(lib().lr_bfv_decrypt(self.h, arr, len(ct) - 1, sk.h, ptOut.h, ptOut.batch))
+        return ptOut
+
+
+def NewBfvEncryptor(contextQ, contextP, max_batch=1, options=None):  # bfv.NewEncryptorFromPk / FromSk, bfv/encryptor.go:72-98
+    return BfvEncryptor(contextQ, contextP, max_batch, options)
+
+
+def NewBfvDecryptor(contextQ, max_batch=1):  # bfv.NewDecryptor, bfv/decryptor.go:28
+    return BfvDecryptor(contextQ, max_batch)
+
+
 class CkksEncoder:
     """ckks.Encoder (ckks/encoder.go:10-226) for a batch of plaintexts on the device (lr_ckks_encoder): rotGroup, the root table, the
     decoder's CRT tables and a pool for up to max_batch plaintexts per call.  roots = the reference's roots[0 .. m], m = 2 N, as a
