@@ -20,6 +20,11 @@
 namespace lr {
 
 std::atomic<unsigned long long> g_stub_launches{0};
+// what the host admitted the last basis extension and the last key inner product with (tests/cpp/admission_driver.cpp prints them):
+// {lazy_terms, exact_terms, word_barrett, wide_ok, input limbs} of the extension's tables; KeyMacLaunch::wide of the Q part and the P part
+// (per thread: the concurrency drivers launch from many threads at once)
+thread_local int g_stub_last_ext[5] = {-1, -1, -1, -1, -1};
+thread_local int g_stub_last_keymac_wide[2] = {-1, -1};
 namespace {
 thread_local volatile u64 t_sink;          // (per thread: the reads are the point, not the sink)
 inline void rd(const u64 *p) { t_sink = *p; }
@@ -229,12 +234,16 @@ static void keymac_touch(const KeyMacLaunch &L, int limbs, int batch) {
 hipError_t launch_keymac(const KeyMacLaunch &L, int limbs, int batch, hipStream_t) {
     g_stub_launches.fetch_add(1);
     keymac_touch(L, limbs, batch);
+    g_stub_last_keymac_wide[0] = g_stub_last_keymac_wide[1];        // (unpaired: the Q part is launched first, then the P part)
+    g_stub_last_keymac_wide[1] = L.wide;
     return hipSuccess;
 }
 hipError_t launch_keymac_pair(const KeyMacLaunch &A, int limbs_a, const KeyMacLaunch &B, int limbs_b, int batch, hipStream_t) {
     g_stub_launches.fetch_add(1);
     keymac_touch(A, limbs_a, batch);
     keymac_touch(B, limbs_b, batch);
+    g_stub_last_keymac_wide[0] = A.wide;
+    g_stub_last_keymac_wide[1] = B.wide;
     return hipSuccess;
 }
 hipError_t launch_bswap(const u64 *in, u64 *out, size_t words, hipStream_t) {
@@ -265,6 +274,8 @@ hipError_t launch_simple_scale(const ScaleLaunch &L, int batch, hipStream_t) {
     return hipSuccess;
 }
 static void ext_touch(const ExtLaunch &L, int n_in, int batch) {
+    const int seen[5] = {L.t.lazy_terms, L.t.exact_terms, L.t.word_barrett, L.t.wide_ok, n_in};
+    std::memcpy(g_stub_last_ext, seen, sizeof seen);
     rows_r(L.in, L.in_stride, L.in_limb0, 1, n_in, batch, L.n);
     for (int s = 0; s < kExtSegments; ++s) {
         const ExtSegment &g = L.seg[s];

@@ -10,12 +10,16 @@
 //   * every launch-shape option of the plan;
 //   * outputs written over operands and over each other where the entry point allows it (the paired launches' refusal side);
 //   * each entry point as the first call on a fresh plan and then at a larger batch (its pools are allocated, then moved, by that call);
-//   * each entry point's refusals: the code, and that nothing was launched.
+//   * each entry point's refusals: the code, and that nothing was launched;
+//   * the same over the rings given on the command line ("logN |Q| |P| q.. p.." each: the test passes moduli at the limits of the admission
+//     bounds -- Q and P just under 2^61 with one special prime, either side of 2^57, either side of 2^33).
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <deque>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -315,9 +319,19 @@ static void cold(const Ring &r, const lr_options &opt, lr_context *q, lr_context
     }
 }
 
-int main() {
+int main(int argc, char **argv) {
     unsigned long long forks16 = 0, forks_other = 0, grouped = 0;
-    for (const Ring &r : kRings) {
+    std::vector<Ring> rings(kRings, kRings + 3);
+    std::deque<std::vector<uint64_t>> extra;                               // (a deque: the rings keep pointers into its elements)
+    for (int a = 1; a + 2 < argc;) {
+        const int logn = std::atoi(argv[a]), nq = std::atoi(argv[a + 1]), np = std::atoi(argv[a + 2]);
+        CHECK(a + 3 + nq + np <= argc);
+        extra.emplace_back();
+        for (int i = 0; i < nq + np; ++i) extra.back().push_back(std::strtoull(argv[a + 3 + i], nullptr, 10));
+        rings.push_back(Ring{(uint64_t)1 << logn, extra.back().data(), nq, extra.back().data() + nq, np});
+        a += 3 + nq + np;
+    }
+    for (const Ring &r : rings) {
         for (int v = 0; v < kVariants; ++v) {
             lr_options opt;
             OK(lr_options_init(&opt));

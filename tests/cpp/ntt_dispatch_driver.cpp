@@ -14,7 +14,10 @@
 //     the top pass and the plain sub-blocks; the pre-applied top stage comes from the key switch), every level of the rescale;
 //   * once, at N = 2^16: a single-limb launch of 65536 polys, which crosses run_ntt's chunking (65535 / count polys per launch), on memory
 //     that is reserved but only touched at the first and the last word of each row;
-//   * each entry point's refusals: the code, and that nothing was launched.
+//   * each entry point's refusals: the code, and that nothing was launched;
+//   * after all of that, the modulus classes given on the command line ("name q0 q1 q2 q3 q4", any number of them: the test passes the classes
+//     at the limits of the admission bounds -- just under 2^61, either side of 2^57, just above and just below 2^33) on every ring under the
+//     options default, no_asm, no_fp, asm_variant 0 and 1: which kernel each limit set selects, pinned without a device.
 // After every call the driver reads lr_context_last_ntt_kernel; a plain transform's name carries the number of launches of the call ("x2": a
 // streaming top-stage pass beside the sub-block kernels).  One line per (ring, moduli, options) lists the set; the test compares the lines
 // with tests/golden/ntt_dispatch_routes.txt.  Routes the stand-in cannot reach (the GPU suite covers them): the stamped whole-transform
@@ -25,6 +28,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <set>
 #include <string>
 #include <vector>
@@ -92,6 +96,7 @@ static const char *set_option(lr_options *o, int v, int logn) {
         return nullptr;
     case 11: if (logn == 15) { o->ntt_split15 = 1; return "ntt_split15=1"; } return nullptr;
     case 12: if (logn == 15) { o->split15_max_workgroups = 4; return "split15_max_workgroups=4"; } return nullptr;
+    case 13: o->no_fp = 1; return "no_fp";
     default: return nullptr;
     }
 }
@@ -340,43 +345,54 @@ static void chunked(Config &C) {
     CHECK(munmap(mem, bytes) == 0);
 }
 
-int main() {
+// one (ring, moduli, options) configuration: every entry point, then the line of its kernel names
+static void run_config(int logn, const Moduli &m, int v) {
+    lr_options opt;
+    OK(lr_options_init(&opt));
+    const char *name = set_option(&opt, v, logn);
+    if (!name) return;
+    Config C;
+    C.N = (uint64_t)1 << logn;
+    OK(lr_context_create_ex(C.N, m.q, NQ, 0, &opt, &C.q));
+    OK(lr_context_create_ex(C.N, P, NP, 0, &opt, &C.p));
+    OK(lr_bext_create(C.q, C.p, &C.bx));
+    OK(lr_ckks_plan_create_ex(C.q, C.p, 2 * MAXB, &opt, &C.pl));
+    int fwd = -2, inv = -2;
+    OK(lr_context_ntt_variants(C.q, &fwd, &inv));
+    if (v == 0 && m.fwd != -2) CHECK(fwd == m.fwd);
+    if (v == 1) CHECK(fwd == -1 && inv == -1);
+    const int fail_before = g_fail;
+    for (int batch : {1, MAXB}) {
+        transforms(C, batch);
+        rescales(C, batch);
+        moddowns(C, batch);
+        galois(C, batch);
+        key_switch(C, batch);
+    }
+    refusals(C);
+    if (logn == 16 && v == 0 && &m == &kModuli[0]) chunked(C);
+    if (g_fail != fail_before) std::fprintf(stderr, "... at N = 2^%d, moduli %s, %s\n", logn, m.name, name);
+    std::printf("routes N=2^%d moduli=%s %s fwd=%d inv=%d:", logn, m.name, name, fwd, inv);
+    for (const std::string &s : C.names) std::printf(" %s", s.c_str());
+    std::printf("\n");
+    OK(lr_ckks_plan_destroy(C.pl));
+    OK(lr_bext_destroy(C.bx));
+    OK(lr_context_destroy(C.q));
+    OK(lr_context_destroy(C.p));
+}
+
+int main(int argc, char **argv) {
     for (int logn : kLogN)
         for (const Moduli &m : kModuli)
-            for (int v = 0; v < 13; ++v) {
-                lr_options opt;
-                OK(lr_options_init(&opt));
-                const char *name = set_option(&opt, v, logn);
-                if (!name) continue;
-                Config C;
-                C.N = (uint64_t)1 << logn;
-                OK(lr_context_create_ex(C.N, m.q, NQ, 0, &opt, &C.q));
-                OK(lr_context_create_ex(C.N, P, NP, 0, &opt, &C.p));
-                OK(lr_bext_create(C.q, C.p, &C.bx));
-                OK(lr_ckks_plan_create_ex(C.q, C.p, 2 * MAXB, &opt, &C.pl));
-                int fwd = -2, inv = -2;
-                OK(lr_context_ntt_variants(C.q, &fwd, &inv));
-                if (v == 0) CHECK(fwd == m.fwd);
-                if (v == 1) CHECK(fwd == -1 && inv == -1);
-                const int fail_before = g_fail;
-                for (int batch : {1, MAXB}) {
-                    transforms(C, batch);
-                    rescales(C, batch);
-                    moddowns(C, batch);
-                    galois(C, batch);
-                    key_switch(C, batch);
-                }
-                refusals(C);
-                if (logn == 16 && v == 0 && &m == &kModuli[0]) chunked(C);
-                if (g_fail != fail_before) std::fprintf(stderr, "... at N = 2^%d, moduli %s, %s\n", logn, m.name, name);
-                std::printf("routes N=2^%d moduli=%s %s fwd=%d inv=%d:", logn, m.name, name, fwd, inv);
-                for (const std::string &s : C.names) std::printf(" %s", s.c_str());
-                std::printf("\n");
-                OK(lr_ckks_plan_destroy(C.pl));
-                OK(lr_bext_destroy(C.bx));
-                OK(lr_context_destroy(C.q));
-                OK(lr_context_destroy(C.p));
-            }
+            for (int v = 0; v < 13; ++v) run_config(logn, m, v);
+    // the classes of the command line: "name q0 .. q4" each, fwd = -2 (no expectation here: the test compares the printed variants with its own
+    // restatement of the admission predicates)
+    for (int a = 1; a + NQ < argc; a += NQ + 1) {
+        Moduli m{argv[a], {}, -2};
+        for (int i = 0; i < NQ; ++i) m.q[i] = std::strtoull(argv[a + 1 + i], nullptr, 10);
+        for (int logn : kLogN)
+            for (int v : {0, 1, 13, 8, 9}) run_config(logn, m, v);
+    }
     CHECK(hipstub_live_allocations() == 0);
     std::printf("ntt_dispatch: calls %d, refusals %d, failures %d\n", g_calls, g_refusals, g_fail);
     return g_fail ? 1 : 0;

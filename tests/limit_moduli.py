@@ -1,0 +1,471 @@
+"""Moduli and residues at which the library's lazy-range bounds are tight (test infrastructure, no GPU dependency).
+
+Every fast path is admitted by a bound on the modulus size that the host checks once; the kernel then relies on a range argument.
+This module names, for each such bound, a modulus set for which the predicate is only just true and a sibling for which it is only
+just false, and builds a batch of polynomials that drive the lazy accumulations to the top of the range the bound allows:
+
+    below(bits, logn), above(bits, logn)   the NTT-friendly primes next to 2^bits
+    admission_sets(logn)                   {name: AdmissionSet}, one or two per bound
+    stress_polys(moduli, N, domain, oc)    (family names, [families, limbs, N] uint64)
+
+The admission predicates are restated here in Python (each with the source line it mirrors), so that the tests can state which
+route a set must take before they ask the library.
+"""
+import importlib.util
+import os
+from collections import namedtuple
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _params():
+    spec = importlib.util.spec_from_file_location("_limit_moduli_params", os.path.join(ROOT, "lattigo-fhe-by-go_amd", "params.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+params = _params()
+FP_LIMIT = 1 << 46                       # kFpLimit (lr_host.hpp), FP_LIMIT (gen_ntt.py)
+
+
+# ------------------------------------------------------------------------------------------
+# primes
+# ------------------------------------------------------------------------------------------
+def below(bits, logn, count=1):
+    """the largest NTT-friendly prime (= 1 mod 2N) below 2^bits; count > 1: the `count` largest, descending"""
+    step = 2 << logn
+    return _walk((1 << bits) - step + 1, -step, count)
+
+
+def above(bits, logn, count=1):
+    """the smallest NTT-friendly prime above 2^bits; count > 1: the `count` smallest, ascending"""
+    return _walk((1 << bits) + 1, 2 << logn, count)
+
+
+def at_most(x, logn, count=1):
+    """the largest NTT-friendly prime <= x"""
+    step = 2 << logn
+    return _walk(x - (x - 1) % step, -step, count)
+
+
+def more_than(x, logn, count=1):
+    """the smallest NTT-friendly prime > x"""
+    step = 2 << logn
+    return _walk(x - (x - 1) % step + step, step, count)
+
+
+def _walk(p, step, count):
+    out = []
+    while len(out) < count:
+        assert p > 2, "no NTT-friendly prime left in this direction"
+        if params.is_prime(p):
+            out.append(p)
+        p += step
+    return out[0] if count == 1 else out
+
+
+# ------------------------------------------------------------------------------------------
+# the host's admission predicates, restated
+# ------------------------------------------------------------------------------------------
+def ntt_mode(moduli, option=-1):
+    """lr_abi_core.cpp:227-234: lazy-correction cadence of the C++ kernels (| 256 when every modulus is at least 2^32)"""
+    qmax, qmin = max(moduli), min(moduli)
+    if qmax < (1 << 57):
+        mode = 2
+    elif qmin >= (1 << 57):
+        mode = 1 if qmax <= (1 << 60) else 0
+    else:
+        mode = 3
+    if option >= 0 and ((option == 0 and mode == 1) or option == 3):
+        mode = option
+    return mode | (256 if qmin >= (1 << 32) else 0)
+
+
+def asm_variants(moduli, asm_variant=-1, no_fp=False, no_asm=False):
+    """lr_abi_core.cpp:235-250, :357-358: (forward, inverse) variant of the assembly kernels, -1 = none"""
+    if no_asm:
+        return (-1, -1)
+    qmax, qmin = max(moduli), min(moduli)
+    fwd = inv = -1
+    if qmin > (1 << 33):
+        fwd = 2 if qmax < (1 << 57) else 1 if qmax <= (1 << 60) else 0
+        inv = 1 if qmax <= (1 << 60) else 0
+        if asm_variant >= 0:
+            if asm_variant == 0 or (asm_variant == 1 and fwd >= 1):
+                fwd = asm_variant
+            if asm_variant == 0:
+                inv = 0
+    if qmin < FP_LIMIT and qmax < (1 << 57) and not no_fp and asm_variant < 0:
+        if all(q < FP_LIMIT or q > (1 << 33) for q in moduli):
+            fwd = inv = 3
+    return (fwd, inv)
+
+
+def supported(moduli):
+    """lr_abi_core.cpp:216-217: a context refuses a modulus of 2^61 or more"""
+    return all(q >> 61 == 0 for q in moduli)
+
+
+def lazy_terms(P):
+    """lr_host.hpp:274-275"""
+    pmax = max(P)
+    return min(((1 << 64) - pmax) // (5 * pmax), 1 << 20)
+
+
+def exact_terms(P):
+    """lr_host.hpp:274,276"""
+    pmax = max(P)
+    return min(((1 << 64) - pmax) // (2 * pmax), 1 << 20)
+
+
+def wide_ok(Q, ext_narrow=False):
+    """lr_host.hpp:279-282"""
+    return 0 if ext_narrow else min(((1 << 64) - 1) // max(Q), 1 << 20)
+
+
+def word_barrett(P):
+    """lr_host.hpp:284"""
+    return int(all((p >> 32) != 0 and p != (1 << 32) for p in P))
+
+
+def keymac_wide_ok(moduli, beta, keymac_narrow=False):
+    """lr_abi_ckks.cpp:293-298"""
+    return (not keymac_narrow) and max(moduli) * beta < (1 << 64)
+
+
+def ext_kernel(Q, P, n_in, N, fast_div_ok=True, ext_narrow=False):
+    """lr_bext.hip launch_n (:487-517) without a pre-applied top stage: the kernel an extension of n_in limbs of Q to P runs on"""
+    lt, et, wo, wb = lazy_terms(P), exact_terms(P), wide_ok(Q, ext_narrow), word_barrett(P)
+    if N % 2 == 0 and et >= 4 and fast_div_ok:
+        if lt >= max(n_in, 2) and wb:
+            return "ext_sum"
+        if lt >= n_in:
+            return "ext_shoup<0>"
+        if wo >= n_in:
+            return "ext_wide<%d>" % n_in
+        if wo >= 16 and n_in > 16:
+            return "ext_wide<16>"
+        if wo >= 8 and n_in > 8:
+            return "ext_wide<8>"
+        return "ext_shoup<7>" if et >= 8 else "ext_shoup<3>"
+    return "ext"
+
+
+# ------------------------------------------------------------------------------------------
+# admission sets
+# ------------------------------------------------------------------------------------------
+AdmissionSet = namedtuple("AdmissionSet", "name kind moduli P terms bound admitted")
+AdmissionSet.__doc__ = """kind "ntt": `moduli` is the context's list.  kind "ext": an extension of `terms` limbs of `moduli` (Q) to `P`.
+kind "keymac": a key switch over Q = `moduli`, `P`, with beta = `terms` digits.  `bound` names the predicate, `admitted` says on which
+side of it the set lies."""
+
+
+def _terms_edge(divisor_per_term, n, logn):
+    """(largest p with floor((2^64 - p) / (k p)) == n, smallest p with the value n - 1): p <= 2^64 / (k n + 1)"""
+    edge = (1 << 64) // (divisor_per_term * n + 1)
+    return at_most(edge, logn), more_than(edge, logn)
+
+
+def admission_sets(logn):
+    """name -> AdmissionSet.  A sibling pair shares its prefix and ends in the side of the bound it lies on."""
+    sets = {}
+
+    def add(name, kind, moduli, bound, admitted, P=(), terms=0):
+        assert name not in sets
+        assert all(q % (2 << logn) == 1 and params.is_prime(q) for q in list(moduli) + list(P)), name
+        sets[name] = AdmissionSet(name, kind, list(moduli), list(P), terms, bound, admitted)
+
+    # ---- NTT variants (lr_abi_core.cpp:227-249, gen_ntt.py:31-34, lr_ntt.hip:29-34): two limbs of one class each
+    add("ntt_below61", "ntt", below(61, logn, 2), "mode 0: q < 2^61, values up to 8q just under 2^64", True)
+    add("ntt_below60", "ntt", below(60, logn, 2), "mode 1: q <= 2^60", True)
+    add("ntt_above60", "ntt", above(60, logn, 2), "mode 1: q <= 2^60", False)
+    add("ntt_below57", "ntt", below(57, logn, 2), "mode 2: q < 2^57, 4 logN + 1 multiples of q below 2^64", True)
+    add("ntt_above57", "ntt", above(57, logn, 2), "mode 2: q < 2^57; modes 0/1: one-multiply quotient estimates need q >= 2^57", False)
+    add("ntt_below46", "ntt", below(46, logn, 2), "FP64 body: q < 2^46", True)
+    add("ntt_above46", "ntt", above(46, logn, 2), "FP64 body: q < 2^46", False)
+    add("ntt_above33", "ntt", above(33, logn, 2), "assembly kernels: q > 2^33 (32-bit Barrett constant)", True)
+    add("ntt_straddle33", "ntt", [below(33, logn), above(33, logn)], "assembly kernels: q > 2^33 (32-bit Barrett constant)", False)
+    add("ntt_above32", "ntt", above(32, logn, 2), "ntt_mode |= 256: q >= 2^32", True)
+    add("ntt_below32", "ntt", below(32, logn, 2), "ntt_mode |= 256: q >= 2^32", False)
+
+    # ---- basis extension (lr_host.hpp:274-284): n input limbs of Q, P = two primes with pmax on either side of the bound
+    for n in (2, 3, 4):
+        lo, hi = _terms_edge(5, n, logn)                                # lazy_terms == n / == n - 1
+        if hi >> 61:
+            continue
+        Q = below(59, logn, n)
+        assert lazy_terms([lo]) == n and lazy_terms([hi]) == n - 1
+        add("ext_lazy%d_in" % n, "ext", Q, "lazy_terms >= n (sum form)", True, P=[lo, at_most(lo - 1, logn)], terms=n)
+        add("ext_lazy%d_out" % n, "ext", Q, "lazy_terms >= n (sum form)", False, P=[hi, at_most(lo - 1, logn)], terms=n)
+    # exact_terms against the cadence of the per-term kernel: >= 8 reduces every 7th term, else every 3rd.  Nine input limbs, so that
+    # the cadence of 7 reduces once; the per-term kernel is what the ext_narrow option leaves for these sets (lazy_terms 3 < 9, and any
+    # q < 2^61 has wide_ok >= 8, which otherwise selects the 128-bit sums in groups of eight)
+    lo, hi = _terms_edge(2, 8, logn)                                    # exact_terms == 8 / == 7
+    assert exact_terms([lo]) == 8 and exact_terms([hi]) == 7
+    Q9 = below(61, logn, 9)
+    add("ext_exact8_in", "ext", Q9, "exact_terms >= 8 (BRedAdd every 7th term)", True, P=[lo, at_most(lo - 1, logn)], terms=9)
+    add("ext_exact8_out", "ext", Q9, "exact_terms >= 8 (BRedAdd every 7th term)", False, P=[hi, at_most(lo - 1, logn)], terms=9)
+    # wide_ok against the group size: P above 2^60 refuses the sum form for 4 limbs (lazy_terms == 2); n * qmax on either side of 2^64
+    PW = above(60, logn, 2)
+    for n in (4,):
+        edge = ((1 << 64) - 1) // n                                     # wide_ok >= n  <=>  qmax <= (2^64 - 1) / n
+        qin = at_most(min(edge, (1 << 61) - 1), logn)
+        if more_than(edge, logn) >> 61 == 0:
+            qout = more_than(edge, logn)
+            add("ext_wide%d_out" % n, "ext", [qout] + below(59, logn, n - 1), "wide_ok >= n (128-bit sums)", False, P=PW, terms=n)
+        add("ext_wide%d_in" % n, "ext", [qin] + below(59, logn, n - 1), "wide_ok >= n (128-bit sums)", True, P=PW, terms=n)
+    # wide_ok == 8 exactly: eight limbs just under 2^61 are one group, nine are a group of eight and one term
+    add("ext_wide8_in", "ext", below(61, logn, 8), "wide_ok >= n (128-bit sums)", True, P=PW, terms=8)
+    add("ext_wide8_out", "ext", Q9, "wide_ok >= n (128-bit sums)", False, P=PW, terms=9)
+    # word_barrett: every p > 2^32
+    Qs = above(40, logn, 2)
+    add("ext_word_in", "ext", Qs, "word_barrett: every p > 2^32", True, P=above(32, logn, 2), terms=2)
+    add("ext_word_out", "ext", Qs, "word_barrett: every p > 2^32", False, P=[above(32, logn), below(32, logn)], terms=2)
+
+    # ---- key inner product (lr_abi_ckks.cpp:292-298): beta * qmax < 2^64 with one special prime, so beta = |Q|
+    q61 = below(61, logn, 10)
+    add("keymac_beta8_in", "keymac", q61[1:9], "beta * q < 2^64", True, P=q61[:1], terms=8)
+    add("keymac_beta9_out", "keymac", q61[1:10], "beta * q < 2^64", False, P=q61[:1], terms=9)
+    assert keymac_wide_ok(q61, 8) and not keymac_wide_ok(q61, 9)
+    return sets
+
+
+# ------------------------------------------------------------------------------------------
+# the reference's butterfly networks in Python integers (ring/ntt.go:53-86, :89-150), exact residues instead of lazy ones
+# ------------------------------------------------------------------------------------------
+def bitrev(i, bits):
+    r = 0
+    for _ in range(bits):
+        r = (r << 1) | (i & 1)
+        i >>= 1
+    return r
+
+
+def psi_tables(q, N, psi):
+    """nttPsi / nttPsiInv in the plain domain: entry bitrev(j) = psi^j resp. psi^-j (ring_context.go: genNTTParams)"""
+    logn = N.bit_length() - 1
+    fwd, inv = [0] * N, [0] * N
+    ipsi = pow(psi, -1, q)
+    a = b = 1
+    for j in range(N):
+        r = bitrev(j, logn)
+        fwd[r], inv[r] = a, b
+        a, b = a * psi % q, b * ipsi % q
+    return fwd, inv
+
+
+def oracle_psi(oc, limb):
+    """the 2N-th root the oracle's context chose for this limb (plain domain): nttPsi[bitrev(1)] out of Montgomery form"""
+    q = oc.moduli[limb]
+    return int(oc.ntt_psi[limb][oc.N >> 1]) * pow(1 << 64, -1, q) % q
+
+
+def _obj(x):
+    return np.array([int(v) for v in x], dtype=object)
+
+
+def fwd_stages(x, q, tab, first=0, last=None):
+    """stages [first, last) of NTT's loop (stage s: m = 2^s blocks of 2t = N / m slots, twiddle nttPsi[m + i]); canonical residues"""
+    N = len(x)
+    logn = N.bit_length() - 1
+    x = _obj(x) % q
+    for s in range(first, logn if last is None else last):
+        m = 1 << s
+        t = N >> (s + 1)
+        w = np.array(tab[m:2 * m], dtype=object).reshape(m, 1)
+        y = x.reshape(m, 2, t)
+        u, vw = y[:, 0, :], y[:, 1, :] * w % q
+        x = np.stack([(u + vw) % q, (u - vw) % q], axis=1).reshape(N)
+    return x
+
+
+def fwd_unstages(x, q, tab, upto):
+    """the state before stage 0 that stages [0, upto) turn into x"""
+    N = len(x)
+    x = _obj(x) % q
+    half = pow(2, -1, q)
+    for s in range(upto - 1, -1, -1):
+        m = 1 << s
+        t = N >> (s + 1)
+        wi = np.array([pow(w, -1, q) for w in tab[m:2 * m]], dtype=object).reshape(m, 1)
+        y = x.reshape(m, 2, t)
+        a, b = y[:, 0, :], y[:, 1, :]
+        x = np.stack([(a + b) * half % q, (a - b) * half % q * wi % q], axis=1).reshape(N)
+    return x
+
+
+def inv_stages(x, q, tab, first=0, last=None, scale=True):
+    """stages [first, last) of InvNTT's loop (stage s: h = N / 2^(s+1) blocks of 2t = 2^(s+1) slots, twiddle nttPsiInv[h + i]), then N^-1"""
+    N = len(x)
+    logn = N.bit_length() - 1
+    x = _obj(x) % q
+    last = logn if last is None else last
+    for s in range(first, last):
+        h = N >> (s + 1)
+        t = 1 << s
+        w = np.array(tab[h:2 * h], dtype=object).reshape(h, 1)
+        y = x.reshape(h, 2, t)
+        u, v = y[:, 0, :], y[:, 1, :]
+        x = np.stack([(u + v) % q, (u - v) % q * w % q], axis=1).reshape(N)
+    if scale and last == logn:
+        x = x * pow(N, -1, q) % q
+    return x
+
+
+def inv_unstages(x, q, tab, upto):
+    N = len(x)
+    x = _obj(x) % q
+    half = pow(2, -1, q)
+    for s in range(upto - 1, -1, -1):
+        h = N >> (s + 1)
+        t = 1 << s
+        wi = np.array([pow(w, -1, q) for w in tab[h:2 * h]], dtype=object).reshape(h, 1)
+        y = x.reshape(h, 2, t)
+        a, b = y[:, 0, :], y[:, 1, :] * wi % q
+        x = np.stack([(a + b) * half % q, (a - b) * half % q], axis=1).reshape(N)
+    return x
+
+
+def stage_pinned(q, N, tab, stage, inverse=False):
+    """the input for which, on entering `stage`, every upper slot is q - 1 and every product V * w resp. (U - V) * w is q - 1:
+    forward V = -w^-1, inverse V = U + w^-1.  Random residues add about q per lazy step; these add what the bound allows."""
+    if inverse:
+        h, t = N >> (stage + 1), 1 << stage
+        wi = np.array([pow(w, -1, q) for w in tab[h:2 * h]], dtype=object).reshape(h, 1)
+        state = np.stack([np.full((h, t), q - 1, dtype=object), (np.full((h, t), q - 1, dtype=object) + wi) % q], axis=1).reshape(N)
+        return inv_unstages(state, q, tab, stage)
+    m, t = 1 << stage, N >> (stage + 1)
+    wi = np.array([pow(w, -1, q) for w in tab[m:2 * m]], dtype=object).reshape(m, 1)
+    state = np.stack([np.full((m, t), q - 1, dtype=object), (np.zeros((m, t), dtype=object) - wi) % q], axis=1).reshape(N)
+    return fwd_unstages(state, q, tab, stage)
+
+
+# ------------------------------------------------------------------------------------------
+# stress polynomials
+# ------------------------------------------------------------------------------------------
+def harshest(logn):
+    """the families no parametrisation leaves out"""
+    return ("qm1", "top", "stage%d" % (logn - 1))
+
+
+def stress_polys(moduli, N, domain, oc=None, families=None, seed=2024):
+    """(names, [families, limbs, N] uint64).  domain:
+         "ntt"       inputs of the forward transform (any 64-bit value; top = 2^64 - 1), stage-pinned for the forward network;
+         "intt"      inputs of the inverse transform (documented range [0, 4q); top = 4q - 1), stage-pinned for the inverse network;
+         "lazy2q"    coefficient-wise inputs where the reference's callers leave lazy values (top = 2q - 1), no stage-pinned polys;
+         "canonical" canonical residues only.
+    oc: the oracle's context for (N, moduli) -- needed for the spectrum pre-image and the stage-pinned polys (its psi tables).
+    families: keep only these names (all limit moduli and harshest(logn) stay in every caller's choice)."""
+    logn = N.bit_length() - 1
+    L = len(moduli)
+    inverse = domain == "intt"
+    names, polys = [], []
+
+    def put(name, rows):
+        if families is None or name in families:
+            names.append(name)
+            polys.append(np.array([[int(v) for v in r] for r in rows], dtype=np.uint64))
+
+    put("zero", [[0] * N for q in moduli])
+    put("qm1", [[q - 1] * N for q in moduli])
+    put("alt", [[0, q - 1] * (N // 2) for q in moduli])
+    put("first", [[q - 1] + [0] * (N - 1) for q in moduli])
+    put("last", [[0] * (N - 1) + [q - 1] for q in moduli])
+    if oc is not None and (families is None or "spectrum_qm1" in families):
+        full = np.array([[q - 1] * N for q in moduli], dtype=np.uint64)
+        put("spectrum_qm1", oc.ntt(full) if inverse else oc.intt(full))
+    rng = np.random.default_rng(seed)
+    put("uniform", [[int(v) % q for v in rng.integers(0, 1 << 63, N, dtype=np.uint64)] for q in moduli])
+    if domain == "ntt":
+        put("top", [[(1 << 64) - 1] * N for q in moduli])
+    elif domain == "intt":
+        put("top", [[4 * q - 1] * N for q in moduli])
+    elif domain == "lazy2q":
+        put("top", [[2 * q - 1] * N for q in moduli])
+    if oc is not None and domain in ("ntt", "intt"):
+        wanted = [s for s in range(logn) if families is None or "stage%d" % s in families]
+        if wanted:
+            tabs = [psi_tables(q, N, oracle_psi(oc, i))[1 if inverse else 0] for i, q in enumerate(moduli)]
+            for s in wanted:
+                put("stage%d" % s, [stage_pinned(q, N, tabs[i], s, inverse) for i, q in enumerate(moduli)])
+    return names, np.stack(polys).reshape(len(names), L, N)
+
+
+def canon(x, moduli):
+    """[..., limbs, N] uint64 -> residues mod the limb's modulus"""
+    x = np.asarray(x, dtype=np.uint64)
+    out = x.copy()
+    for i, q in enumerate(moduli):
+        out[..., i, :] = x[..., i, :] % np.uint64(q)
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# operand corners of the coefficient-wise family
+# ------------------------------------------------------------------------------------------
+LANE_WIDTH = 4            # the coefficient-wise kernels move 16 bytes (two coefficients) per lane; four covers two
+
+
+def corner_values(q, wide):
+    """the residues at which a conditional subtraction or a carry can go wrong; wide: the non-canonical values too"""
+    vals = [0, 1, 2, q // 2, q // 2 + 1, q - 2, q - 1]
+    return vals + ([q, 2 * q - 1, (1 << 64) - 1] if wide else [])
+
+
+def corner_operands(moduli, N, wide=False):
+    """(a, b, c): three [batch, limbs, N] operands over the corner values such that every pair (a, b) occurs at every position
+    modulo LANE_WIDTH (a runs through the values fastest, b is the same list advanced once per round of a, c takes a third
+    combination); the batch is as long as that needs.  b and c stay canonical (the accumulating forms read c)."""
+    k = len(corner_values(3, wide))
+    kb = len(corner_values(3, False))
+    total = LANE_WIDTH * k * kb
+    batch = -(-total // N)
+    f = np.arange(batch * N)
+    ia, ib = (f // LANE_WIDTH) % k, (f // (LANE_WIDTH * k)) % kb
+    ic = (ia + 2 * ib + 1) % kb
+    a = np.zeros((batch, len(moduli), N), dtype=np.uint64)
+    b, c = a.copy(), a.copy()
+    for i, q in enumerate(moduli):
+        va = np.array(corner_values(q, wide), dtype=np.uint64)
+        vb = np.array(corner_values(q, False), dtype=np.uint64)
+        a[:, i, :] = va[ia].reshape(batch, N)
+        b[:, i, :] = vb[ib].reshape(batch, N)
+        c[:, i, :] = vb[ic].reshape(batch, N)
+    return a, b, c
+
+
+def pairs_at_every_lane(a, b, q, wide):
+    """does every pair of corner values of modulus q occur in the rows a, b ([batch, N]) at every position modulo LANE_WIDTH?"""
+    seen = {(j % LANE_WIDTH, int(x), int(y)) for row_a, row_b in zip(a, b) for j, (x, y) in enumerate(zip(row_a, row_b))}
+    return all((r, x, y) in seen for r in range(LANE_WIDTH) for x in set(corner_values(q, wide)) for y in set(corner_values(q, False)))
+
+
+R64 = 1 << 64
+# the canonical forms as integer formulas (ring/ring_operations.go); the ...Constant and ...NoMod forms keep the reference's lazy
+# intermediate, which only the oracle restates
+EWISE_FORMULAS = {
+    "ADD": lambda a, b, c, q: (a + b) % q,
+    "SUB": lambda a, b, c, q: (a - b) % q,
+    "NEG": lambda a, b, c, q: q - a,                                   # (the reference leaves q for a zero)
+    "REDUCE": lambda a, b, c, q: a % q,
+    "MUL_COEFFS": lambda a, b, c, q: a * b % q,
+    "MUL_COEFFS_AND_ADD": lambda a, b, c, q: (c + a * b) % q,
+    "MUL_MONT": lambda a, b, c, q: a * b * pow(R64, -1, q) % q,
+    "MUL_MONT_AND_ADD": lambda a, b, c, q: (c + a * b * pow(R64, -1, q)) % q,
+    "MUL_MONT_AND_SUB": lambda a, b, c, q: (c - a * b * pow(R64, -1, q)) % q,
+    "MFORM": lambda a, b, c, q: a * R64 % q,
+    "INV_MFORM": lambda a, b, c, q: a * pow(R64, -1, q) % q,
+    "COPY": lambda a, b, c, q: a,
+}
+# ops whose reference takes any 64-bit first operand
+EWISE_WIDE = ("REDUCE", "MFORM", "INV_MFORM", "COPY", "ADD_NOMOD", "SUB_NOMOD")
+
+
+def ewise_moduli(logn):
+    """one limb per size class of the coefficient-wise kernels' reductions, and a small prime: the 14-bit 12289 up to N = 2^11, beyond
+    that the smallest NTT-friendly prime there is (N = 2^12: 40961, 16 bits -- nothing below is 1 modulo 8192 and prime)"""
+    small = [12289] if logn <= 11 else [more_than(1 << 13, logn)]
+    return [below(61, logn), above(60, logn), above(57, logn), below(57, logn), below(32, logn)] + small

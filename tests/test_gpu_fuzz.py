@@ -4,6 +4,8 @@ degrees that run on the whole-limb kernel, moduli of mixed sizes, the key-switch
 import numpy as np
 import pytest
 
+import limit_moduli as lm
+
 pytestmark = pytest.mark.gpu
 
 
@@ -11,6 +13,9 @@ def _moduli(pkg, rng, logn, count):
     """a random mix of modulus sizes that are NTT-friendly for this degree"""
     pool = list(pkg.params.Qi60()[-8:]) + list(pkg.params.Pi60()[-4:])
     pool += pkg.params.GenerateNTTPrimes(40, logn, 3) + pkg.params.GenerateNTTPrimes(50, logn, 2) + pkg.params.GenerateNTTPrimes(34, logn, 1)
+    # ... and the primes next to every admission bound (tests/limit_moduli.py)
+    pool += [lm.below(61, logn), lm.above(60, logn), lm.below(60, logn), lm.above(57, logn), lm.below(57, logn), lm.above(46, logn), lm.below(46, logn),
+             lm.above(33, logn), lm.below(33, logn), lm.above(32, logn), lm.below(32, logn)]
     pool = sorted(set(pool))
     idx = rng.choice(len(pool), size=count, replace=False)
     return [pool[i] for i in idx]
@@ -115,6 +120,9 @@ def _ckks_size_moduli(pkg, rng, logn, count):
     pool = []
     for bits in (30, 34, 40, 45, 46, 50, 56):
         pool += pkg.params.GenerateNTTPrimes(bits, logn, 2)
+    # ... and the limit primes of that range (tests/limit_moduli.py): the top of the dual kernels' integer body, both sides of the FP64 body's
+    # limit, both sides of 2^33 and 2^32 (FP64 limbs either way)
+    pool += [lm.below(57, logn), lm.above(46, logn), lm.below(46, logn), lm.above(33, logn), lm.below(33, logn), lm.above(32, logn), lm.below(32, logn)]
     pool = sorted(set(pool))
     idx = rng.choice(len(pool), size=count, replace=False)
     return [pool[i] for i in idx]

@@ -6,18 +6,26 @@ RotateHoisted and Rescale of CKKS, SwitchKeys, Relinearize and Rotate of BFV, at
 single-limb and trivially copied digits), batches on both sides of the pairing and forking thresholds, every launch-shape option, outputs
 over operands and in either address order, every entry point on cold pools (a pointer into a pool is taken after Pool::ensure, which may
 move it), and every refusal.  The stubs touch the first and the last word of every row a kernel would read or write, so a wrong pool size,
-digit offset or pair stride is a sanitizer report."""
+digit offset or pair stride is a sanitizer report.  The same calls then run over rings whose moduli sit at the limits of the admission bounds
+(tests/limit_moduli.py)."""
 import os
 import subprocess
 
+import limit_moduli as lm
 from host_stub_build import build_host_driver
+
+# (logN, Q, P): the largest primes below 2^61 with one special prime (beta = |Q| = 5); either side of 2^57; either side of 2^33
+LIMIT_RINGS = [(12, lm.below(61, 16, 6)[1:], [lm.below(61, 16)]),
+               (15, lm.above(57, 16, 5), lm.below(57, 16, 2)),
+               (16, lm.above(33, 16, 4), lm.below(33, 16, 2))]
 
 
 def test_key_switch_host_side_under_asan_ubsan(tmp_path):
     exe = build_host_driver(str(tmp_path), "key_switch_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan")
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the paths, not the caller's env
     env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    args = [str(a) for logn, Q, P in LIMIT_RINGS for a in [logn, len(Q), len(P)] + Q + P]
+    res = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
     assert "failures 0" in res.stdout, res.stdout
     calls = int(res.stdout.split("calls ")[1].split(",")[0])
@@ -26,8 +34,10 @@ def test_key_switch_host_side_under_asan_ubsan(tmp_path):
     # above 0 (3 at level 1), and below N = 2^16 3 more CKKS calls per level (descending outputs); |Q| = 5, 5 and 4
     per_batch = lambda nq, below16: 17 * nq + 11 + 4 * (nq - 1) - 1 + (3 * nq if below16 else 0)
     # ... and per plan, each of the 7 entry points twice on a plan of its own
-    assert calls == 10 * 3 * (2 * per_batch(5, True) + per_batch(4, False)) + 3 * 10 * 7 * 2, res.stdout
-    assert refusals == 3 * 10 * REFUSALS_PER_PLAN, res.stdout
+    # ... over the three rings of the driver and the limit rings
+    rings = [(5, True), (5, True), (4, False)] + [(len(Q), logn < 16) for logn, Q, P in LIMIT_RINGS]
+    assert calls == 10 * 3 * sum(per_batch(nq, below16) for nq, below16 in rings) + len(rings) * 10 * 7 * 2, res.stdout
+    assert refusals == len(rings) * 10 * REFUSALS_PER_PLAN, res.stdout
 
 
 # lr_ckks_switch_keys (one of them found at the inner product, after launches), _mulrelin, _rotate, _rotate_hoisted, lr_bfv_switch_keys, _relinearize,

@@ -4,12 +4,21 @@ g++ against the host-only HIP stand-in and the recording launch stubs of tests/c
 tests/cpp/ntt_dispatch_driver.cpp through the public ABI: N = 2^10 .. 2^16, moduli sets for the forward variants 0 .. 3, every option that
 changes a route, batches 1 and 3 and one launch that crosses run_ntt's chunking, in place and out of place, and every refusal.  After each
 call the driver reads the name of the kernel the context dispatched; the set of names per (ring, moduli, options) is compared with
-tests/golden/ntt_dispatch_routes.txt, which was recorded from the dispatcher as it was before it was split into decision and launches."""
+tests/golden/ntt_dispatch_routes.txt, which was recorded from the dispatcher as it was before it was split into decision and launches.
+After those, the modulus classes at the limits of the admission bounds (tests/limit_moduli.py: just under 2^61, either side of 2^57, just
+above and just below 2^33) under the options that move them between the assembly variants, the FP64 body and the C++ kernels: the variants
+the contexts report must be the ones the Python restatement of the predicates gives, and the kernel names are pinned by the same golden."""
 import os
 import subprocess
 
+import limit_moduli as lm
 from conftest import ROOT
 from host_stub_build import build_host_driver
+
+# five primes = 1 mod 2^17 per class (NTT-friendly for every ring of the driver)
+LIMIT_CLASSES = {"61-": lm.below(61, 16, 5), "57-": lm.below(57, 16, 5), "57+": lm.above(57, 16, 5), "33+": lm.above(33, 16, 5),
+                 "33-": lm.below(33, 16, 5)}
+LIMIT_OPTIONS = {"default": {}, "no_asm": {"no_asm": True}, "no_fp": {"no_fp": True}, "asm_variant=0": {"asm_variant": 0}, "asm_variant=1": {"asm_variant": 1}}
 
 # one name per route of NttRoute::Kind that a public call can end on ("xK": a plain transform call of K launches; without: the last
 # transform of a compound call).  The lazy inverse routes are always followed by another transform inside the call that asks for them, and
@@ -32,13 +41,15 @@ def test_ntt_dispatch_host_side_under_asan_ubsan(tmp_path):
     exe = build_host_driver(str(tmp_path), "ntt_dispatch_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan")
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the contexts' options decide the routes, not the caller's env
     env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
+    args = [str(a) for name, qs in LIMIT_CLASSES.items() for a in [name] + qs]
+    res = subprocess.run([exe] + args, capture_output=True, text=True, timeout=1500, env=env)
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
     assert "failures 0" in res.stdout, res.stdout[-2000:]
     calls = int(res.stdout.split("calls ")[1].split(",")[0])
     refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
     # 5 rings x 4 moduli sets x 10 option sets, one more option set at N = 2^14 and three more at N = 2^15
-    configs = 4 * (5 * 10 + 1 + 3)
+    # ... and the five limit classes x 5 rings x 5 option sets
+    configs = 4 * (5 * 10 + 1 + 3) + len(LIMIT_CLASSES) * 5 * len(LIMIT_OPTIONS)
     # per batch (1 and 3): 18 + 10 transforms, 4 x 5 + 2 x 5 divisions, 3 x 3 rescales of a ciphertext, 3 x 3 ModDowns, 4 x 3 monomial products,
     # 3 x 4 permutations, 2 key switches; the six host-slice transforms at batch 1 only; the three calls of the chunked launch once
     assert calls == configs * (2 * (28 + 30 + 9 + 9 + 12 + 12 + 2) + 6) + 3, res.stdout[-300:]
@@ -49,6 +60,16 @@ def test_ntt_dispatch_host_side_under_asan_ubsan(tmp_path):
     for g, w in zip(got, want):
         assert g == w
     assert len(got) == len(want)
+    # the limit classes: what the contexts report is what the restated predicates say (a changed bound shows here, next to the golden)
+    seen = 0
+    for ln in got:
+        head = ln.split(":", 1)[0].split()
+        cls, opt = head[2].split("=", 1)[1], head[3]
+        if cls in LIMIT_CLASSES:
+            want_fwd, want_inv = lm.asm_variants(LIMIT_CLASSES[cls], **LIMIT_OPTIONS[opt])
+            assert head[4:] == ["fwd=%d" % want_fwd, "inv=%d" % want_inv], ln
+            seen += 1
+    assert seen == len(LIMIT_CLASSES) * 5 * len(LIMIT_OPTIONS)
     names = {n for ln in got for n in ln.split(":", 1)[1].split()}
     for route, witnesses in ROUTE_WITNESSES.items():
         for w in witnesses:
