@@ -619,6 +619,54 @@ int lr_ckks_decode(lr_ckks_encoder *enc, const lr_poly *pt, int slots, int level
 int lr_ckks_encode_device(lr_ckks_encoder *enc, const void *device_values, int slots, int level, double scale, int batch, lr_poly *pt);
 int lr_ckks_decode_device(lr_ckks_encoder *enc, const lr_poly *pt, int slots, int level, double scale, int batch, void *device_values);
 
+/* ckks.Encryptor (ckks/encryptor.go:100-362) for a batch of ciphertexts, device-resident, after the sampling.  lr_ckks_encryptor owns what
+ * newEncryptor builds (:100-119): NewFastBasisExtender(contextQ, contextP), three pool polys over Q||P for max_batch ciphertexts, the
+ * matrixTernaryMontgomery rows of every limb (ring/ring_context.go:119-122) and a pinned staging buffer.  ctxP == NULL is the reference's
+ * "modulus P is empty": only the fast forms work (fast = 0 is LR_ERR_ARG).  max_batch outside 1 .. 65535, N < 8 (a bit plane is N / 8
+ * bytes) and a ctxP on another device or of another N are LR_ERR_ARG.  The work is ordered on ctxQ's stream.
+ * The randomness is exactly lr_bfv_encryptor's: u_coeff_bits, u_sign_bits [batch][N / 8] (sampleTernary at p = 0.5), e0, e1, e [batch][N]
+ * (magnitude in bits 0-6, sign in bit 7; the residue is ring/gaussianSampler.go:247: sign 1 -> coeff, sign 0 -> q_j - coeff) -- N / 4 + 2 N
+ * bytes per public-key ciphertext instead of the three polys over Q||P that lr_ckks_encrypt_pk takes.
+ * pt, out_c0, out_c1: polys of ctxQ in the NTT domain with at least level + 1 limbs, as lr_ckks_encode writes them and lr_ckks_decrypt
+ * reads them; limbs above level are not touched.  Keys: polys of ctxQ in NTT + Montgomery form with |Q| + |P| limbs in contextQP's order
+ * (fast: |Q| suffice).  Keys and pt have batch 1 or the call's batch.  crp: the uniform poly in the NTT domain, over Q||P (fast: over Q),
+ * of the call's batch, read only (crp as an output is LR_ERR_ARG).  out_c0 == out_c1 is LR_ERR_ARG; a poly of another context is
+ * LR_ERR_ARG; batch < 1, > max_batch or != the polys', too few limbs, or a level outside 0 .. |Q| - 1: LR_ERR_SHAPE.
+ * encrypt_pk = pkEncryptor.encrypt (:179-237).
+ *   fast = 1 (:187-200, :234): u expanded then NTT, e_k expanded then NTT, ct_k = CRed(MRed(u, pk_k) + e_k), + pt on component 0, all over
+ *   limbs 0 .. level: below the top level the natural restriction of the reference's lines to those limbs.
+ *   fast = 0 (:204-234): for the same decisions the bits of lr_ckks_encrypt_pk fed the expanded polys, at every level: u -> NTT, the two
+ *   products and InvNTT over all of Q||P, SampleAndAdd on every row, ModDownPQ(level) -- which reads its "P part" at rows level + 1 ..
+ *   level + |P| of the pool poly (ring_basis_extension.go:256) -- NTT over limbs 0 .. level, + pt.  The rows ModDownPQ reads are the
+ *   special primes' only at level = |Q| - 1: below it the call follows the reference's lines literally and the result is not a
+ *   ciphertext of pt (the reference itself only runs at the top level: its Context.NTT at :229 walks every modulus of contextQ).
+ * encrypt_sk = skEncryptor.encrypt (:318-362).
+ *   fast = 1 (:324-330, :359): ct0 = CRed(CRed(Neg(MRed(crp, sk)) + NTT(e)) + pt), ct1 = crp, over limbs 0 .. level (Neg of 0 is q_j, as
+ *   in the reference).
+ *   fast = 0 (:337-359): Neg(MRed(crp, sk)) over Q||P, InvNTT, SampleAndAdd, ModDownPQ(level) as above, NTT, + pt; ct1 =
+ *   ModDownNTTPQ(level, crp), which reads its P part at rows |Q| .. (ring_basis_extension.go:163-190) and runs here on a copy of those
+ *   rows, so that crp stays intact.  Below the top level ct1 is therefore round(crp / P) over limbs 0 .. level, while ct0 is what the
+ *   literal ModDownPQ gives: only level = |Q| - 1 yields a ciphertext of pt.
+ * The host forms stage the bytes through the pinned buffer: the caller's arrays are free on return, the call is asynchronous.  The
+ * _device forms take the same bytes in device memory: stream-ordered, no host copy, no synchronisation.
+ * lr_options::no_epilogue selects the reference's call-by-call shape (the samplers expand into pool polys, then one launch per Context
+ * call); both shapes give the same bits. */
+typedef struct lr_ckks_encryptor lr_ckks_encryptor;
+int lr_ckks_encryptor_create(lr_context *ctxQ, lr_context *ctxP, int max_batch, lr_ckks_encryptor **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_ckks_encryptor_create_ex(lr_context *ctxQ, lr_context *ctxP, int max_batch, const lr_options *opt, lr_ckks_encryptor **out);
+int lr_ckks_encryptor_destroy(lr_ckks_encryptor *enc);
+int lr_ckks_encryptor_encrypt_pk(lr_ckks_encryptor *enc, int fast, int level, const lr_poly *pk0, const lr_poly *pk1,
+                                 const uint8_t *u_coeff_bits, const uint8_t *u_sign_bits, const uint8_t *e0, const uint8_t *e1,
+                                 const lr_poly *pt, int batch, lr_poly *out_c0, lr_poly *out_c1);
+int lr_ckks_encryptor_encrypt_sk(lr_ckks_encryptor *enc, int fast, int level, const lr_poly *sk, const lr_poly *crp, const uint8_t *e,
+                                 const lr_poly *pt, int batch, lr_poly *out_c0, lr_poly *out_c1);
+int lr_ckks_encryptor_encrypt_pk_device(lr_ckks_encryptor *enc, int fast, int level, const lr_poly *pk0, const lr_poly *pk1,
+                                        const void *u_coeff_bits, const void *u_sign_bits, const void *e0, const void *e1,
+                                        const lr_poly *pt, int batch, lr_poly *out_c0, lr_poly *out_c1);
+int lr_ckks_encryptor_encrypt_sk_device(lr_ckks_encryptor *enc, int fast, int level, const lr_poly *sk, const lr_poly *crp, const void *e,
+                                        const lr_poly *pt, int batch, lr_poly *out_c0, lr_poly *out_c1);
+
 /* ------------------------------------------------------------------ multi-device ------ */
 /* a batch of independent ciphertexts shards across the GPUs of a node by contiguous blocks (replicated contexts, tables
  * and keys, created per device with lr_context_create(..., device, ...)); nothing crosses devices but finished results.  The reference's

@@ -304,4 +304,41 @@ class CkksEncoder {
     lr_ckks_encoder *h_ = nullptr;
 };
 
+// ckks.Encryptor (ckks/encryptor.go:100-362) for batches of ciphertexts, after the sampling: the randomness in BfvEncryptor's compact form,
+// plaintext and ciphertext in the NTT domain over limbs 0 .. level.  contextP == nullptr: "modulus P is empty", only the fast forms
+class CkksEncryptor {
+  public:
+    CkksEncryptor(const Context *contextQ, const Context *contextP, int max_batch = 1, const lr_options *options = nullptr) {      // newEncryptor :100
+        check(lr_ckks_encryptor_create_ex(contextQ->handle(), contextP ? contextP->handle() : nullptr, max_batch, options, &h_));
+    }
+    ~CkksEncryptor() { lr_ckks_encryptor_destroy(h_); }
+    CkksEncryptor(const CkksEncryptor &) = delete;
+    CkksEncryptor &operator=(const CkksEncryptor &) = delete;
+    void EncryptPk(int level, const Poly *pk0, const Poly *pk1, const std::vector<uint8_t> &u_coeff_bits, const std::vector<uint8_t> &u_sign_bits,
+                   const std::vector<uint8_t> &e0, const std::vector<uint8_t> &e1, const Poly *plaintext, int batch, Poly *c0, Poly *c1,
+                   bool fast = false) {                                                                                                // :179
+        check(lr_ckks_encryptor_encrypt_pk(h_, fast ? 1 : 0, level, pk0->handle(), pk1->handle(), u_coeff_bits.data(), u_sign_bits.data(), e0.data(),
+                                           e1.data(), plaintext->handle(), batch, c0->handle(), c1->handle()));
+    }
+    void EncryptSk(int level, const Poly *sk, const Poly *crp, const std::vector<uint8_t> &e, const Poly *plaintext, int batch, Poly *c0, Poly *c1,
+                   bool fast = false) {                                                                                                // :318
+        check(lr_ckks_encryptor_encrypt_sk(h_, fast ? 1 : 0, level, sk->handle(), crp->handle(), e.data(), plaintext->handle(), batch, c0->handle(),
+                                           c1->handle()));
+    }
+    // the same bytes in device memory: stream-ordered, no host copy
+    void EncryptPkDevice(int level, const Poly *pk0, const Poly *pk1, const void *u_coeff_bits, const void *u_sign_bits, const void *e0,
+                         const void *e1, const Poly *plaintext, int batch, Poly *c0, Poly *c1, bool fast = false) {
+        check(lr_ckks_encryptor_encrypt_pk_device(h_, fast ? 1 : 0, level, pk0->handle(), pk1->handle(), u_coeff_bits, u_sign_bits, e0, e1,
+                                                  plaintext->handle(), batch, c0->handle(), c1->handle()));
+    }
+    void EncryptSkDevice(int level, const Poly *sk, const Poly *crp, const void *e, const Poly *plaintext, int batch, Poly *c0, Poly *c1,
+                         bool fast = false) {
+        check(lr_ckks_encryptor_encrypt_sk_device(h_, fast ? 1 : 0, level, sk->handle(), crp->handle(), e, plaintext->handle(), batch, c0->handle(),
+                                                  c1->handle()));
+    }
+
+  private:
+    lr_ckks_encryptor *h_ = nullptr;
+};
+
 }  // namespace ring

@@ -159,6 +159,13 @@ SYMBOLS = {
     "lr_bfv_encrypt_sk": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
     "lr_bfv_encrypt_pk_device": [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
     "lr_bfv_encrypt_sk_device": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
+    "lr_ckks_encryptor_create": [vp, vp, i32, C.POINTER(vp)],
+    "lr_ckks_encryptor_create_ex": [vp, vp, i32, vp, C.POINTER(vp)],
+    "lr_ckks_encryptor_destroy": [vp],
+    "lr_ckks_encryptor_encrypt_pk": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_ckks_encryptor_encrypt_sk": [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp],
+    "lr_ckks_encryptor_encrypt_pk_device": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_ckks_encryptor_encrypt_sk_device": [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp],
     "lr_bfv_decryptor_create": [vp, i32, C.POINTER(vp)],
     "lr_bfv_decryptor_destroy": [vp],
     "lr_bfv_decrypt": [vp, C.POINTER(vp), i32, vp, vp, i32],

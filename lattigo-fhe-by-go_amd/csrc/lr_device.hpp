@@ -420,6 +420,40 @@ struct NegMulLaunch {
 };
 hipError_t launch_bfv_negmul(const NegMulLaunch &L, int limbs, int batch, hipStream_t stream);
 
+// ---- ckks.Encryptor (lr_ckks_encrypt.hip): the fast forms of ckks/encryptor.go around one forward transform ----
+// the operands of that transform in one launch: `ternary` (0 or 1) polys from the two bit planes (as TernaryLaunch), then `noises` (0 .. 2)
+// polys from the Gaussian samplers' bytes, part k of `batch` polys at out + k * part_stride.  A noise coefficient is the reference's
+// residue (sign 1 -> c, sign 0 -> q - c) with the q of (0, sign 0) written as 0: the transform that follows reduces it to that anyway.
+struct CkksExpandLaunch {
+    const unsigned char *coeff_bits, *sign_bits;   // device [batch][n / 8]
+    const unsigned char *e[2];                     // device [batch][n]
+    u64 *out;
+    long long out_stride, part_stride;
+    int n, ternary, noises;
+    LimbScalars one, minus_one;
+    const LimbParams *lp;
+};
+hipError_t launch_ckks_expand(const CkksExpandLaunch &L, int limbs, int batch, hipStream_t stream);
+// pkEncryptor.encrypt, fast (ckks/encryptor.go:187-200, :234): out_k = CRed(MRed(u, pk_k) + e_k), out0 = CRed(out0 + pt); u, e0, e1 are
+// the transformed polys of one expansion (poly stride r_stride)
+struct CkksPkFastLaunch {
+    const u64 *u, *e0, *e1, *pk0, *pk1, *pt;
+    u64 *out0, *out1;
+    long long r_stride, pk0_stride, pk1_stride, pt_stride, out0_stride, out1_stride;   // between batch polys (0 = broadcast)
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_ckks_pk_fast(const CkksPkFastLaunch &L, int limbs, int batch, hipStream_t stream);
+// skEncryptor.encrypt, fast (ckks/encryptor.go:324-330, :359): out0 = CRed(CRed((q - MRed(crp, sk)) + e) + pt), out1 = crp
+struct CkksSkFastLaunch {
+    const u64 *crp, *sk, *e, *pt;
+    u64 *out0, *out1;
+    long long crp_stride, sk_stride, e_stride, pt_stride, out0_stride, out1_stride;
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_ckks_sk_fast(const CkksSkFastLaunch &L, int limbs, int batch, hipStream_t stream);
+
 // ---- ckks.Encoder (lr_ckks_encode.hip): Encode / Decode of ckks/encoder.go for a batch of plaintexts ----
 struct Cplx { double re, im; };                 // a complex128 as Go lays it out
 constexpr int kCkksFusedMaxLogSlots = 13;       // the fused kernels hold 16 * slots bytes in one CU's LDS: 128 KiB of the 160

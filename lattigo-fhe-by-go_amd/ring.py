@@ -1004,6 +1004,71 @@ def NewCkksEncoder(contextQ, max_batch=1, roots=None, options=None):  # ckks.New
     return CkksEncoder(contextQ, max_batch, roots, options)
 
 
+class CkksEncryptor:
+    """ckks.Encryptor (ckks/encryptor.go:100-362) for a batch of ciphertexts on the device (lr_ckks_encryptor), after the sampling.  The
+    randomness is BfvEncryptor's compact form: u_bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each; e = uint8 [batch, N] per
+    sampled poly, magnitude in the low 7 bits and sign in bit 7.  Keys are Poly of contextQ over Q||P (fast: over Q) in NTT + Montgomery
+    form, batch 1 or the call's; plaintext and ctOut are Poly of contextQ in the NTT domain with at least level + 1 limbs (what
+    CkksEncoder.Encode writes and CkksPlan.Decrypt reads); limbs above level are not touched.  contextP None: only the fast forms."""
+
+    def __init__(self, contextQ, contextP, max_batch=1, options=None):
+        self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
+        h = C.c_void_p()
+        hP = None if contextP is None else contextP.h
+        if options is None:
+            check(lib().lr_ckks_encryptor_create(contextQ.h, hP, max_batch, C.byref(h)))
+        else:
+            check(lib().lr_ckks_encryptor_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().lr_ckks_encryptor_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _bytes(self, a, batch, per_poly):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.size != batch * per_poly:
+            raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
+        return a
+
+    def EncryptPk(self, pk, u_bits, e, plaintext, ctOut, level, fast=False):  # pkEncryptor.encrypt, ckks/encryptor.go:179
+        batch, N = ctOut[0].batch, self.contextQ.N
+        uc, us = self._bytes(u_bits[0], batch, N // 8), self._bytes(u_bits[1], batch, N // 8)
+        e0, e1 = self._bytes(e[0], batch, N), self._bytes(e[1], batch, N)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().lr_ckks_encryptor_encrypt_pk(self.h, 1 if fast else 0, level, pk[0].h, pk[1].h, p(uc), p(us), p(e0), p(e1), plaintext.h,
+                                                 batch, ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+    def EncryptSk(self, sk, crp, e, plaintext, ctOut, level, fast=False):  # skEncryptor.encrypt, :318
+        batch = ctOut[0].batch
+        eb = self._bytes(e, batch, self.contextQ.N)
+        check(lib().lr_ckks_encryptor_encrypt_sk(self.h, 1 if fast else 0, level, sk.h, crp.h, eb.ctypes.data_as(C.c_void_p), plaintext.h,
+                                                 batch, ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+    def EncryptPkDevice(self, pk, u_bits_ptrs, e_ptrs, plaintext, ctOut, level, fast=False):
+        """the same with the randomness in device memory (pointers, e.g. a torch uint8 tensor's data_ptr()); stream-ordered"""
+        v = C.c_void_p
+        check(lib().lr_ckks_encryptor_encrypt_pk_device(self.h, 1 if fast else 0, level, pk[0].h, pk[1].h, v(u_bits_ptrs[0]),
+                                                        v(u_bits_ptrs[1]), v(e_ptrs[0]), v(e_ptrs[1]), plaintext.h, ctOut[0].batch,
+                                                        ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+    def EncryptSkDevice(self, sk, crp, e_ptr, plaintext, ctOut, level, fast=False):
+        check(lib().lr_ckks_encryptor_encrypt_sk_device(self.h, 1 if fast else 0, level, sk.h, crp.h, C.c_void_p(e_ptr), plaintext.h,
+                                                        ctOut[0].batch, ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+
+def NewCkksEncryptor(contextQ, contextP, max_batch=1, options=None):  # ckks.NewEncryptorFromPk / FromSk, ckks/encryptor.go:76-98
+    return CkksEncryptor(contextQ, contextP, max_batch, options)
+
+
 class BfvBatcher:
     """Merges the Mul and Relinearize calls of concurrent BFV evaluators -- the reference's own pooled workload: every task of
     examples/dbfv/psi/psi.go:215-233 calls evaluator.Mul and evaluator.Relinearize on one ciphertext pair -- into batched launches

@@ -1,0 +1,89 @@
+// Stand-ins for the launchers of lr_ckks_encrypt.hip, for the CPU-sanitizer build of the CKKS encryptor's host side
+// (tests/test_host_ckks_encryptor_sanitizers.py); the companion of bfv_encryptor_stub.cpp, which serves the launchers the two encryptors
+// share and stays as it is.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.  A stub counts its launch and touches the
+// first and the last byte of everything the real kernel would read or write at the addresses the launch names: "device" memory is
+// malloc'ed at its exact size, so a wrong size, stride, part offset or batch count in the host code is an AddressSanitizer report.
+#include <atomic>
+
+#include "lr_device.hpp"
+
+namespace lr {
+
+extern std::atomic<unsigned long long> g_encryptor_stub_launches;      // bfv_encryptor_stub.cpp
+std::atomic<unsigned long long> g_ckks_expand_launches{0}, g_ckks_fast_launches{0};
+
+namespace {
+thread_local volatile u64 t_sink;
+template <class T>
+void rd(const T *p, long long count) {
+    if (count <= 0) return;
+    t_sink = (u64)((const volatile unsigned char *)p)[0];
+    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
+}
+void wr(u64 *p, long long count) {
+    if (count <= 0) return;
+    p[0] = p[0];
+    p[count - 1] = p[count - 1];
+}
+}  // namespace
+
+hipError_t launch_ckks_expand(const CkksExpandLaunch &L, int limbs, int batch, hipStream_t) {
+    const int parts = L.ternary + L.noises;
+    if (limbs <= 0 || batch <= 0 || parts <= 0) return hipSuccess;
+    if (L.n < 8 || limbs > kMaxLimbs || L.ternary < 0 || L.ternary > 1 || L.noises < 0 || L.noises > 2 || batch > 65535) return hipErrorInvalidValue;
+    g_encryptor_stub_launches.fetch_add(1);
+    g_ckks_expand_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b) {
+        if (L.ternary) {
+            rd(L.coeff_bits + (long long)b * (L.n >> 3), L.n >> 3);
+            rd(L.sign_bits + (long long)b * (L.n >> 3), L.n >> 3);
+        }
+        for (int k = 0; k < L.noises; ++k) rd(L.e[k] + (long long)b * L.n, L.n);
+        for (int p = 0; p < parts; ++p)
+            for (int i = 0; i < limbs; ++i) wr(L.out + p * L.part_stride + b * L.out_stride + (long long)i * L.n, L.n);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_ckks_pk_fast(const CkksPkFastLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || batch > 65535) return hipErrorInvalidValue;
+    g_encryptor_stub_launches.fetch_add(1);
+    g_ckks_fast_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.u + b * L.r_stride + row, L.n);
+            rd(L.e0 + b * L.r_stride + row, L.n);
+            rd(L.e1 + b * L.r_stride + row, L.n);
+            rd(L.pk0 + b * L.pk0_stride + row, L.n);
+            rd(L.pk1 + b * L.pk1_stride + row, L.n);
+            rd(L.pt + b * L.pt_stride + row, L.n);
+            wr(L.out0 + b * L.out0_stride + row, L.n);
+            wr(L.out1 + b * L.out1_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+hipError_t launch_ckks_sk_fast(const CkksSkFastLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || batch > 65535) return hipErrorInvalidValue;
+    g_encryptor_stub_launches.fetch_add(1);
+    g_ckks_fast_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.crp + b * L.crp_stride + row, L.n);
+            rd(L.sk + b * L.sk_stride + row, L.n);
+            rd(L.e + b * L.e_stride + row, L.n);
+            rd(L.pt + b * L.pt_stride + row, L.n);
+            wr(L.out0 + b * L.out0_stride + row, L.n);
+            wr(L.out1 + b * L.out1_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+}  // namespace lr
