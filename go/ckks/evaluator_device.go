@@ -109,6 +109,11 @@ func (eval *evaluator) keyImage(k *SwitchingKey) *ring.Poly {
 	if img, ok := s.keys[k]; ok {
 		return img
 	}
+	if made, ok := generatedKeyImages.Load(k); ok { // a key of this process's key generator (keygen_device.go): already on the device
+		generatedKeyImages.Delete(k) // from here on the evaluator's state owns the image: ReleaseDevice lets it go
+		s.keys[k] = made.(*ring.Poly)
+		return s.keys[k]
+	}
 	img := s.plan.SwitchingKeyImage(k.evakey)
 	s.keys[k] = img
 	return img

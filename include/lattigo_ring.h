@@ -667,6 +667,60 @@ int lr_ckks_encryptor_encrypt_pk_device(lr_ckks_encryptor *enc, int fast, int le
 int lr_ckks_encryptor_encrypt_sk_device(lr_ckks_encryptor *enc, int fast, int level, const lr_poly *sk, const lr_poly *crp, const void *e,
                                         const lr_poly *pt, int batch, lr_poly *out_c0, lr_poly *out_c1);
 
+/* ckks.KeyGenerator and bfv.KeyGenerator (ckks/keygen.go:79-494, bfv/keygen.go:70-441) for a batch of keys, device-resident, after the
+ * sampling.  lr_keygen owns what NewKeyGenerator builds -- a pool over Q||P -- plus MForm(P mod q_j), the matrixTernaryMontgomery rows of
+ * every limb and a pinned staging buffer.  ctxP == NULL is the reference's "modulus P is empty": only lr_keygen_secret_key and
+ * lr_keygen_public_key work, over Q (the three switching-key entry points are LR_ERR_ARG).  max_batch outside 1 .. 65535, N < 8 (a bit
+ * plane is N / 8 bytes) and a ctxP on another device or of another N are LR_ERR_ARG.  The work is ordered on ctxQ's stream.
+ * The randomness is exactly lr_bfv_encryptor's: coeff_bits, sign_bits [batch][N / 8] (coefficient i uses bit i & 7 of byte i >> 3, and
+ * index = (coeff & (sign ^ 1)) | ((sign & coeff) << 1) selects {0, MForm(1), MForm(q_j - 1)} -- what sampleTernary ends in at p = 1/3, at
+ * any p and in the sparse sampler alike); e [..][N] bytes per sampled poly, magnitude in bits 0-6, sign in bit 7 (the residue is
+ * ring/gaussianSampler.go:247: sign 1 -> coeff, sign 0 -> q_j - coeff).  Both Gaussian samplers are bound to contextQP
+ * (ckks/ckks.go:81, bfv/bfv.go:70), so one byte decides a coefficient on every row of Q||P.  The uniform polys are the caller's.
+ * Every poly is a poly of ctxQ in NTT + Montgomery form with |Q| + |P| limbs in contextQP's order.
+ * lr_keygen_secret_key = GenSecretKey (ckks/keygen.go:97-113): SampleTernaryMontgomeryNTTNew into sk_out, batch polys.
+ * lr_keygen_public_key = GenPublicKey (:138-151): pk0_out = Neg(MulCoeffsMontgomeryAndAdd(sk, pk1, SampleNTT(e))) (Neg of 0 is q_j, as in
+ *   the reference); pk1 = the caller's uniform poly, read only; sk has batch 1 or the call's; e = [batch][N].
+ * The three switching-key entry points are newSwitchingKey (ckks/keygen.go:282-338, bfv/keygen.go:285-333) for n_keys keys.  evks = n_keys
+ *   polys in the layout lr_ckks_switch_keys reads: batch 2 beta (beta = ceil(|Q| / |P|)), member 2 i = evakey[i][0], member 2 i + 1 =
+ *   evakey[i][1].  The odd members hold the caller's uniform a on entry and are not written (the reference samples a straight into the
+ *   key too); the even members are outputs: evakey[i][0] = CRed(CRed(MForm(NTT(e_i)) + [row in digit i] P skIn) + (q_j - MRed(a_i, skOut))),
+ *   digit i owning rows i |P| .. min((i + 1) |P|, |Q|) - 1.  e = [n_keys][beta][N].  The keys are read through the pointer array: they
+ *   need not be contiguous.  The two schemes' lines -- P multiplied in before or after the powers of sk, the digit loop broken at |Q| - 1
+ *   or at |Q| + |P| - 1 -- give the same bits (every MRed is fully reduced, P skIn is zero on the rows of P), so one path serves both.
+ *   lr_keygen_switching_keys = GenSwitchingKey (:247-258): skIn = sk_in, batch n_keys or 1; sk_out has batch n_keys or 1.
+ *   lr_keygen_relin_keys = GenRelinKey: key i switches from sk^(i + 2); n_powers = 1 is ckks/keygen.go:192-205, n_powers = maxDegree is
+ *     bfv/keygen.go:172-196.  sk has batch 1.
+ *   lr_keygen_rotation_keys = genrotKey (ckks/keygen.go:487-494, bfv/keygen.go:429-441) for each Galois element: skIn =
+ *     PermuteNTT(sk, galois_elements[k]).  sk has batch 1; the elements are read on the host during the call.
+ * Refusals: LR_ERR_ARG: a null argument, a poly of another context, an output that shares memory with an input or with another output,
+ * an even Galois element, a switching-key call on a handle without ctxP, ctxQ and ctxP on different streams at the time of a call
+ * (every entry point of a handle with a ctxP: call lr_context_set_stream on both or on neither); LR_ERR_SHAPE: batch, n_keys or
+ * n_powers < 1 or > max_batch, a poly with fewer than |Q| + |P| limbs, a poly whose batch differs from the call's (where batch 1 is not
+ * allowed), a key whose batch is not 2 beta; LR_ERR_UNSUPPORTED, at creation: N > 2^30, more than 64 limbs in Q||P.
+ * The host forms stage the bytes through the pinned buffer: the caller's arrays are free on return, the call is asynchronous.  The
+ * _device forms take the same bytes in device memory: stream-ordered, no host copy, no synchronisation.
+ * lr_options::no_epilogue selects the reference's call-by-call shape (one launch per Context call: MForm, Add on the digit's rows,
+ * MulCoeffsMontgomeryAndSub, PermuteNTT, MulScalarBigint, MulCoeffsMontgomery); both shapes give the same bits. */
+typedef struct lr_keygen lr_keygen;
+int lr_keygen_create(lr_context *ctxQ, lr_context *ctxP, int max_batch, lr_keygen **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_keygen_create_ex(lr_context *ctxQ, lr_context *ctxP, int max_batch, const lr_options *opt, lr_keygen **out);
+int lr_keygen_destroy(lr_keygen *kg);
+int lr_keygen_secret_key(lr_keygen *kg, const uint8_t *coeff_bits, const uint8_t *sign_bits, int batch, lr_poly *sk_out);
+int lr_keygen_public_key(lr_keygen *kg, const lr_poly *sk, const uint8_t *e, int batch, lr_poly *pk0_out, const lr_poly *pk1);
+int lr_keygen_switching_keys(lr_keygen *kg, const lr_poly *sk_in, const lr_poly *sk_out, const uint8_t *e, int n_keys, lr_poly *const *evks);
+int lr_keygen_relin_keys(lr_keygen *kg, const lr_poly *sk, int n_powers, const uint8_t *e, lr_poly *const *evks);
+int lr_keygen_rotation_keys(lr_keygen *kg, const lr_poly *sk, const uint64_t *galois_elements, int n_keys, const uint8_t *e,
+                            lr_poly *const *evks);
+int lr_keygen_secret_key_device(lr_keygen *kg, const void *coeff_bits, const void *sign_bits, int batch, lr_poly *sk_out);
+int lr_keygen_public_key_device(lr_keygen *kg, const lr_poly *sk, const void *e, int batch, lr_poly *pk0_out, const lr_poly *pk1);
+int lr_keygen_switching_keys_device(lr_keygen *kg, const lr_poly *sk_in, const lr_poly *sk_out, const void *e, int n_keys,
+                                    lr_poly *const *evks);
+int lr_keygen_relin_keys_device(lr_keygen *kg, const lr_poly *sk, int n_powers, const void *e, lr_poly *const *evks);
+int lr_keygen_rotation_keys_device(lr_keygen *kg, const lr_poly *sk, const uint64_t *galois_elements, int n_keys, const void *e,
+                                   lr_poly *const *evks);
+
 /* ------------------------------------------------------------------ multi-device ------ */
 /* a batch of independent ciphertexts shards across the GPUs of a node by contiguous blocks (replicated contexts, tables
  * and keys, created per device with lr_context_create(..., device, ...)); nothing crosses devices but finished results.  The reference's

@@ -341,4 +341,63 @@ class CkksEncryptor {
     lr_ckks_encryptor *h_ = nullptr;
 };
 
+// ckks.KeyGenerator / bfv.KeyGenerator (ckks/keygen.go:79-494, bfv/keygen.go:70-441) for batches of keys, after the sampling: the randomness
+// in BfvEncryptor's compact form, keys over Q||P in NTT + Montgomery form, switching keys as images of batch 2 beta whose odd members hold
+// the caller's uniform polys.  contextP == nullptr: "modulus P is empty", only the secret key and the public key
+class KeyGenerator {
+  public:
+    KeyGenerator(const Context *contextQ, const Context *contextP, int max_batch = 1, const lr_options *options = nullptr) {       // NewKeyGenerator :79
+        check(lr_keygen_create_ex(contextQ->handle(), contextP ? contextP->handle() : nullptr, max_batch, options, &h_));
+    }
+    ~KeyGenerator() { lr_keygen_destroy(h_); }
+    KeyGenerator(const KeyGenerator &) = delete;
+    KeyGenerator &operator=(const KeyGenerator &) = delete;
+    void GenSecretKey(const std::vector<uint8_t> &coeff_bits, const std::vector<uint8_t> &sign_bits, int batch, Poly *sk) {         // :97
+        check(lr_keygen_secret_key(h_, coeff_bits.data(), sign_bits.data(), batch, sk->handle()));
+    }
+    void GenPublicKey(const Poly *sk, const std::vector<uint8_t> &e, int batch, Poly *pk0, const Poly *pk1) {                       // :138
+        check(lr_keygen_public_key(h_, sk->handle(), e.data(), batch, pk0->handle(), pk1->handle()));
+    }
+    void GenSwitchingKeys(const Poly *sk_in, const Poly *sk_out, const std::vector<uint8_t> &e, const std::vector<Poly *> &keys) {  // :247
+        std::vector<lr_poly *> hs = handles(keys);
+        check(lr_keygen_switching_keys(h_, sk_in->handle(), sk_out->handle(), e.data(), (int)hs.size(), hs.data()));
+    }
+    void GenRelinKeys(const Poly *sk, const std::vector<uint8_t> &e, const std::vector<Poly *> &keys) {                             // :192, bfv :172
+        std::vector<lr_poly *> hs = handles(keys);
+        check(lr_keygen_relin_keys(h_, sk->handle(), (int)hs.size(), e.data(), hs.data()));
+    }
+    void GenRotationKeys(const Poly *sk, const std::vector<uint64_t> &galois_elements, const std::vector<uint8_t> &e,
+                         const std::vector<Poly *> &keys) {                                                                        // genrotKey :487
+        std::vector<lr_poly *> hs = handles(keys);
+        check(lr_keygen_rotation_keys(h_, sk->handle(), galois_elements.data(), (int)hs.size(), e.data(), hs.data()));
+    }
+    // the same bytes in device memory: stream-ordered, no host copy
+    void GenSecretKeyDevice(const void *coeff_bits, const void *sign_bits, int batch, Poly *sk) {
+        check(lr_keygen_secret_key_device(h_, coeff_bits, sign_bits, batch, sk->handle()));
+    }
+    void GenPublicKeyDevice(const Poly *sk, const void *e, int batch, Poly *pk0, const Poly *pk1) {
+        check(lr_keygen_public_key_device(h_, sk->handle(), e, batch, pk0->handle(), pk1->handle()));
+    }
+    void GenSwitchingKeysDevice(const Poly *sk_in, const Poly *sk_out, const void *e, const std::vector<Poly *> &keys) {
+        std::vector<lr_poly *> hs = handles(keys);
+        check(lr_keygen_switching_keys_device(h_, sk_in->handle(), sk_out->handle(), e, (int)hs.size(), hs.data()));
+    }
+    void GenRelinKeysDevice(const Poly *sk, const void *e, const std::vector<Poly *> &keys) {
+        std::vector<lr_poly *> hs = handles(keys);
+        check(lr_keygen_relin_keys_device(h_, sk->handle(), (int)hs.size(), e, hs.data()));
+    }
+    void GenRotationKeysDevice(const Poly *sk, const std::vector<uint64_t> &galois_elements, const void *e, const std::vector<Poly *> &keys) {
+        std::vector<lr_poly *> hs = handles(keys);
+        check(lr_keygen_rotation_keys_device(h_, sk->handle(), galois_elements.data(), (int)hs.size(), e, hs.data()));
+    }
+
+  private:
+    static std::vector<lr_poly *> handles(const std::vector<Poly *> &keys) {
+        std::vector<lr_poly *> hs;
+        for (Poly *k : keys) hs.push_back(k->handle());
+        return hs;
+    }
+    lr_keygen *h_ = nullptr;
+};
+
 }  // namespace ring

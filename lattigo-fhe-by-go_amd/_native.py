@@ -166,6 +166,19 @@ SYMBOLS = {
     "lr_ckks_encryptor_encrypt_sk": [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp],
     "lr_ckks_encryptor_encrypt_pk_device": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
     "lr_ckks_encryptor_encrypt_sk_device": [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp],
+    "lr_keygen_create": [vp, vp, i32, C.POINTER(vp)],
+    "lr_keygen_create_ex": [vp, vp, i32, vp, C.POINTER(vp)],
+    "lr_keygen_destroy": [vp],
+    "lr_keygen_secret_key": [vp, vp, vp, i32, vp],
+    "lr_keygen_public_key": [vp, vp, vp, i32, vp, vp],
+    "lr_keygen_switching_keys": [vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_keygen_relin_keys": [vp, vp, i32, vp, C.POINTER(vp)],
+    "lr_keygen_rotation_keys": [vp, vp, u64p, i32, vp, C.POINTER(vp)],
+    "lr_keygen_secret_key_device": [vp, vp, vp, i32, vp],
+    "lr_keygen_public_key_device": [vp, vp, vp, i32, vp, vp],
+    "lr_keygen_switching_keys_device": [vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_keygen_relin_keys_device": [vp, vp, i32, vp, C.POINTER(vp)],
+    "lr_keygen_rotation_keys_device": [vp, vp, u64p, i32, vp, C.POINTER(vp)],
     "lr_bfv_decryptor_create": [vp, i32, C.POINTER(vp)],
     "lr_bfv_decryptor_destroy": [vp],
     "lr_bfv_decrypt": [vp, C.POINTER(vp), i32, vp, vp, i32],

@@ -454,6 +454,54 @@ struct CkksSkFastLaunch {
 };
 hipError_t launch_ckks_sk_fast(const CkksSkFastLaunch &L, int limbs, int batch, hipStream_t stream);
 
+// ---- KeyGenerator (lr_keygen.hip): newSwitchingKey and GenPublicKey of ckks/keygen.go and bfv/keygen.go around one forward transform ----
+constexpr int kKeygenKeysPerLaunch = 32;   // keys whose addresses and Galois elements travel in one launch's kernel arguments
+// SwitchingKey.evakey as lr_ckks_switch_keys reads it: member m of the key at base + m * stride, 2 i = evakey[i][0], 2 i + 1 = evakey[i][1]
+struct KeygenKeyRef {
+    u64 *base;
+    long long stride;
+};
+// skIn of `keys` keys over the rows of Q: out[k] = MRed(PermuteNTT(sk[k], gen[k]), MForm(P mod q)); gen = 1: no permutation
+struct KeygenSkInLaunch {
+    const u64 *sk;
+    u64 *out;
+    long long sk_stride, out_stride;               // between keys (sk: 0 = one secret key for all)
+    u32 gen[kKeygenKeysPerLaunch];                 // Galois elements modulo 2 N, odd
+    int n, logn;
+    LimbScalars pmont;                             // MForm(P mod q) per limb of Q
+    const LimbParams *lp;
+};
+hipError_t launch_keygen_skin(const KeygenSkInLaunch &L, int limbs, int keys, hipStream_t stream);
+// out[k] = P sk^(first + k + 2) over the rows of Q, k < keys: GenRelinKey's running product
+struct KeygenPowersLaunch {
+    const u64 *sk;
+    u64 *out;
+    long long out_stride;
+    int n, first, keys;
+    LimbScalars pmont;
+    const LimbParams *lp;
+};
+hipError_t launch_keygen_powers(const KeygenPowersLaunch &L, int limbs, hipStream_t stream);
+// evakey[i][0] = CRed(CRed(MForm(e) + [row in digit i] P skIn) + (q - MRed(evakey[i][1], skOut))) for `keys` keys x beta digits, every row of
+// Q||P; e = the transformed noise of item k * beta + i
+struct KeygenFinishLaunch {
+    const u64 *e, *skin, *skout;
+    long long e_stride, skin_stride, skout_stride; // e: between items; skin, skout: between keys (skout: 0 = shared)
+    KeygenKeyRef key[kKeygenKeysPerLaunch];
+    int n, nQ, alpha, beta;
+    const LimbParams *lp;                          // of contextQP
+};
+hipError_t launch_keygen_finish(const KeygenFinishLaunch &L, int rows, int keys, hipStream_t stream);
+// pk0 = q - CRed(pk0 + MRed(sk, pk1)), pk0 holding NTT(e) on entry: GenPublicKey (ckks/keygen.go:144-148)
+struct KeygenPkLaunch {
+    const u64 *sk, *pk1;
+    u64 *pk0;
+    long long sk_stride, pk1_stride, pk0_stride;   // between batch polys (sk: 0 = broadcast)
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_keygen_pk(const KeygenPkLaunch &L, int rows, int batch, hipStream_t stream);
+
 // ---- ckks.Encoder (lr_ckks_encode.hip): Encode / Decode of ckks/encoder.go for a batch of plaintexts ----
 struct Cplx { double re, im; };                 // a complex128 as Go lays it out
 constexpr int kCkksFusedMaxLogSlots = 13;       // the fused kernels hold 16 * slots bytes in one CU's LDS: 128 KiB of the 160

@@ -1069,6 +1069,145 @@ def NewCkksEncryptor(contextQ, contextP, max_batch=1, options=None):  # ckks.New
     return CkksEncryptor(contextQ, contextP, max_batch, options)
 
 
+class KeyGenerator:
+    """ckks.KeyGenerator / bfv.KeyGenerator (ckks/keygen.go:79-494, bfv/keygen.go:70-441) on the device (lr_keygen), after the sampling.
+    The randomness is the encryptors' compact form: bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each; e = uint8 [..., N] per
+    sampled poly, magnitude in the low 7 bits and sign in bit 7.  Every key is a Poly of contextQ over Q||P in NTT + Montgomery form; a
+    switching key is the image CkksPlan.NewSwitchingKey allocates, whose odd members hold the caller's uniform polys on entry and are not
+    written.  contextP None: only the secret key and the public key, over Q."""
+
+    def __init__(self, contextQ, contextP, max_batch=1, options=None):
+        self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
+        h = C.c_void_p()
+        hP = None if contextP is None else contextP.h
+        if options is None:
+            check(lib().lr_keygen_create(contextQ.h, hP, max_batch, C.byref(h)))
+        else:
+            check(lib().lr_keygen_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().lr_keygen_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _bytes(self, a, batch, per_poly):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.size != batch * per_poly:
+            raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
+        return a
+
+    @property
+    def beta(self):
+        if self.contextP is None:
+            raise LatticeRingError(4, "key generator: modulus P is empty (ckks/keygen.go:249-251)")      # LR_ERR_ARG, as the C calls refuse
+        nQ, nP = len(self.contextQ.Modulus), len(self.contextP.Modulus)
+        return -(-nQ // nP)
+
+    def NewKey(self, batch=1):
+        """storage for a secret key or one half of a public key: `batch` polys over Q||P"""
+        return Poly(self.contextQ, len(self.contextQ.Modulus) + (len(self.contextP.Modulus) if self.contextP else 0), batch)
+
+    def NewSwitchingKey(self):
+        """storage for SwitchingKey.evakey (ckks/keygen.go:68-70): beta x 2 polys over Q||P"""
+        beta = self.beta
+        return Poly(self.contextQ, len(self.contextQ.Modulus) + len(self.contextP.Modulus), 2 * beta)
+
+    @staticmethod
+    def _keys(evks):
+        return (C.c_void_p * len(evks))(*[k.h.value for k in evks])
+
+    def GenSecretKey(self, bits, skOut):  # ckks/keygen.go:97
+        batch, N = skOut.batch, self.contextQ.N
+        c, s = self._bytes(bits[0], batch, N // 8), self._bytes(bits[1], batch, N // 8)
+        check(lib().lr_keygen_secret_key(self.h, c.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), batch, skOut.h))
+        return skOut
+
+    def GenPublicKey(self, sk, e, pk):  # :138; pk = (pk0 out, pk1 = the uniform poly)
+        batch = pk[0].batch
+        eb = self._bytes(e, batch, self.contextQ.N)
+        check(lib().lr_keygen_public_key(self.h, sk.h, eb.ctypes.data_as(C.c_void_p), batch, pk[0].h, pk[1].h))
+        return pk
+
+    def GenSwitchingKeys(self, skIn, skOut, e, evks):  # :247, one key per entry of evks
+        eb = self._bytes(e, len(evks) * self.beta, self.contextQ.N)
+        check(lib().lr_keygen_switching_keys(self.h, skIn.h, skOut.h, eb.ctypes.data_as(C.c_void_p), len(evks), self._keys(evks)))
+        return evks
+
+    def GenRelinKeys(self, sk, e, evks):  # ckks/keygen.go:192 (one key), bfv/keygen.go:172 (maxDegree keys)
+        eb = self._bytes(e, len(evks) * self.beta, self.contextQ.N)
+        check(lib().lr_keygen_relin_keys(self.h, sk.h, len(evks), eb.ctypes.data_as(C.c_void_p), self._keys(evks)))
+        return evks
+
+    def GenRotationKeys(self, sk, galois_elements, e, evks):  # genrotKey, :487, for each Galois element
+        eb = self._bytes(e, len(evks) * self.beta, self.contextQ.N)
+        if len(galois_elements) != len(evks):
+            raise LatticeRingError(3, "one switching key per Galois element")
+        check(lib().lr_keygen_rotation_keys(self.h, sk.h, _u64(galois_elements), len(evks), eb.ctypes.data_as(C.c_void_p), self._keys(evks)))
+        return evks
+
+    def Pow2GaloisElements(self):
+        """the Galois elements of GenRotationKeysPow2 (:391-417) in its order: for n = 1, 2, .. < N / 2 the left rotation 5^n and the right
+        rotation 5^(N / 2 - n), then the conjugation 2 N - 1 -- 2 (logN - 1) + 1 elements"""
+        N = self.contextQ.N
+        left = GenGaloisParams(N, 5)
+        right = GenGaloisParams(N, pow(5, -1, 2 * N))
+        out, n = [], 1
+        while n < N >> 1:
+            out += [left[n], right[n]]
+            n <<= 1
+        return out + [2 * N - 1]
+
+    def GenRotationKeysPow2(self, sk, sampler_bytes, uniform):
+        """GenRotationKeysPow2: returns {"left": {n: (element, key)}, "right": {n: (element, key)}, "conjugate": (element, key)}.
+        sampler_bytes = uint8 [2 (logN - 1) + 1, beta, N]; uniform = uint64 [2 (logN - 1) + 1, beta, |Q| + |P|, N], the evakey[i][1] of
+        every key in the order of Pow2GaloisElements (what NewUniformPoly drew: a key without them reveals the secret)."""
+        gens = self.Pow2GaloisElements()
+        rows, beta = len(self.contextQ.Modulus) + len(self.contextP.Modulus), self.beta
+        uniform = np.asarray(uniform, dtype=np.uint64)
+        if uniform.shape != (len(gens), beta, rows, self.contextQ.N):
+            raise LatticeRingError(3, "expected uniform polys of shape %s, got %s" % ((len(gens), beta, rows, self.contextQ.N), uniform.shape))
+        evks = []
+        for a in uniform:
+            img = np.zeros((2 * beta, rows, self.contextQ.N), dtype=np.uint64)
+            img[1::2] = a
+            evks.append(self.NewSwitchingKey().set(img))
+        self.GenRotationKeys(sk, gens, sampler_bytes, evks)
+        out = {"left": {}, "right": {}, "conjugate": (gens[-1], evks[-1])}
+        for i in range(len(gens) // 2):
+            out["left"][1 << i] = (gens[2 * i], evks[2 * i])
+            out["right"][1 << i] = (gens[2 * i + 1], evks[2 * i + 1])
+        return out
+
+    # the same with the randomness in device memory (pointers, e.g. a torch uint8 tensor's data_ptr()); stream-ordered
+    def GenSecretKeyDevice(self, bits_ptrs, skOut):
+        check(lib().lr_keygen_secret_key_device(self.h, C.c_void_p(bits_ptrs[0]), C.c_void_p(bits_ptrs[1]), skOut.batch, skOut.h))
+        return skOut
+
+    def GenPublicKeyDevice(self, sk, e_ptr, pk):
+        check(lib().lr_keygen_public_key_device(self.h, sk.h, C.c_void_p(e_ptr), pk[0].batch, pk[0].h, pk[1].h))
+        return pk
+
+    def GenSwitchingKeysDevice(self, skIn, skOut, e_ptr, evks):
+        check(lib().lr_keygen_switching_keys_device(self.h, skIn.h, skOut.h, C.c_void_p(e_ptr), len(evks), self._keys(evks)))
+        return evks
+
+    def GenRelinKeysDevice(self, sk, e_ptr, evks):
+        check(lib().lr_keygen_relin_keys_device(self.h, sk.h, len(evks), C.c_void_p(e_ptr), self._keys(evks)))
+        return evks
+
+    def GenRotationKeysDevice(self, sk, galois_elements, e_ptr, evks):
+        check(lib().lr_keygen_rotation_keys_device(self.h, sk.h, _u64(galois_elements), len(evks), C.c_void_p(e_ptr), self._keys(evks)))
+        return evks
+
+
+def NewKeyGenerator(contextQ, contextP, max_batch=1, options=None):  # ckks.NewKeyGenerator, ckks/keygen.go:79
+    return KeyGenerator(contextQ, contextP, max_batch, options)
+
+
 class BfvBatcher:
     """Merges the Mul and Relinearize calls of concurrent BFV evaluators -- the reference's own pooled workload: every task of
     examples/dbfv/psi/psi.go:215-233 calls evaluator.Mul and evaluator.Relinearize on one ciphertext pair -- into batched launches

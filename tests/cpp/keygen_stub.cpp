@@ -1,0 +1,90 @@
+// Stand-ins for the launchers of lr_keygen.hip, for the CPU-sanitizer build of the key generator's host side
+// (tests/test_host_keygen_sanitizers.py); the expansion it shares with the CKKS encryptor is served by ckks_encryptor_stub.cpp, which
+// stays as it is.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.  A stub counts its launch and touches the first and the
+// last byte of everything the real kernel would read or write at the addresses the launch names: "device" memory is malloc'ed at its
+// exact size, so a wrong size, stride, digit or key count in the host code is an AddressSanitizer report.
+#include <atomic>
+
+#include "lr_device.hpp"
+
+namespace lr {
+
+std::atomic<unsigned long long> g_keygen_skin_launches{0}, g_keygen_finish_launches{0}, g_keygen_pk_launches{0};
+
+namespace {
+thread_local volatile u64 t_sink;
+template <class T>
+void rd(const T *p, long long count) {
+    if (count <= 0) return;
+    t_sink = (u64)((const volatile unsigned char *)p)[0];
+    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
+}
+void wr(u64 *p, long long count) {
+    if (count <= 0) return;
+    p[0] = p[0];
+    p[count - 1] = p[count - 1];
+}
+}  // namespace
+
+hipError_t launch_keygen_skin(const KeygenSkInLaunch &L, int limbs, int keys, hipStream_t) {
+    if (limbs <= 0 || keys <= 0) return hipSuccess;
+    if (L.n < 2 || L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || limbs > kMaxLimbs || keys > kKeygenKeysPerLaunch) return hipErrorInvalidValue;
+    g_keygen_skin_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int k = 0; k < keys; ++k) {
+        if (!(L.gen[k] & 1u) || L.gen[k] >= 2u * (u32)L.n) return hipErrorInvalidValue;
+        for (int i = 0; i < limbs; ++i) {
+            rd(L.sk + k * L.sk_stride + (long long)i * L.n, L.n);
+            wr(L.out + k * L.out_stride + (long long)i * L.n, L.n);
+        }
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_keygen_powers(const KeygenPowersLaunch &L, int limbs, hipStream_t) {
+    if (limbs <= 0 || L.keys <= 0) return hipSuccess;
+    if (L.n < 2 || limbs > kMaxLimbs || L.first < 0) return hipErrorInvalidValue;
+    g_keygen_skin_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int i = 0; i < limbs; ++i) {
+        rd(L.sk + (long long)i * L.n, L.n);
+        for (int k = 0; k < L.keys; ++k) wr(L.out + k * L.out_stride + (long long)i * L.n, L.n);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_keygen_finish(const KeygenFinishLaunch &L, int rows, int keys, hipStream_t) {
+    if (rows <= 0 || keys <= 0) return hipSuccess;
+    if (L.n < 2 || rows > kMaxLimbs || keys > kKeygenKeysPerLaunch || L.beta < 1 || L.beta > kMaxLimbs || L.alpha < 1 || L.nQ < 1 || L.nQ > rows)
+        return hipErrorInvalidValue;
+    g_keygen_finish_launches.fetch_add(1);
+    rd(L.lp, rows);
+    for (int k = 0; k < keys; ++k)
+        for (int d = 0; d < L.beta; ++d)
+            for (int i = 0; i < rows; ++i) {
+                const long long row = (long long)i * L.n;
+                rd(L.e + (long long)(k * L.beta + d) * L.e_stride + row, L.n);
+                rd(L.key[k].base + (long long)(2 * d + 1) * L.key[k].stride + row, L.n);
+                rd(L.skout + k * L.skout_stride + row, L.n);
+                if (i >= d * L.alpha && i < (d + 1) * L.alpha && i < L.nQ) rd(L.skin + k * L.skin_stride + row, L.n);
+                wr(L.key[k].base + (long long)(2 * d) * L.key[k].stride + row, L.n);
+            }
+    return hipSuccess;
+}
+
+hipError_t launch_keygen_pk(const KeygenPkLaunch &L, int rows, int batch, hipStream_t) {
+    if (rows <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || rows > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    g_keygen_pk_launches.fetch_add(1);
+    rd(L.lp, rows);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < rows; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.sk + b * L.sk_stride + row, L.n);
+            rd(L.pk1 + b * L.pk1_stride + row, L.n);
+            wr(L.pk0 + b * L.pk0_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+}  // namespace lr
