@@ -721,6 +721,76 @@ int lr_keygen_relin_keys_device(lr_keygen *kg, const lr_poly *sk, int n_powers, 
 int lr_keygen_rotation_keys_device(lr_keygen *kg, const lr_poly *sk, const uint64_t *galois_elements, int n_keys, const void *e,
                                    lr_poly *const *evks);
 
+/* Collective key switching of dckks and dbfv for a batch of ciphertexts, device-resident, after the sampling: CKSProtocol.GenShare
+ * (dckks/keyswitching.go:62-94, dbfv/keyswitching.go:74-109), PCKSProtocol.GenShare (dckks/public_keyswitching.go:63-93,
+ * dbfv/public_keyswitching.go:111-148), and AggregateShares / KeySwitch of all four (dckks/keyswitching.go:99-108,
+ * dckks/public_keyswitching.go:99-113, dbfv/keyswitching.go:114-122, dbfv/public_keyswitching.go:154-165) as one n-ary fold.
+ * lr_collective owns what the four New*Protocol constructors build: NewFastBasisExtender(contextQ, contextP), three pool polys over Q||P
+ * for max_batch ciphertexts (tmp, share0tmp, share1tmp), MForm(P mod q_j), the matrixTernaryMontgomery rows of every limb and a pinned
+ * staging buffer with its event.  ctxP is required (all four protocols divide by P): NULL is LR_ERR_ARG.  max_batch outside 1 .. 65535,
+ * N < 8 (a bit plane is N / 8 bytes) and a ctxP on another device, of another N or on another stream are LR_ERR_ARG.  The work is ordered
+ * on ctxQ's stream.
+ * The randomness is exactly the encryptors': e, e0, e1 [batch][N] bytes (magnitude in bits 0-6, sign in bit 7; the residue is
+ * ring/gaussianSampler.go:247: sign 1 -> coeff, sign 0 -> q_j - coeff), u_coeff_bits, u_sign_bits [batch][N / 8] (sampleTernary at
+ * p = 0.5) -- N bytes per CKS share, N / 4 + 2 N per PCKS share.  The smudging sampler and the regular one differ only in which bytes the
+ * caller draws.  A magnitude is at most 127: with the reference's bound int(6 sigma) that is sigma_smudge <= 21 (the reference's tests
+ * use 6.36, its examples 3.19); larger magnitudes are outside this interface's domain.
+ * Keys: polys of ctxQ in NTT + Montgomery form over Q||P in contextQP's order (|Q| limbs suffice for sk, sk_in and sk_out), of batch 1 or
+ * the call's batch.  CKKS c1 and shares: NTT domain, at least level + 1 limbs; limbs above level are not touched.  BFV c1 and shares:
+ * coefficient domain over all of Q.  Both of the call's batch.
+ * lr_collective_ckks_cks_share: Sub over Q (:64), MulCoeffsMontgomeryLvl (:74), MulScalarBigintLvl by P (:76), SampleNTT over Q||P and
+ *   AddLvl (:79-80), hP = the rows of P of the transformed noise (:82-88), ModDownSplitedNTTPQ(level) (:90).  A share at every level.
+ *   Default shape: the noise is expanded on limbs 0 .. level and on the rows of P only, and only the rows of Q are transformed -- the
+ *   ModDown transforms hP straight back (ring_basis_extension.go:199-201), so hP is the noise itself with its q_j of (0, sign 0) reduced
+ *   to 0 -- then one pass CRed(MRed(MRed(c1, CRed(sk_in + q - sk_out)), MForm(P mod q_j)) + NTT(e)), then the ModDown.
+ * lr_collective_bfv_cks_share (dbfv/keyswitching.go:76-105): NTT(c1), the same products, InvNTT, Sample over Q||P and Add over Q, hP = the
+ *   sampled rows of P, ModDownSplitedPQ.  (0, sign 0) leaves the residue p_j itself in hP; the default shape writes 0 there, which changes
+ *   no bit of the ModDown's output (pinned on the CPU, tests/test_oracle_collective.py); the call-by-call shape feeds p_j literally.
+ * lr_collective_ckks_pcks_share (dckks/public_keyswitching.go:68-90): u -> NTT over Q||P, the products with pk0 and pk1, SampleNTT + Add
+ *   of e0 and e1, two ModDownNTTPQ(level), MulCoeffsMontgomeryAndAddLvl(c1, sk) onto out0.  Default shape: everything in front of the
+ *   ModDowns on limbs 0 .. level and the rows of P only (the rows a ModDownNTTPQ(level) reads).
+ * lr_collective_bfv_pcks_share (dbfv/public_keyswitching.go:116-144): pkEncryptor.encrypt's steps through P (products, InvNTT,
+ *   SampleAndAdd, two ModDownPQ(|Q| - 1)), then out0 += InvNTT(MRed(NTT(c1), sk)).
+ * lr_collective_aggregate: acc = shares[0]; acc = CRed(acc + shares[k]) for k = 1 .. n_shares - 1 in this order; out = CRed(base + acc)
+ *   if base is not NULL, else acc; over limbs 0 .. level.  n_shares = 1 and base = NULL is KeySwitch's Copy, base = ct[0] its Add.  One
+ *   pass reads n_shares (+ 1) rows and writes one; more than 32 shares run as further passes over the running sum.  out may be base or
+ *   any of the shares (AggregateShares(a, b, a)); a partial overlap is LR_ERR_ARG.  Every poly has the same batch, at most max_batch.
+ * Refusals: LR_ERR_ARG: a null argument, a poly of another context, an output of a share call that shares memory with an input or with
+ * the other output, ctxQ and ctxP on different streams at the time of a call; LR_ERR_SHAPE: batch < 1 or > max_batch, a poly with too few
+ * limbs, a poly whose batch differs from the call's (where batch 1 is not allowed), a level outside 0 .. |Q| - 1, n_shares < 1;
+ * LR_ERR_UNSUPPORTED, at creation: more than 64 limbs in Q||P.
+ * The host forms stage the bytes through the pinned buffer: the caller's arrays are free on return, the call is asynchronous.  The
+ * _device forms take the same bytes in device memory: kernels only on ctxQ's stream, no host copy, no synchronisation.
+ * lr_options::no_epilogue selects the reference's call-by-call shape (one launch per Context call, every line over the rows the
+ * reference walks); both shapes give the same bits. */
+typedef struct lr_collective lr_collective;
+int lr_collective_create(lr_context *ctxQ, lr_context *ctxP, int max_batch, lr_collective **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_collective_create_ex(lr_context *ctxQ, lr_context *ctxP, int max_batch, const lr_options *opt, lr_collective **out);
+int lr_collective_destroy(lr_collective *col);
+int lr_collective_ckks_cks_share(lr_collective *col, int level, const lr_poly *sk_in, const lr_poly *sk_out, const lr_poly *c1,
+                                 const uint8_t *e, int batch, lr_poly *share_out);
+int lr_collective_bfv_cks_share(lr_collective *col, const lr_poly *sk_in, const lr_poly *sk_out, const lr_poly *c1, const uint8_t *e,
+                                int batch, lr_poly *share_out);
+int lr_collective_ckks_pcks_share(lr_collective *col, int level, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1,
+                                  const lr_poly *c1, const uint8_t *u_coeff_bits, const uint8_t *u_sign_bits, const uint8_t *e0,
+                                  const uint8_t *e1, int batch, lr_poly *out0, lr_poly *out1);
+int lr_collective_bfv_pcks_share(lr_collective *col, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1,
+                                 const uint8_t *u_coeff_bits, const uint8_t *u_sign_bits, const uint8_t *e0, const uint8_t *e1, int batch,
+                                 lr_poly *out0, lr_poly *out1);
+int lr_collective_ckks_cks_share_device(lr_collective *col, int level, const lr_poly *sk_in, const lr_poly *sk_out, const lr_poly *c1,
+                                        const void *e, int batch, lr_poly *share_out);
+int lr_collective_bfv_cks_share_device(lr_collective *col, const lr_poly *sk_in, const lr_poly *sk_out, const lr_poly *c1, const void *e,
+                                       int batch, lr_poly *share_out);
+int lr_collective_ckks_pcks_share_device(lr_collective *col, int level, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1,
+                                         const lr_poly *c1, const void *u_coeff_bits, const void *u_sign_bits, const void *e0,
+                                         const void *e1, int batch, lr_poly *out0, lr_poly *out1);
+int lr_collective_bfv_pcks_share_device(lr_collective *col, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1,
+                                        const void *u_coeff_bits, const void *u_sign_bits, const void *e0, const void *e1, int batch,
+                                        lr_poly *out0, lr_poly *out1);
+int lr_collective_aggregate(lr_collective *col, int level, const lr_poly *base /* may be NULL */, const lr_poly *const *shares, int n_shares,
+                            lr_poly *out);
+
 /* ------------------------------------------------------------------ multi-device ------ */
 /* a batch of independent ciphertexts shards across the GPUs of a node by contiguous blocks (replicated contexts, tables
  * and keys, created per device with lr_context_create(..., device, ...)); nothing crosses devices but finished results.  The reference's

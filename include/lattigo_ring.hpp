@@ -400,4 +400,61 @@ class KeyGenerator {
     lr_keygen *h_ = nullptr;
 };
 
+// CKSProtocol and PCKSProtocol of dckks and dbfv (dckks/keyswitching.go, dckks/public_keyswitching.go and their dbfv twins) for batches of
+// ciphertexts, after the sampling: the randomness in BfvEncryptor's compact form, keys over Q||P in NTT + Montgomery form; CKKS ciphertexts
+// and shares in the NTT domain over limbs 0 .. level, BFV ones in the coefficient domain over Q
+class Collective {
+  public:
+    Collective(const Context *contextQ, const Context *contextP, int max_batch = 1, const lr_options *options = nullptr) {
+        check(lr_collective_create_ex(contextQ->handle(), contextP ? contextP->handle() : nullptr, max_batch, options, &h_));
+    }
+    ~Collective() { lr_collective_destroy(h_); }
+    Collective(const Collective &) = delete;
+    Collective &operator=(const Collective &) = delete;
+    void CkksCksShare(int level, const Poly *sk_in, const Poly *sk_out, const Poly *c1, const std::vector<uint8_t> &e, int batch, Poly *share) {
+        check(lr_collective_ckks_cks_share(h_, level, sk_in->handle(), sk_out->handle(), c1->handle(), e.data(), batch, share->handle()));
+    }
+    void BfvCksShare(const Poly *sk_in, const Poly *sk_out, const Poly *c1, const std::vector<uint8_t> &e, int batch, Poly *share) {
+        check(lr_collective_bfv_cks_share(h_, sk_in->handle(), sk_out->handle(), c1->handle(), e.data(), batch, share->handle()));
+    }
+    void CkksPcksShare(int level, const Poly *sk, const Poly *pk0, const Poly *pk1, const Poly *c1, const std::vector<uint8_t> &u_coeff_bits,
+                       const std::vector<uint8_t> &u_sign_bits, const std::vector<uint8_t> &e0, const std::vector<uint8_t> &e1, int batch, Poly *out0,
+                       Poly *out1) {
+        check(lr_collective_ckks_pcks_share(h_, level, sk->handle(), pk0->handle(), pk1->handle(), c1->handle(), u_coeff_bits.data(),
+                                            u_sign_bits.data(), e0.data(), e1.data(), batch, out0->handle(), out1->handle()));
+    }
+    void BfvPcksShare(const Poly *sk, const Poly *pk0, const Poly *pk1, const Poly *c1, const std::vector<uint8_t> &u_coeff_bits,
+                      const std::vector<uint8_t> &u_sign_bits, const std::vector<uint8_t> &e0, const std::vector<uint8_t> &e1, int batch, Poly *out0,
+                      Poly *out1) {
+        check(lr_collective_bfv_pcks_share(h_, sk->handle(), pk0->handle(), pk1->handle(), c1->handle(), u_coeff_bits.data(), u_sign_bits.data(),
+                                           e0.data(), e1.data(), batch, out0->handle(), out1->handle()));
+    }
+    // AggregateShares over all parties and, with base = ct[0], KeySwitch's Add; one share and no base is its Copy
+    void Aggregate(int level, const Poly *base, const std::vector<const Poly *> &shares, Poly *out) {
+        std::vector<const lr_poly *> hs;
+        for (const Poly *s : shares) hs.push_back(s->handle());
+        check(lr_collective_aggregate(h_, level, base ? base->handle() : nullptr, hs.data(), (int)hs.size(), out->handle()));
+    }
+    // the same bytes in device memory: stream-ordered, no host copy
+    void CkksCksShareDevice(int level, const Poly *sk_in, const Poly *sk_out, const Poly *c1, const void *e, int batch, Poly *share) {
+        check(lr_collective_ckks_cks_share_device(h_, level, sk_in->handle(), sk_out->handle(), c1->handle(), e, batch, share->handle()));
+    }
+    void BfvCksShareDevice(const Poly *sk_in, const Poly *sk_out, const Poly *c1, const void *e, int batch, Poly *share) {
+        check(lr_collective_bfv_cks_share_device(h_, sk_in->handle(), sk_out->handle(), c1->handle(), e, batch, share->handle()));
+    }
+    void CkksPcksShareDevice(int level, const Poly *sk, const Poly *pk0, const Poly *pk1, const Poly *c1, const void *u_coeff_bits,
+                             const void *u_sign_bits, const void *e0, const void *e1, int batch, Poly *out0, Poly *out1) {
+        check(lr_collective_ckks_pcks_share_device(h_, level, sk->handle(), pk0->handle(), pk1->handle(), c1->handle(), u_coeff_bits, u_sign_bits,
+                                                   e0, e1, batch, out0->handle(), out1->handle()));
+    }
+    void BfvPcksShareDevice(const Poly *sk, const Poly *pk0, const Poly *pk1, const Poly *c1, const void *u_coeff_bits, const void *u_sign_bits,
+                            const void *e0, const void *e1, int batch, Poly *out0, Poly *out1) {
+        check(lr_collective_bfv_pcks_share_device(h_, sk->handle(), pk0->handle(), pk1->handle(), c1->handle(), u_coeff_bits, u_sign_bits, e0, e1,
+                                                  batch, out0->handle(), out1->handle()));
+    }
+
+  private:
+    lr_collective *h_ = nullptr;
+};
+
 }  // namespace ring

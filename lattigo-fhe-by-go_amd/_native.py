@@ -179,6 +179,18 @@ SYMBOLS = {
     "lr_keygen_switching_keys_device": [vp, vp, vp, vp, i32, C.POINTER(vp)],
     "lr_keygen_relin_keys_device": [vp, vp, i32, vp, C.POINTER(vp)],
     "lr_keygen_rotation_keys_device": [vp, vp, u64p, i32, vp, C.POINTER(vp)],
+    "lr_collective_create": [vp, vp, i32, C.POINTER(vp)],
+    "lr_collective_create_ex": [vp, vp, i32, vp, C.POINTER(vp)],
+    "lr_collective_destroy": [vp],
+    "lr_collective_ckks_cks_share": [vp, i32, vp, vp, vp, vp, i32, vp],
+    "lr_collective_bfv_cks_share": [vp, vp, vp, vp, vp, i32, vp],
+    "lr_collective_ckks_pcks_share": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_collective_bfv_pcks_share": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_collective_ckks_cks_share_device": [vp, i32, vp, vp, vp, vp, i32, vp],
+    "lr_collective_bfv_cks_share_device": [vp, vp, vp, vp, vp, i32, vp],
+    "lr_collective_ckks_pcks_share_device": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_collective_bfv_pcks_share_device": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_collective_aggregate": [vp, i32, vp, C.POINTER(vp), i32, vp],
     "lr_bfv_decryptor_create": [vp, i32, C.POINTER(vp)],
     "lr_bfv_decryptor_destroy": [vp],
     "lr_bfv_decrypt": [vp, C.POINTER(vp), i32, vp, vp, i32],

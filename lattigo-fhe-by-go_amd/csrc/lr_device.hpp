@@ -502,6 +502,46 @@ struct KeygenPkLaunch {
 };
 hipError_t launch_keygen_pk(const KeygenPkLaunch &L, int rows, int batch, hipStream_t stream);
 
+// ---- dckks / dbfv collective key switching (lr_collective.hip): CKSProtocol, PCKSProtocol, AggregateShares, KeySwitch ----
+constexpr int kFoldSharesPerLaunch = 32;   // shares whose addresses and strides travel in one launch's kernel arguments
+// out = CRed(MRed(MRed(c1, CRed(sk_in + q - sk_out)), MForm(P mod q)) + e) over the rows of Q in the NTT domain: Sub, MulCoeffsMontgomery,
+// MulScalarBigint and Add of genShareDelta (dckks/keyswitching.go:64-80) in one pass; e == nullptr: no addend (dbfv/keyswitching.go:76-90,
+// whose noise arrives after the inverse transform)
+struct CksShareLaunch {
+    const u64 *c1, *sk_in, *sk_out, *e;
+    u64 *out;
+    long long c1_stride, sk_in_stride, sk_out_stride, e_stride, out_stride;   // between batch polys (keys: 0 = broadcast)
+    int n;
+    LimbScalars pmont;                                                         // MForm(P mod q) per limb of Q
+    const LimbParams *lp;
+};
+hipError_t launch_cks_share(const CksShareLaunch &L, int limbs, int batch, hipStream_t stream);
+// out0 = CRed(out0 + MRed(c1, sk)): MulCoeffsMontgomeryAndAddLvl at the end of PCKSProtocol.GenShare (dckks/public_keyswitching.go:90)
+struct PcksAddendLaunch {
+    const u64 *c1, *sk;
+    u64 *out0;
+    long long c1_stride, sk_stride, out0_stride;
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_pcks_addend(const PcksAddendLaunch &L, int limbs, int batch, hipStream_t stream);
+// acc = share[0]; acc = CRed(acc + share[k]) for k = 1 .. count - 1 in this order; out = base ? CRed(base + acc) : acc.  Element-wise: out
+// may be base or any share as a whole poly.
+struct FoldShareRef {
+    const u64 *base;
+    long long stride;
+};
+struct FoldLaunch {
+    FoldShareRef share[kFoldSharesPerLaunch];
+    int count;
+    const u64 *base;                                                           // nullptr: none
+    u64 *out;
+    long long base_stride, out_stride;
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_fold(const FoldLaunch &L, int limbs, int batch, hipStream_t stream);
+
 // ---- ckks.Encoder (lr_ckks_encode.hip): Encode / Decode of ckks/encoder.go for a batch of plaintexts ----
 struct Cplx { double re, im; };                 // a complex128 as Go lays it out
 constexpr int kCkksFusedMaxLogSlots = 13;       // the fused kernels hold 16 * slots bytes in one CU's LDS: 128 KiB of the 160

@@ -1208,6 +1208,102 @@ def NewKeyGenerator(contextQ, contextP, max_batch=1, options=None):  # ckks.NewK
     return KeyGenerator(contextQ, contextP, max_batch, options)
 
 
+class Collective:
+    """CKSProtocol and PCKSProtocol of dckks and dbfv (dckks/keyswitching.go, dckks/public_keyswitching.go and their dbfv twins) for a
+    batch of ciphertexts on the device (lr_collective), after the sampling.  The randomness is the encryptors' compact form: e = uint8
+    [batch, N] per sampled poly, magnitude in the low 7 bits and sign in bit 7 (the smudging sampler and the regular one differ only in the
+    bytes drawn); u_bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each.  Keys are Poly of contextQ over Q||P in NTT + Montgomery
+    form (the secret keys are read on the rows of Q), batch 1 or the call's.  CKKS c1 and shares: NTT domain, at least level + 1 limbs;
+    BFV c1 and shares: coefficient domain over Q.  The batch of a call is that of its output."""
+
+    def __init__(self, contextQ, contextP, max_batch=1, options=None):
+        self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
+        h = C.c_void_p()
+        hP = None if contextP is None else contextP.h
+        if options is None:
+            check(lib().lr_collective_create(contextQ.h, hP, max_batch, C.byref(h)))
+        else:
+            check(lib().lr_collective_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().lr_collective_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _bytes(self, a, batch, per_poly):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.size != batch * per_poly:
+            raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
+        return a
+
+    def _pcks_bytes(self, u_bits, e, batch):
+        N = self.contextQ.N
+        arrays = [self._bytes(u_bits[0], batch, N // 8), self._bytes(u_bits[1], batch, N // 8), self._bytes(e[0], batch, N),
+                  self._bytes(e[1], batch, N)]
+        return arrays, [a.ctypes.data_as(C.c_void_p) for a in arrays]
+
+    def CkksCksShare(self, skInput, skOutput, c1, e, shareOut, level):  # CKSProtocol.GenShare, dckks/keyswitching.go:62
+        eb = self._bytes(e, shareOut.batch, self.contextQ.N)
+        check(lib().lr_collective_ckks_cks_share(self.h, level, skInput.h, skOutput.h, c1.h, eb.ctypes.data_as(C.c_void_p), shareOut.batch,
+                                                 shareOut.h))
+        return shareOut
+
+    def BfvCksShare(self, skInput, skOutput, c1, e, shareOut):  # dbfv/keyswitching.go:74
+        eb = self._bytes(e, shareOut.batch, self.contextQ.N)
+        check(lib().lr_collective_bfv_cks_share(self.h, skInput.h, skOutput.h, c1.h, eb.ctypes.data_as(C.c_void_p), shareOut.batch, shareOut.h))
+        return shareOut
+
+    def CkksPcksShare(self, sk, pk, c1, u_bits, e, shareOut, level):  # PCKSProtocol.GenShare, dckks/public_keyswitching.go:63
+        batch = shareOut[0].batch
+        keep, p = self._pcks_bytes(u_bits, e, batch)
+        check(lib().lr_collective_ckks_pcks_share(self.h, level, sk.h, pk[0].h, pk[1].h, c1.h, p[0], p[1], p[2], p[3], batch, shareOut[0].h,
+                                                  shareOut[1].h))
+        return shareOut
+
+    def BfvPcksShare(self, sk, pk, c1, u_bits, e, shareOut):  # dbfv/public_keyswitching.go:111
+        batch = shareOut[0].batch
+        keep, p = self._pcks_bytes(u_bits, e, batch)
+        check(lib().lr_collective_bfv_pcks_share(self.h, sk.h, pk[0].h, pk[1].h, c1.h, p[0], p[1], p[2], p[3], batch, shareOut[0].h,
+                                                 shareOut[1].h))
+        return shareOut
+
+    def Aggregate(self, shares, out, level, base=None):
+        """AggregateShares over all the parties' shares in their order and, with base = ct[0], KeySwitch's Add; one share and no base is
+        KeySwitch's Copy.  out may be base or one of the shares."""
+        hs = (C.c_void_p * len(shares))(*[s.h.value for s in shares])
+        check(lib().lr_collective_aggregate(self.h, level, None if base is None else base.h, hs, len(shares), out.h))
+        return out
+
+    # the same with the randomness in device memory (pointers, e.g. a torch uint8 tensor's data_ptr()); stream-ordered
+    def CkksCksShareDevice(self, skInput, skOutput, c1, e_ptr, shareOut, level):
+        check(lib().lr_collective_ckks_cks_share_device(self.h, level, skInput.h, skOutput.h, c1.h, C.c_void_p(e_ptr), shareOut.batch, shareOut.h))
+        return shareOut
+
+    def BfvCksShareDevice(self, skInput, skOutput, c1, e_ptr, shareOut):
+        check(lib().lr_collective_bfv_cks_share_device(self.h, skInput.h, skOutput.h, c1.h, C.c_void_p(e_ptr), shareOut.batch, shareOut.h))
+        return shareOut
+
+    def CkksPcksShareDevice(self, sk, pk, c1, u_bits_ptrs, e_ptrs, shareOut, level):
+        v = C.c_void_p
+        check(lib().lr_collective_ckks_pcks_share_device(self.h, level, sk.h, pk[0].h, pk[1].h, c1.h, v(u_bits_ptrs[0]), v(u_bits_ptrs[1]),
+                                                         v(e_ptrs[0]), v(e_ptrs[1]), shareOut[0].batch, shareOut[0].h, shareOut[1].h))
+        return shareOut
+
+    def BfvPcksShareDevice(self, sk, pk, c1, u_bits_ptrs, e_ptrs, shareOut):
+        v = C.c_void_p
+        check(lib().lr_collective_bfv_pcks_share_device(self.h, sk.h, pk[0].h, pk[1].h, c1.h, v(u_bits_ptrs[0]), v(u_bits_ptrs[1]),
+                                                        v(e_ptrs[0]), v(e_ptrs[1]), shareOut[0].batch, shareOut[0].h, shareOut[1].h))
+        return shareOut
+
+
+def NewCollective(contextQ, contextP, max_batch=1, options=None):  # NewCKSProtocol / NewPCKSProtocol of dckks and dbfv
+    return Collective(contextQ, contextP, max_batch, options)
+
+
 class BfvBatcher:
     """Merges the Mul and Relinearize calls of concurrent BFV evaluators -- the reference's own pooled workload: every task of
     examples/dbfv/psi/psi.go:215-233 calls evaluator.Mul and evaluator.Relinearize on one ciphertext pair -- into batched launches

@@ -1,0 +1,77 @@
+// Stand-ins for the launchers of lr_collective.hip, for the CPU-sanitizer build of the collective handle's host side
+// (tests/test_host_collective_sanitizers.py); the expansions and the pk pass it shares with the encryptors are served by
+// ckks_encryptor_stub.cpp and bfv_encryptor_stub.cpp, which stay as they are.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives
+// here.  A stub counts its launch and touches the first and the last byte of everything the real kernel would read or write at the
+// addresses the launch names: "device" memory is malloc'ed at its exact size, so a wrong size, stride, level or share count in the host
+// code is an AddressSanitizer report.
+#include <atomic>
+
+#include "lr_device.hpp"
+
+namespace lr {
+
+std::atomic<unsigned long long> g_cks_share_launches{0}, g_pcks_addend_launches{0}, g_fold_launches{0};
+
+namespace {
+thread_local volatile u64 t_sink;
+template <class T>
+void rd(const T *p, long long count) {
+    if (count <= 0) return;
+    t_sink = (u64)((const volatile unsigned char *)p)[0];
+    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
+}
+void wr(u64 *p, long long count) {
+    if (count <= 0) return;
+    p[0] = p[0];
+    p[count - 1] = p[count - 1];
+}
+}  // namespace
+
+hipError_t launch_cks_share(const CksShareLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    g_cks_share_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.c1 + b * L.c1_stride + row, L.n);
+            rd(L.sk_in + b * L.sk_in_stride + row, L.n);
+            rd(L.sk_out + b * L.sk_out_stride + row, L.n);
+            if (L.e) rd(L.e + b * L.e_stride + row, L.n);
+            wr(L.out + b * L.out_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+hipError_t launch_pcks_addend(const PcksAddendLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    g_pcks_addend_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.c1 + b * L.c1_stride + row, L.n);
+            rd(L.sk + b * L.sk_stride + row, L.n);
+            wr(L.out0 + b * L.out0_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+hipError_t launch_fold(const FoldLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535 || L.count < 1 || L.count > kFoldSharesPerLaunch) return hipErrorInvalidValue;
+    g_fold_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            for (int k = 0; k < L.count; ++k) rd(L.share[k].base + b * L.share[k].stride + row, L.n);
+            if (L.base) rd(L.base + b * L.base_stride + row, L.n);
+            wr(L.out + b * L.out_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+}  // namespace lr
