@@ -4,53 +4,25 @@
 // The randomness arrives in the compact form of the encryptors (lr_bfv_encryptor).  Kernels: lr_collective.hip, the expansions of
 // lr_ckks_encrypt.hip and lr_bfv_encrypt.hip, launch_mul2 and launch_ckks_pk_fast where the lines are pkEncryptor.encrypt's.
 // The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// it calls have a stand-in of their own (tests/cpp/collective_stub.cpp).
-#include "lr_host.hpp"
+// it calls have a stand-in of their own (tests/cpp/collective_stub.cpp).  What it shares with the encryptors and lr_keygen.cpp is
+// lr_qp_handle.hpp.
+#include "lr_qp_handle.hpp"
 
-// what the four New*Protocol constructors build (dckks/keyswitching.go:28-49, dckks/public_keyswitching.go:28-49 and their dbfv twins),
-// plus the staging of the host-randomness entry points
-struct lr_collective {
-    int device = 0;
-    lr_context *cQ = nullptr, *cP = nullptr;
+// what the four New*Protocol constructors build (dckks/keyswitching.go:28-49, dckks/public_keyswitching.go:28-49 and their dbfv twins);
+// the contexts, the scalars and the staging of the host-randomness entry points (max_batch * (N / 4 + 2 N) bytes) are QpHandle's
+struct lr_collective : lr_host::QpHandle {
     lr_bext *bext = nullptr;                  // NewFastBasisExtender(contextQ, contextP), owned
-    int nQ = 0, nP = 0, max_batch = 0;
-    bool call_by_call = false;                // Options::no_epilogue: the reference's call-by-call shape
-    LimbScalars one, minus_one;               // matrixTernaryMontgomery rows 1 and 2 (ring/ring_context.go:119-122) per limb of Q||P
-    LimbScalars pmont;                        // MForm(P mod q_j) per limb of Q: MulScalarBigint's scalar (ring/ring.go:547)
-    LimbParams *d_lp = nullptr;               // the limb constants of contextQP: contextQ's, then contextP's
     u64 *d_pool = nullptr;                    // tmp, share0tmp, share1tmp: three polys over Q||P for max_batch ciphertexts
     u64 *d_zero = nullptr;                    // one poly of zeros over Q||P: the plaintext operand of launch_ckks_pk_fast
-    unsigned char *d_rand = nullptr;          // the host-randomness entry points' bytes on the device ...
-    unsigned char *h_rand = nullptr;          // ... and pinned: max_batch * (N / 4 + 2 N)
-    hipEvent_t staged = nullptr;              // the last copy out of h_rand: the next call waits for it before it refills the buffer
     ~lr_collective() {
-        for (void *p : {(void *)d_lp, (void *)d_pool, (void *)d_zero, (void *)d_rand})
+        for (void *p : {(void *)d_pool, (void *)d_zero})
             if (p) (void)hipFree(p);
-        if (h_rand) (void)hipHostFree(h_rand);
-        if (staged) (void)hipEventDestroy(staged);
         if (bext) lr_bext_destroy(bext);
     }
 };
 
 namespace lr_host {
 namespace {
-
-long long key_stride(const lr_poly *p, int batch) { return p->batch == 1 && batch > 1 ? 0 : p->stride(); }
-
-// a poly of the handle's contextQ with at least `limbs` limbs and the call's batch (or, where allowed, one poly for the whole batch)
-int check_poly(const lr_collective *h, const lr_poly *p, int limbs, int batch, bool broadcast, const char *what) {
-    if (p->ctx != h->cQ) return fail(LR_ERR_ARG, std::string("collective: ") + what + " belongs to another context");
-    if (p->N != h->cQ->h.N || p->limbs < limbs) return fail(LR_ERR_SHAPE, std::string("collective: ") + what + " has too few limbs");
-    if (p->batch != batch && !(broadcast && p->batch == 1)) return fail(LR_ERR_SHAPE, std::string("collective: batch differs from the batch of ") + what);
-    return LR_OK;
-}
-
-// the words of two polys overlap: an output that is, or lies inside, an input
-bool overlap(const lr_poly *a, const lr_poly *b) {
-    const u64 *a1 = a->d + (long long)(a->batch - 1) * a->stride() + (long long)a->alloc_limbs * (long long)a->N;
-    const u64 *b1 = b->d + (long long)(b->batch - 1) * b->stride() + (long long)b->alloc_limbs * (long long)b->N;
-    return a->d < b1 && b->d < a1;
-}
 
 // the same words, poly for poly: what an element-wise pass may read and write at once
 bool same_poly(const lr_poly *a, const lr_poly *b) { return a->d == b->d && a->batch == b->batch && (a->batch == 1 || a->stride() == b->stride()); }
@@ -72,16 +44,6 @@ int check_outputs(const lr_poly *const *outs, int n_outs, const lr_poly *const *
     return LR_OK;
 }
 
-// the three pool polys of a call, back to back: [3][batch][|Q| + |P|][N]
-struct Pools {
-    u64 *p[3];
-    long long stride, part;
-};
-Pools pools_of(const lr_collective *h, int batch) {
-    const long long n = (long long)h->cQ->h.N, s = (long long)(h->nQ + h->nP) * n;
-    return Pools{{h->d_pool, h->d_pool + batch * s, h->d_pool + 2 * batch * s}, s, batch * s};
-}
-
 // the rows of Q||P a call at `level` reads: limbs 0 .. level of Q and the rows of P; one run of rows at the top level, two below it
 struct Span { int row0, count; };
 int spans_of(const lr_collective *h, int level, Span s[2]) {
@@ -94,83 +56,19 @@ int spans_of(const lr_collective *h, int level, Span s[2]) {
     return 2;
 }
 
-LimbScalars from_row(const LimbScalars &v, int row0) {
-    LimbScalars r;
-    std::memset(&r, 0, sizeof r);
-    for (int i = row0; i < kMaxLimbs; ++i) r.v[i - row0] = v.v[i];
-    return r;
-}
-
-// one Context call of contextQP on rows inside the pools: the Q rows under contextQ, the P rows under contextP
-int ewise_qp(lr_collective *h, int op, int batch, const u64 *a, long long a_stride, const u64 *b, long long b_stride, u64 *out,
-             long long out_stride) {
-    const long long offP = (long long)h->nQ * (long long)h->cQ->h.N;
-    LR_TRY(run_ewise(h->cQ, op, h->nQ, batch, a, a_stride, b, b_stride, out, out_stride, nullptr));
-    return run_ewise(h->cP, op, h->nP, batch, a + offP, a_stride, b ? b + offP : nullptr, b_stride, out + offP, out_stride, nullptr);
-}
-
 // Context.NTT / InvNTT in place on `items` pool polys: limbs 0 .. level under contextQ, the rows of P under contextP
 int ntt_rows(lr_collective *h, bool inverse, int level, u64 *p, long long stride, int items) {
-    LR_TRY(run_ntt(h->cQ, inverse, Rows{p, stride, 0, 1}, Rows{p, stride, 0, 1}, 0, 1, level + 1, items));
-    return run_ntt(h->cP, inverse, Rows{p, stride, h->nQ, 1}, Rows{p, stride, h->nQ, 1}, 0, 1, h->nP, items);
+    return ntt_qp(h, true, inverse, level + 1, items, p, stride, p, stride);
 }
 
-// SampleTernaryMontgomery and / or KYSampler.Sample as the forward transform's operands (the q of (0, sign 0) written as 0) on the rows a
-// call at `level` reads: `ternary` + `noises` parts of `batch` polys from `out` on, part_stride apart
+// SampleTernaryMontgomery and / or KYSampler.Sample as the forward transform's operands on the rows a call at `level` reads: `ternary` +
+// `noises` parts of `batch` polys from `out` on, part_stride apart
 int expand(lr_collective *h, int level, int ternary, const unsigned char *u_coeff, const unsigned char *u_sign, int noises,
            const unsigned char *e0, const unsigned char *e1, u64 *out, long long stride, long long part, int batch) {
     Span s[2];
     const int n_spans = spans_of(h, level, s);
-    for (int k = 0; k < n_spans; ++k) {
-        CkksExpandLaunch X;
-        std::memset(&X, 0, sizeof X);
-        X.coeff_bits = u_coeff;
-        X.sign_bits = u_sign;
-        X.e[0] = e0;
-        X.e[1] = e1;
-        X.out = out + (long long)s[k].row0 * (long long)h->cQ->h.N;
-        X.out_stride = stride;
-        X.part_stride = part;
-        X.n = (int)h->cQ->h.N;
-        X.ternary = ternary;
-        X.noises = noises;
-        X.one = from_row(h->one, s[k].row0);
-        X.minus_one = from_row(h->minus_one, s[k].row0);
-        X.lp = h->d_lp + s[k].row0;
-        LR_HIP(launch_ckks_expand(X, s[k].count, batch, h->cQ->stream));
-    }
-    return LR_OK;
-}
-
-// KYSampler.Sample into a pool poly over all of Q||P (add = 0, the residue q_j of (0, sign 0) as the reference stores it), or
-// SampleAndAdd / Sample + Context.Add on `comps` pool polys (add = 1) over rows 0 .. rows - 1
-int noise(lr_collective *h, int add, int comps, const unsigned char *const *eb, u64 *const *x, long long stride, int rows, int batch) {
-    NoiseLaunch L;
-    std::memset(&L, 0, sizeof L);
-    for (int k = 0; k < comps; ++k) {
-        L.x[k] = add ? x[k] : nullptr;
-        L.out[k] = x[k];
-        L.x_stride[k] = L.out_stride[k] = stride;
-        L.e[k] = eb[k];
-    }
-    L.n = (int)h->cQ->h.N;
-    L.add = add;
-    L.lp = h->d_lp;
-    LR_HIP(launch_bfv_noise(L, comps, rows, batch, h->cQ->stream));
-    return LR_OK;
-}
-
-// the caller's bytes through the pinned buffer to the device, pieces one behind the other; the caller's arrays are free on return
-int stage_random(lr_collective *h, const unsigned char *const *src, const size_t *bytes, int pieces, const unsigned char **dev) {
-    LR_HIP(hipEventSynchronize(h->staged));               // the copy of the call before has left the pinned buffer
-    size_t off = 0;
-    for (int i = 0; i < pieces; ++i) {
-        std::memcpy(h->h_rand + off, src[i], bytes[i]);
-        dev[i] = h->d_rand + off;
-        off += bytes[i];
-    }
-    LR_HIP(hipMemcpyAsync(h->d_rand, h->h_rand, off, hipMemcpyHostToDevice, h->cQ->stream));
-    LR_HIP(hipEventRecord(h->staged, h->cQ->stream));
+    for (int k = 0; k < n_spans; ++k)
+        LR_TRY(expand_qp(h, s[k].row0, s[k].count, ternary, u_coeff, u_sign, noises, e0, e1, out, stride, part, batch));
     return LR_OK;
 }
 
@@ -200,10 +98,10 @@ int delta_product(lr_collective *h, int level, const u64 *x, long long x_stride,
 
 int check_cks(const lr_collective *h, int level, const lr_poly *sk_in, const lr_poly *sk_out, const lr_poly *c1, int batch, const lr_poly *share) {
     LR_TRY(check_call(h, level, batch));
-    LR_TRY(check_poly(h, sk_in, h->nQ, batch, true, "the input secret key"));
-    LR_TRY(check_poly(h, sk_out, h->nQ, batch, true, "the output secret key"));
-    LR_TRY(check_poly(h, c1, level + 1, batch, false, "the ciphertext"));
-    LR_TRY(check_poly(h, share, level + 1, batch, false, "the share"));
+    LR_TRY(h->check_poly(sk_in, h->nQ, batch, true, "the input secret key"));
+    LR_TRY(h->check_poly(sk_out, h->nQ, batch, true, "the output secret key"));
+    LR_TRY(h->check_poly(c1, level + 1, batch, false, "the ciphertext"));
+    LR_TRY(h->check_poly(share, level + 1, batch, false, "the share"));
     const lr_poly *outs[1] = {share}, *ins[3] = {sk_in, sk_out, c1};
     return check_outputs(outs, 1, ins, 3);
 }
@@ -214,14 +112,9 @@ int ckks_cks_share(lr_collective *h, int level, const lr_poly *sk_in, const lr_p
     if (!h || !sk_in || !sk_out || !c1 || !eb || !share) return fail(LR_ERR_ARG, "null argument");
     LR_TRY(check_cks(h, level, sk_in, sk_out, c1, batch, share));
     LR_HIP(hipSetDevice(h->device));
-    if (!on_device) {
-        const unsigned char *src[1] = {eb}, *dev[1];
-        const size_t bytes[1] = {(size_t)batch * (size_t)h->cQ->h.N};
-        LR_TRY(stage_random(h, src, bytes, 1, dev));
-        eb = dev[0];
-    }
+    if (!on_device) LR_TRY(h->stage_random(&eb, (size_t)batch * (size_t)h->cQ->h.N));
     lr_context *cQ = h->cQ;
-    const Pools P = pools_of(h, batch);
+    const Pools P = pools_of(h, h->d_pool, batch);
     const int L1 = level + 1;
     const Rows hP{P.p[0], P.stride, h->nQ, 1};
     if (h->call_by_call) {
@@ -247,88 +140,55 @@ int bfv_cks_share(lr_collective *h, const lr_poly *sk_in, const lr_poly *sk_out,
     const int level = h->nQ - 1;
     LR_TRY(check_cks(h, level, sk_in, sk_out, c1, batch, share));
     LR_HIP(hipSetDevice(h->device));
-    if (!on_device) {
-        const unsigned char *src[1] = {eb}, *dev[1];
-        const size_t bytes[1] = {(size_t)batch * (size_t)h->cQ->h.N};
-        LR_TRY(stage_random(h, src, bytes, 1, dev));
-        eb = dev[0];
-    }
+    if (!on_device) LR_TRY(h->stage_random(&eb, (size_t)batch * (size_t)h->cQ->h.N));
     lr_context *cQ = h->cQ;
-    const Pools P = pools_of(h, batch);
+    const Pools P = pools_of(h, h->d_pool, batch);
     const Rows q0{P.p[0], P.stride, 0, 1}, q2{P.p[2], P.stride, 0, 1};
     LR_TRY(run_ntt(cQ, false, Rows{c1->d, c1->stride(), 0, 1}, q0, 0, 1, h->nQ, batch));                              // :88
     if (h->call_by_call) {
         LR_TRY(delta_product(h, level, P.p[0], P.stride, sk_in, sk_out, P, batch));                                   // :76, :89, :90
         LR_TRY(run_ntt(cQ, true, q2, q2, 0, 1, h->nQ, batch));                                                        // :92
-        LR_TRY(noise(h, 0, 1, &eb, &P.p[0], P.stride, h->nQ + h->nP, batch));                                         // :94 Sample over Q||P
+        LR_TRY(noise_qp(h, 0, 1, &eb, &P.p[0], P.stride, h->rows(), batch));                                          // :94 Sample over Q||P
         LR_TRY(run_ewise(cQ, LR_ADD, h->nQ, batch, P.p[2], P.stride, P.p[0], P.stride, P.p[2], P.stride, nullptr));   // :95
         // :97-103: hP = the rows of P as they are, p_j of (0, sign 0) included
         return moddown_pq_core(h->bext, level, P.p[2], P.stride, Rows{P.p[0], P.stride, h->nQ, 1}, batch, share, false);   // :105
     }
     LR_HIP(launch_cks_share(share_launch(h, P.p[0], P.stride, sk_in, sk_out, nullptr, P.p[0], P.stride, batch), h->nQ, batch, cQ->stream));
     LR_TRY(run_ntt(cQ, true, q0, q0, 0, 1, h->nQ, batch));
-    LR_TRY(noise(h, 1, 1, &eb, &P.p[0], P.stride, h->nQ, batch));                           // CRed(x + residue) on the rows of Q
-    {   // the residue on the rows of P, p_j written as 0: no bit of the ModDown's output changes (tests/test_oracle_collective.py)
-        CkksExpandLaunch X;
-        std::memset(&X, 0, sizeof X);
-        X.e[0] = eb;
-        X.out = P.p[0] + (long long)h->nQ * (long long)cQ->h.N;
-        X.out_stride = P.stride;
-        X.n = (int)cQ->h.N;
-        X.noises = 1;
-        X.lp = h->d_lp + h->nQ;
-        LR_HIP(launch_ckks_expand(X, h->nP, batch, cQ->stream));
-    }
+    LR_TRY(noise_qp(h, 1, 1, &eb, &P.p[0], P.stride, h->nQ, batch));                        // CRed(x + residue) on the rows of Q
+    // the residue on the rows of P, p_j written as 0: no bit of the ModDown's output changes (tests/test_oracle_collective.py)
+    LR_TRY(expand_qp(h, h->nQ, h->nP, 0, nullptr, nullptr, 1, eb, nullptr, P.p[0], P.stride, 0, batch));
     return moddown_pq_core(h->bext, level, P.p[0], P.stride, Rows{P.p[0], P.stride, h->nQ, 1}, batch, share, false);
 }
-
-struct PcksRandom { const unsigned char *u_coeff, *u_sign, *e0, *e1; };
 
 int check_pcks(const lr_collective *h, int level, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1, int batch,
                const lr_poly *o0, const lr_poly *o1) {
     LR_TRY(check_call(h, level, batch));
-    LR_TRY(check_poly(h, sk, h->nQ, batch, true, "the secret key"));
-    LR_TRY(check_poly(h, pk0, h->nQ + h->nP, batch, true, "the public key"));
-    LR_TRY(check_poly(h, pk1, h->nQ + h->nP, batch, true, "the public key"));
-    LR_TRY(check_poly(h, c1, level + 1, batch, false, "the ciphertext"));
-    LR_TRY(check_poly(h, o0, level + 1, batch, false, "the share"));
-    LR_TRY(check_poly(h, o1, level + 1, batch, false, "the share"));
+    LR_TRY(h->check_poly(sk, h->nQ, batch, true, "the secret key"));
+    LR_TRY(h->check_poly(pk0, h->nQ + h->nP, batch, true, "the public key"));
+    LR_TRY(h->check_poly(pk1, h->nQ + h->nP, batch, true, "the public key"));
+    LR_TRY(h->check_poly(c1, level + 1, batch, false, "the ciphertext"));
+    LR_TRY(h->check_poly(o0, level + 1, batch, false, "the share"));
+    LR_TRY(h->check_poly(o1, level + 1, batch, false, "the share"));
     const lr_poly *outs[2] = {o0, o1}, *ins[4] = {sk, pk0, pk1, c1};
     return check_outputs(outs, 2, ins, 4);
 }
 
-int stage_pcks(lr_collective *h, PcksRandom *R, int batch) {
-    const size_t N = (size_t)h->cQ->h.N, plane = (size_t)batch * (N >> 3), bytes_e = (size_t)batch * N;
-    const unsigned char *src[4] = {R->u_coeff, R->u_sign, R->e0, R->e1}, *dev[4];
-    const size_t bytes[4] = {plane, plane, bytes_e, bytes_e};
-    LR_TRY(stage_random(h, src, bytes, 4, dev));
-    *R = PcksRandom{dev[0], dev[1], dev[2], dev[3]};
-    return LR_OK;
-}
-
 // SampleTernaryMontgomeryNTT over Q||P (dckks/public_keyswitching.go:68, dbfv :116) into P.p[2]
-int ternary_ntt(lr_collective *h, const PcksRandom &R, const Pools &P, int batch) {
-    TernaryLaunch T;
-    T.coeff_bits = R.u_coeff;
-    T.sign_bits = R.u_sign;
-    T.out = P.p[2];
-    T.out_stride = P.stride;
-    T.n = (int)h->cQ->h.N;
-    T.one = h->one;
-    T.minus_one = h->minus_one;
-    LR_HIP(launch_bfv_ternary(T, h->nQ + h->nP, batch, h->cQ->stream));
+int ternary_ntt(lr_collective *h, const PkRandom &R, const Pools &P, int batch) {
+    LR_TRY(ternary_qp(h, P, R.u_coeff, R.u_sign, h->rows(), batch));
     return ntt_rows(h, false, h->nQ - 1, P.p[2], P.stride, batch);
 }
 
 // PCKSProtocol.GenShare of dckks (dckks/public_keyswitching.go:63-93)
-int ckks_pcks_share(lr_collective *h, int level, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1, PcksRandom R, int batch,
+int ckks_pcks_share(lr_collective *h, int level, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1, PkRandom R, int batch,
                     lr_poly *o0, lr_poly *o1, bool on_device) {
     if (!h || !sk || !pk0 || !pk1 || !c1 || !R.u_coeff || !R.u_sign || !R.e0 || !R.e1 || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
     LR_TRY(check_pcks(h, level, sk, pk0, pk1, c1, batch, o0, o1));
     LR_HIP(hipSetDevice(h->device));
-    if (!on_device) LR_TRY(stage_pcks(h, &R, batch));
+    if (!on_device) LR_TRY(h->stage_random(&R, batch));
     lr_context *cQ = h->cQ;
-    const Pools P = pools_of(h, batch);
+    const Pools P = pools_of(h, h->d_pool, batch);
     const long long n = (long long)cQ->h.N;
     const int L1 = level + 1, top = h->nQ - 1;
     const lr_poly *pk[2] = {pk0, pk1};
@@ -337,11 +197,11 @@ int ckks_pcks_share(lr_collective *h, int level, const lr_poly *sk, const lr_pol
         const unsigned char *eb[2] = {R.e0, R.e1};
         LR_TRY(ternary_ntt(h, R, P, batch));                                                                          // :68
         for (int k = 0; k < 2; ++k)                                                                                   // :71, :73
-            LR_TRY(ewise_qp(h, LR_MUL_MONT, batch, P.p[2], P.stride, pk[k]->d, key_stride(pk[k], batch), P.p[k], P.stride));
+            LR_TRY(ewise_qp(h, true, LR_MUL_MONT, batch, P.p[2], P.stride, pk[k]->d, key_stride(pk[k], batch), P.p[k], P.stride));
         for (int k = 0; k < 2; ++k) {                                                                                 // :76-80
             LR_TRY(expand(h, top, 0, nullptr, nullptr, 1, eb[k], nullptr, P.p[2], P.stride, P.part, batch));
             LR_TRY(ntt_rows(h, false, top, P.p[2], P.stride, batch));
-            LR_TRY(ewise_qp(h, LR_ADD, batch, P.p[k], P.stride, P.p[2], P.stride, P.p[k], P.stride));
+            LR_TRY(ewise_qp(h, true, LR_ADD, batch, P.p[k], P.stride, P.p[2], P.stride, P.p[k], P.stride));
         }
         for (int k = 0; k < 2; ++k) {                                                                                 // :83, :87 ModDownNTTPQ
             const Rows pP{P.p[k], P.stride, h->nQ, 1};
@@ -386,39 +246,31 @@ int ckks_pcks_share(lr_collective *h, int level, const lr_poly *sk, const lr_pol
 }
 
 // PCKSProtocol.GenShare of dbfv (dbfv/public_keyswitching.go:111-148): pkEncryptor.encrypt's steps through P, then s c1
-int bfv_pcks_share(lr_collective *h, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1, PcksRandom R, int batch, lr_poly *o0,
+int bfv_pcks_share(lr_collective *h, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1, PkRandom R, int batch, lr_poly *o0,
                    lr_poly *o1, bool on_device) {
     if (!h || !sk || !pk0 || !pk1 || !c1 || !R.u_coeff || !R.u_sign || !R.e0 || !R.e1 || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
     const int level = h->nQ - 1, rows = h->nQ + h->nP;
     LR_TRY(check_pcks(h, level, sk, pk0, pk1, c1, batch, o0, o1));
     LR_HIP(hipSetDevice(h->device));
-    if (!on_device) LR_TRY(stage_pcks(h, &R, batch));
+    if (!on_device) LR_TRY(h->stage_random(&R, batch));
     lr_context *cQ = h->cQ;
-    const Pools P = pools_of(h, batch);
+    const Pools P = pools_of(h, h->d_pool, batch);
     const lr_poly *pk[2] = {pk0, pk1};
     lr_poly *outs[2] = {o0, o1};
     const unsigned char *eb[2] = {R.e0, R.e1};
     LR_TRY(ternary_ntt(h, R, P, batch));                                                                              // :116
     if (h->call_by_call) {
         for (int k = 0; k < 2; ++k)                                                                                   // :119, :121
-            LR_TRY(ewise_qp(h, LR_MUL_MONT, batch, P.p[2], P.stride, pk[k]->d, key_stride(pk[k], batch), P.p[k], P.stride));
+            LR_TRY(ewise_qp(h, true, LR_MUL_MONT, batch, P.p[2], P.stride, pk[k]->d, key_stride(pk[k], batch), P.p[k], P.stride));
         for (int k = 0; k < 2; ++k) LR_TRY(ntt_rows(h, true, level, P.p[k], P.stride, batch));                        // :123-124
         for (int k = 0; k < 2; ++k) {                                                                                 // :127, :129: the residues as a poly, then Context.Add
-            LR_TRY(noise(h, 0, 1, &eb[k], &P.p[2], P.stride, rows, batch));
-            LR_TRY(ewise_qp(h, LR_ADD, batch, P.p[k], P.stride, P.p[2], P.stride, P.p[k], P.stride));
+            LR_TRY(noise_qp(h, 0, 1, &eb[k], &P.p[2], P.stride, rows, batch));
+            LR_TRY(ewise_qp(h, true, LR_ADD, batch, P.p[k], P.stride, P.p[2], P.stride, P.p[k], P.stride));
         }
     } else {
-        Mul2Launch M;                    // both products in one pass over u, all rows of Q||P in one launch
-        M.a = P.p[2]; M.a_stride = P.stride;
-        M.b0 = pk0->d; M.b0_stride = key_stride(pk0, batch);
-        M.b1 = pk1->d; M.b1_stride = key_stride(pk1, batch);
-        M.out0 = P.p[0]; M.out1 = P.p[1];
-        M.out0_stride = M.out1_stride = P.stride;
-        M.n = (int)cQ->h.N;
-        M.lp = h->d_lp;
-        LR_HIP(launch_mul2(M, rows, batch, cQ->stream));
+        LR_TRY(mul2_qp(h, P, pk0, pk1, rows, batch));
         LR_TRY(ntt_rows(h, true, level, P.p[0], P.stride, 2 * batch));                      // the two pools are back to back
-        LR_TRY(noise(h, 1, 2, eb, P.p, P.stride, rows, batch));
+        LR_TRY(noise_qp(h, 1, 2, eb, P.p, P.stride, rows, batch));
     }
     for (int k = 0; k < 2; ++k)                                                                                       // :132, :136
         LR_TRY(moddown_pq_core(h->bext, level, P.p[k], P.stride, Rows{P.p[k], P.stride, h->nQ, 1}, batch, outs[k], false));
@@ -435,19 +287,19 @@ int aggregate(lr_collective *h, int level, const lr_poly *base, const lr_poly *c
     if (n_shares < 1) return fail(LR_ERR_SHAPE, "collective: n_shares must be at least 1");
     const int batch = out->batch;
     LR_TRY(check_call(h, level, batch));
-    LR_TRY(check_poly(h, out, level + 1, batch, false, "the output"));
+    LR_TRY(h->check_poly(out, level + 1, batch, false, "the output"));
     if (base) {
-        LR_TRY(check_poly(h, base, level + 1, batch, false, "the base"));
+        LR_TRY(h->check_poly(base, level + 1, batch, false, "the base"));
         if (overlap(out, base) && !same_poly(out, base)) return fail(LR_ERR_ARG, "collective: the output overlaps the base without being it");
     }
     for (int k = 0; k < n_shares; ++k) {
         if (!shares[k]) return fail(LR_ERR_ARG, "null argument");
-        LR_TRY(check_poly(h, shares[k], level + 1, batch, false, "a share"));
+        LR_TRY(h->check_poly(shares[k], level + 1, batch, false, "a share"));
         if (overlap(out, shares[k]) && !same_poly(out, shares[k])) return fail(LR_ERR_ARG, "collective: the output overlaps a share without being it");
     }
     LR_HIP(hipSetDevice(h->device));
     lr_context *cQ = h->cQ;
-    const Pools P = pools_of(h, batch);
+    const Pools P = pools_of(h, h->d_pool, batch);
     const int L1 = level + 1;
     if (h->call_by_call) {     // n_shares - 1 Context.Add calls, then KeySwitch's; the running sum lives in the pool: out may be base or a share
         const u64 *acc = shares[0]->d;
@@ -498,66 +350,29 @@ extern "C" int lr_collective_create_ex(lr_context *cQ, lr_context *cP, int max_b
     return guarded([&]() -> int {
     if (!cQ || !out) return fail(LR_ERR_ARG, "null argument");
     *out = nullptr;
+    const char *name = "collective";
     if (!cP) return fail(LR_ERR_ARG, "collective: modulus P is empty (all four protocols divide by P)");
-    Options parsed = cQ->opt;
-    if (options) LR_TRY(options_from_public(options, &parsed));
-    else parsed.apply_env();
-    if (max_batch < 1 || max_batch > 65535) return fail(LR_ERR_ARG, "max_batch must be in 1 .. 65535");
-    if (cQ->h.N < 8) return fail(LR_ERR_ARG, "collective: N must be at least 8 (the ternary bit planes hold N / 8 bytes, ring/ternarySampler.go:157)");
-    if (cP->device != cQ->device) return fail(LR_ERR_ARG, "contexts live on different devices");
-    if (cP->h.N != cQ->h.N) return fail(LR_ERR_ARG, "contexts have different ring degrees");
+    Options parsed;
+    LR_TRY(check_create(name, cQ, max_batch, options, &parsed));
+    LR_TRY(check_pair(cQ, cP));
     LR_TRY(same_stream(cQ, cP));
     std::unique_ptr<lr_collective> h(new lr_collective());
-    h->cQ = cQ;
-    h->cP = cP;
-    h->device = cQ->device;
-    h->max_batch = max_batch;
-    h->call_by_call = parsed.no_epilogue;
-    h->nQ = cQ->h.L();
-    h->nP = cP->h.L();
-    const int rows = h->nQ + h->nP;
-    if (rows > kMaxLimbs) return fail(LR_ERR_UNSUPPORTED, "collective: more than 64 limbs in Q||P");
-    std::memset(&h->one, 0, sizeof h->one);
-    std::memset(&h->minus_one, 0, sizeof h->minus_one);
-    std::memset(&h->pmont, 0, sizeof h->pmont);
-    for (int i = 0; i < rows; ++i) {     // ring/ring_context.go:119-122
-        const HostContext &c = i < h->nQ ? cQ->h : cP->h;
-        const int l = i < h->nQ ? i : i - h->nQ;
-        h->one.v[i] = mform(1, c.q[l], c.bred[l].hi, c.bred[l].lo);
-        h->minus_one.v[i] = mform(c.q[l] - 1, c.q[l], c.bred[l].hi, c.bred[l].lo);
-    }
-    for (int i = 0; i < h->nQ; ++i) {    // contextP.ModulusBigint mod q_i, then MForm (ring/ring.go:545-547)
-        const u64 q = cQ->h.q[i];
-        u64 p = 1 % q;
-        for (int j = 0; j < h->nP; ++j) p = (u64)(((u128)p * (cP->h.q[j] % q)) % q);
-        h->pmont.v[i] = mform(p, q, cQ->h.bred[i].hi, cQ->h.bred[i].lo);
-    }
+    LR_TRY(h->init(name, cQ, cP, max_batch, parsed));
     LR_HIP(hipSetDevice(cQ->device));
     LR_TRY(lr_bext_create(cQ, cP, &h->bext));
-    LR_HIP(hipMalloc((void **)&h->d_lp, (size_t)rows * sizeof(LimbParams)));
-    LR_HIP(hipMemcpy(h->d_lp, cQ->d_lp, (size_t)h->nQ * sizeof(LimbParams), hipMemcpyDeviceToDevice));
-    LR_HIP(hipMemcpy(h->d_lp + h->nQ, cP->d_lp, (size_t)h->nP * sizeof(LimbParams), hipMemcpyDeviceToDevice));
-    const size_t N = (size_t)cQ->h.N, rand_bytes = (size_t)max_batch * (N / 4 + 2 * N);
-    LR_HIP(hipMalloc((void **)&h->d_pool, (size_t)3 * max_batch * rows * N * sizeof(u64)));
-    LR_HIP(hipMalloc((void **)&h->d_zero, (size_t)rows * N * sizeof(u64)));
-    LR_HIP(hipMemsetAsync(h->d_zero, 0, (size_t)rows * N * sizeof(u64), cQ->stream));
+    const size_t N = (size_t)cQ->h.N, poly_bytes = (size_t)h->rows() * N * sizeof(u64);
+    LR_TRY(h->allocate((size_t)max_batch * (N / 4 + 2 * N)));
+    LR_HIP(hipMalloc((void **)&h->d_pool, (size_t)3 * max_batch * poly_bytes));
+    LR_HIP(hipMalloc((void **)&h->d_zero, poly_bytes));
+    LR_HIP(hipMemsetAsync(h->d_zero, 0, poly_bytes, cQ->stream));
     LR_HIP(hipStreamSynchronize(cQ->stream));          // the contexts may be given another stream before the first call
-    LR_HIP(hipMalloc((void **)&h->d_rand, rand_bytes));
-    LR_HIP(hipHostMalloc((void **)&h->h_rand, rand_bytes, 0));
-    LR_HIP(hipEventCreateWithFlags(&h->staged, hipEventDisableTiming));
     *out = h.release();
     return LR_OK;
     });
 }
 
 extern "C" int lr_collective_destroy(lr_collective *h) {
-    return guarded([&]() -> int {
-    if (!h) return LR_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();   // the handle's work may be on its context's caller-supplied stream
-    delete h;
-    return LR_OK;
-    });
+    return guarded([&]() -> int { return destroy_handle(h); });
 }
 
 typedef const unsigned char *bytes_t;
@@ -582,14 +397,14 @@ extern "C" int lr_collective_ckks_pcks_share(lr_collective *h, int level, const 
                                              const lr_poly *c1, const uint8_t *u_coeff_bits, const uint8_t *u_sign_bits, const uint8_t *e0,
                                              const uint8_t *e1, int batch, lr_poly *out0, lr_poly *out1) {
     return guarded([&]() -> int {
-        return ckks_pcks_share(h, level, sk, pk0, pk1, c1, PcksRandom{u_coeff_bits, u_sign_bits, e0, e1}, batch, out0, out1, false);
+        return ckks_pcks_share(h, level, sk, pk0, pk1, c1, PkRandom{u_coeff_bits, u_sign_bits, e0, e1}, batch, out0, out1, false);
     });
 }
 extern "C" int lr_collective_ckks_pcks_share_device(lr_collective *h, int level, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1,
                                                     const lr_poly *c1, const void *u_coeff_bits, const void *u_sign_bits, const void *e0,
                                                     const void *e1, int batch, lr_poly *out0, lr_poly *out1) {
     return guarded([&]() -> int {
-        return ckks_pcks_share(h, level, sk, pk0, pk1, c1, PcksRandom{(bytes_t)u_coeff_bits, (bytes_t)u_sign_bits, (bytes_t)e0, (bytes_t)e1}, batch,
+        return ckks_pcks_share(h, level, sk, pk0, pk1, c1, PkRandom{(bytes_t)u_coeff_bits, (bytes_t)u_sign_bits, (bytes_t)e0, (bytes_t)e1}, batch,
                                out0, out1, true);
     });
 }
@@ -597,14 +412,14 @@ extern "C" int lr_collective_bfv_pcks_share(lr_collective *h, const lr_poly *sk,
                                             const uint8_t *u_coeff_bits, const uint8_t *u_sign_bits, const uint8_t *e0, const uint8_t *e1,
                                             int batch, lr_poly *out0, lr_poly *out1) {
     return guarded([&]() -> int {
-        return bfv_pcks_share(h, sk, pk0, pk1, c1, PcksRandom{u_coeff_bits, u_sign_bits, e0, e1}, batch, out0, out1, false);
+        return bfv_pcks_share(h, sk, pk0, pk1, c1, PkRandom{u_coeff_bits, u_sign_bits, e0, e1}, batch, out0, out1, false);
     });
 }
 extern "C" int lr_collective_bfv_pcks_share_device(lr_collective *h, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const lr_poly *c1,
                                                    const void *u_coeff_bits, const void *u_sign_bits, const void *e0, const void *e1, int batch,
                                                    lr_poly *out0, lr_poly *out1) {
     return guarded([&]() -> int {
-        return bfv_pcks_share(h, sk, pk0, pk1, c1, PcksRandom{(bytes_t)u_coeff_bits, (bytes_t)u_sign_bits, (bytes_t)e0, (bytes_t)e1}, batch, out0,
+        return bfv_pcks_share(h, sk, pk0, pk1, c1, PkRandom{(bytes_t)u_coeff_bits, (bytes_t)u_sign_bits, (bytes_t)e0, (bytes_t)e1}, batch, out0,
                               out1, true);
     });
 }

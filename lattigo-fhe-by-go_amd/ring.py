@@ -842,27 +842,27 @@ def NewBfvEncoder(contextQ, t, max_batch=1, options=None):  # bfv.NewEncoder, bf
     return BfvEncoder(contextQ, t, max_batch, options)
 
 
-class BfvEncryptor:
-    """bfv.Encryptor (bfv/encryptor.go:100-345) for a batch of ciphertexts on the device (lr_bfv_encryptor), after the sampling: the
-    randomness arrives as the samplers' compact decisions.  u_bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each
-    (ring/ternarySampler.go:157-177); e = uint8 [batch, N] per sampled poly, magnitude in the low 7 bits and sign in bit 7
-    (ring/gaussianSampler.go:247).  Keys are Poly of contextQ over Q||P (fast: over Q) in NTT + Montgomery form, batch 1 or the
-    call's; plaintext and ctOut are Poly over Q in the coefficient domain.  contextP None: only the fast forms."""
+class _QpHandle:
+    """What BfvEncryptor, CkksEncryptor, KeyGenerator and Collective share (csrc/lr_qp_handle.hpp): a handle over contextQ and contextP
+    with a max_batch, made by <_abi>_create / <_abi>_create_ex and freed by <_abi>_destroy, and the check of the compact randomness'
+    size.  contextP None goes to the library as NULL: it says which handles and which calls need a P."""
+
+    _abi = None
 
     def __init__(self, contextQ, contextP, max_batch=1, options=None):
         self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
         h = C.c_void_p()
         hP = None if contextP is None else contextP.h
         if options is None:
-            check(lib().lr_bfv_encryptor_create(contextQ.h, hP, max_batch, C.byref(h)))
+            check(getattr(lib(), self._abi + "_create")(contextQ.h, hP, max_batch, C.byref(h)))
         else:
-            check(lib().lr_bfv_encryptor_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
+            check(getattr(lib(), self._abi + "_create_ex")(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
         self.h = h
 
     def __del__(self):
         try:
             if getattr(self, "h", None):
-                lib().lr_bfv_encryptor_destroy(self.h)
+                getattr(lib(), self._abi + "_destroy")(self.h)
                 self.h = None
         except Exception:
             pass
@@ -872,6 +872,16 @@ class BfvEncryptor:
         if a.size != batch * per_poly:
             raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
         return a
+
+
+class BfvEncryptor(_QpHandle):
+    """bfv.Encryptor (bfv/encryptor.go:100-345) for a batch of ciphertexts on the device (lr_bfv_encryptor), after the sampling: the
+    randomness arrives as the samplers' compact decisions.  u_bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each
+    (ring/ternarySampler.go:157-177); e = uint8 [batch, N] per sampled poly, magnitude in the low 7 bits and sign in bit 7
+    (ring/gaussianSampler.go:247).  Keys are Poly of contextQ over Q||P (fast: over Q) in NTT + Montgomery form, batch 1 or the
+    call's; plaintext and ctOut are Poly over Q in the coefficient domain.  contextP None: only the fast forms."""
+
+    _abi = "lr_bfv_encryptor"
 
     def EncryptPk(self, pk, u_bits, e, plaintext, ctOut, fast=False):  # pkEncryptor.encrypt, bfv/encryptor.go:169
         batch, N = ctOut[0].batch, self.contextQ.N
@@ -1004,36 +1014,14 @@ def NewCkksEncoder(contextQ, max_batch=1, roots=None, options=None):  # ckks.New
     return CkksEncoder(contextQ, max_batch, roots, options)
 
 
-class CkksEncryptor:
+class CkksEncryptor(_QpHandle):
     """ckks.Encryptor (ckks/encryptor.go:100-362) for a batch of ciphertexts on the device (lr_ckks_encryptor), after the sampling.  The
     randomness is BfvEncryptor's compact form: u_bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each; e = uint8 [batch, N] per
     sampled poly, magnitude in the low 7 bits and sign in bit 7.  Keys are Poly of contextQ over Q||P (fast: over Q) in NTT + Montgomery
     form, batch 1 or the call's; plaintext and ctOut are Poly of contextQ in the NTT domain with at least level + 1 limbs (what
     CkksEncoder.Encode writes and CkksPlan.Decrypt reads); limbs above level are not touched.  contextP None: only the fast forms."""
 
-    def __init__(self, contextQ, contextP, max_batch=1, options=None):
-        self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
-        h = C.c_void_p()
-        hP = None if contextP is None else contextP.h
-        if options is None:
-            check(lib().lr_ckks_encryptor_create(contextQ.h, hP, max_batch, C.byref(h)))
-        else:
-            check(lib().lr_ckks_encryptor_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                lib().lr_ckks_encryptor_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def _bytes(self, a, batch, per_poly):
-        a = np.ascontiguousarray(a, dtype=np.uint8)
-        if a.size != batch * per_poly:
-            raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
-        return a
+    _abi = "lr_ckks_encryptor"
 
     def EncryptPk(self, pk, u_bits, e, plaintext, ctOut, level, fast=False):  # pkEncryptor.encrypt, ckks/encryptor.go:179
         batch, N = ctOut[0].batch, self.contextQ.N
@@ -1069,36 +1057,14 @@ def NewCkksEncryptor(contextQ, contextP, max_batch=1, options=None):  # ckks.New
     return CkksEncryptor(contextQ, contextP, max_batch, options)
 
 
-class KeyGenerator:
+class KeyGenerator(_QpHandle):
     """ckks.KeyGenerator / bfv.KeyGenerator (ckks/keygen.go:79-494, bfv/keygen.go:70-441) on the device (lr_keygen), after the sampling.
     The randomness is the encryptors' compact form: bits = (coeff_bits, sign_bits), uint8 [batch, N / 8] each; e = uint8 [..., N] per
     sampled poly, magnitude in the low 7 bits and sign in bit 7.  Every key is a Poly of contextQ over Q||P in NTT + Montgomery form; a
     switching key is the image CkksPlan.NewSwitchingKey allocates, whose odd members hold the caller's uniform polys on entry and are not
     written.  contextP None: only the secret key and the public key, over Q."""
 
-    def __init__(self, contextQ, contextP, max_batch=1, options=None):
-        self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
-        h = C.c_void_p()
-        hP = None if contextP is None else contextP.h
-        if options is None:
-            check(lib().lr_keygen_create(contextQ.h, hP, max_batch, C.byref(h)))
-        else:
-            check(lib().lr_keygen_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                lib().lr_keygen_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def _bytes(self, a, batch, per_poly):
-        a = np.ascontiguousarray(a, dtype=np.uint8)
-        if a.size != batch * per_poly:
-            raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
-        return a
+    _abi = "lr_keygen"
 
     @property
     def beta(self):
@@ -1208,7 +1174,7 @@ def NewKeyGenerator(contextQ, contextP, max_batch=1, options=None):  # ckks.NewK
     return KeyGenerator(contextQ, contextP, max_batch, options)
 
 
-class Collective:
+class Collective(_QpHandle):
     """CKSProtocol and PCKSProtocol of dckks and dbfv (dckks/keyswitching.go, dckks/public_keyswitching.go and their dbfv twins) for a
     batch of ciphertexts on the device (lr_collective), after the sampling.  The randomness is the encryptors' compact form: e = uint8
     [batch, N] per sampled poly, magnitude in the low 7 bits and sign in bit 7 (the smudging sampler and the regular one differ only in the
@@ -1216,29 +1182,7 @@ class Collective:
     form (the secret keys are read on the rows of Q), batch 1 or the call's.  CKKS c1 and shares: NTT domain, at least level + 1 limbs;
     BFV c1 and shares: coefficient domain over Q.  The batch of a call is that of its output."""
 
-    def __init__(self, contextQ, contextP, max_batch=1, options=None):
-        self.contextQ, self.contextP, self.max_batch = contextQ, contextP, int(max_batch)
-        h = C.c_void_p()
-        hP = None if contextP is None else contextP.h
-        if options is None:
-            check(lib().lr_collective_create(contextQ.h, hP, max_batch, C.byref(h)))
-        else:
-            check(lib().lr_collective_create_ex(contextQ.h, hP, max_batch, C.byref(options), C.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                lib().lr_collective_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def _bytes(self, a, batch, per_poly):
-        a = np.ascontiguousarray(a, dtype=np.uint8)
-        if a.size != batch * per_poly:
-            raise LatticeRingError(3, "expected %d x %d bytes of randomness, got %s" % (batch, per_poly, a.shape))      # LR_ERR_SHAPE
-        return a
+    _abi = "lr_collective"
 
     def _pcks_bytes(self, u_bits, e, batch):
         N = self.contextQ.N

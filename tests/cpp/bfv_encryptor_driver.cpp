@@ -37,6 +37,13 @@ static std::atomic<int> g_fail{0};
         }                                                                                                        \
     } while (0)
 #define OK(x) CHECK((x) == LR_OK)
+// a refused call: the code as CHECK sees it, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
+static std::vector<std::string> g_refusal_log;
+#define REFUSED(cond)                                    \
+    do {                                                 \
+        CHECK(cond);                                     \
+        g_refusal_log.push_back(lr_last_error_string()); \
+    } while (0)
 
 // DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16): three for Q, one for P
 static const uint64_t Qm[4] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull};
@@ -166,20 +173,21 @@ static int refusals() {
     lr_bfv_decryptor *dec = nullptr, *nodec = nullptr;
     const unsigned long long before = launches();
     // creation
-    CHECK(lr_bfv_encryptor_create(nullptr, r.p, 1, &none) == LR_ERR_ARG);
-    CHECK(lr_bfv_encryptor_create(r.q, r.p, 1, nullptr) == LR_ERR_ARG);
-    CHECK(lr_bfv_encryptor_create(r.q, r.p, 0, &none) == LR_ERR_ARG && none == nullptr);
-    CHECK(lr_bfv_encryptor_create(r.q, r.p, 65536, &none) == LR_ERR_ARG);
-    CHECK(lr_bfv_encryptor_create(small, nullptr, 1, &none) == LR_ERR_ARG);                 // N < 8
-    CHECK(lr_bfv_encryptor_create(r.q, big, 1, &none) == LR_ERR_ARG);                       // ctxP with another N
-    CHECK(lr_bfv_encryptor_create(r.q, dev1, 1, &none) == LR_ERR_ARG);                      // ctxP on another device
+    REFUSED(lr_bfv_encryptor_create(nullptr, r.p, 1, &none) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encryptor_create(r.q, r.p, 1, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encryptor_create(r.q, r.p, 0, &none) == LR_ERR_ARG && none == nullptr);
+    REFUSED(lr_bfv_encryptor_create(r.q, r.p, 65536, &none) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encryptor_create(small, nullptr, 1, &none) == LR_ERR_ARG);                 // N < 8
+    REFUSED(lr_bfv_encryptor_create(r.q, big, 1, &none) == LR_ERR_ARG);                       // ctxP with another N
+    REFUSED(lr_bfv_encryptor_create(r.q, dev1, 1, &none) == LR_ERR_ARG);                      // ctxP on another device
     lr_options bad;
     OK(lr_options_init(&bad));
     bad.version = 99;
-    CHECK(lr_bfv_encryptor_create_ex(r.q, r.p, 1, &bad, &none) == LR_ERR_ARG);
-    CHECK(lr_bfv_decryptor_create(nullptr, 1, &nodec) == LR_ERR_ARG);
-    CHECK(lr_bfv_decryptor_create(r.q, 1, nullptr) == LR_ERR_ARG);
-    CHECK(lr_bfv_decryptor_create(r.q, 0, &nodec) == LR_ERR_ARG && lr_bfv_decryptor_create(r.q, 65536, &nodec) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encryptor_create_ex(r.q, r.p, 1, &bad, &none) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decryptor_create(nullptr, 1, &nodec) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decryptor_create(r.q, 1, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decryptor_create(r.q, 0, &nodec) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decryptor_create(r.q, 65536, &nodec) == LR_ERR_ARG);
     count += 12;
     OK(lr_bfv_encryptor_create(r.q, r.p, 2, &enc));
     OK(lr_bfv_encryptor_create(r.q, nullptr, 2, &fast_only));
@@ -190,50 +198,53 @@ static int refusals() {
     std::vector<uint8_t> b((size_t)3 * N, 0);
     const uint8_t *u = b.data();
     // the form against the handle
-    CHECK(lr_bfv_encrypt_pk(fast_only, 0, pk0, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(fast_only, 0, pk0, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
     CHECK(std::string(lr_last_error_string()).find("fast form") != std::string::npos);
-    CHECK(lr_bfv_encrypt_sk(fast_only, 0, sk, crp, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk(fast_only, 0, sk, crp, u, pt, 2, c0, c1) == LR_ERR_ARG);
     OK(lr_bfv_encrypt_pk(fast_only, 1, keyq, keyq, u, u, u, u, pt, 2, c0, c1));               // ... which serves the fast forms, keys over Q
     // NULL arguments
-    CHECK(lr_bfv_encrypt_pk(nullptr, 0, pk0, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, nullptr, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, nullptr, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, nullptr, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk_device(enc, 0, pk0, pk1, u, nullptr, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, nullptr, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 2, c0, nullptr) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_sk(enc, 0, nullptr, crp, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_sk(enc, 0, sk, nullptr, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_sk(enc, 0, sk, crp, nullptr, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_sk_device(enc, 0, sk, crp, nullptr, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(nullptr, 0, pk0, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, nullptr, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, nullptr, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, nullptr, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk_device(enc, 0, pk0, pk1, u, nullptr, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, nullptr, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 2, c0, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk(enc, 0, nullptr, crp, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk(enc, 0, sk, nullptr, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk(enc, 0, sk, crp, nullptr, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk_device(enc, 0, sk, crp, nullptr, pt, 2, c0, c1) == LR_ERR_ARG);
     // out_c0 == out_c1, a poly of another context
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 2, c0, c0) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_sk(enc, 1, sk, crp, u, pt, 2, c1, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, foreign, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, foreign, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_sk(enc, 0, sk, foreign, u, pt, 2, c0, c1) == LR_ERR_ARG);
-    CHECK(lr_bfv_encrypt_sk(enc, 0, sk, crp, u, pt, 2, foreign, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 2, c0, c0) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk(enc, 1, sk, crp, u, pt, 2, c1, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, foreign, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, foreign, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk(enc, 0, sk, foreign, u, pt, 2, c0, c1) == LR_ERR_ARG);
+    REFUSED(lr_bfv_encrypt_sk(enc, 0, sk, crp, u, pt, 2, foreign, c1) == LR_ERR_ARG);
     // batch and limbs
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 0, c0, c1) == LR_ERR_SHAPE);
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, three, 3, three, c1) == LR_ERR_SHAPE);   // above max_batch
-    CHECK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 1, c0, c1) == LR_ERR_SHAPE);         // differs from the polys'
-    CHECK(lr_bfv_encrypt_pk(enc, 0, three, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_SHAPE);
-    CHECK(lr_bfv_encrypt_sk(enc, 0, sk, pk0, u, pt, 2, c0, c1) == LR_ERR_SHAPE);                   // crp of batch 1
-    CHECK(lr_bfv_encrypt_pk(enc, 0, keyq, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_SHAPE);        // a key over Q for the form through P
-    CHECK(lr_bfv_encrypt_pk(enc, 1, pk0, pk1, u, u, u, u, pt, 2, narrow, c1) == LR_ERR_SHAPE);
-    CHECK(lr_bfv_encrypt_sk(enc, 1, sk, crp, u, narrow, 2, c0, c1) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 0, c0, c1) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, three, 3, three, c1) == LR_ERR_SHAPE);   // above max_batch
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 1, c0, c1) == LR_ERR_SHAPE);         // differs from the polys'
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, three, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_encrypt_sk(enc, 0, sk, pk0, u, pt, 2, c0, c1) == LR_ERR_SHAPE);                   // crp of batch 1
+    REFUSED(lr_bfv_encrypt_pk(enc, 0, keyq, pk1, u, u, u, u, pt, 2, c0, c1) == LR_ERR_SHAPE);        // a key over Q for the form through P
+    REFUSED(lr_bfv_encrypt_pk(enc, 1, pk0, pk1, u, u, u, u, pt, 2, narrow, c1) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_encrypt_sk(enc, 1, sk, crp, u, narrow, 2, c0, c1) == LR_ERR_SHAPE);
     // decrypt
     const lr_poly *ct[2] = {c0, c1}, *with_null[2] = {c0, nullptr}, *with_foreign[2] = {c0, foreign}, *with_narrow[2] = {narrow, c1};
-    CHECK(lr_bfv_decrypt(dec, ct, -1, sk, pt, 2) == LR_ERR_ARG);
-    CHECK(lr_bfv_decrypt(nullptr, ct, 1, sk, pt, 2) == LR_ERR_ARG && lr_bfv_decrypt(dec, nullptr, 1, sk, pt, 2) == LR_ERR_ARG);
-    CHECK(lr_bfv_decrypt(dec, ct, 1, nullptr, pt, 2) == LR_ERR_ARG && lr_bfv_decrypt(dec, ct, 1, sk, nullptr, 2) == LR_ERR_ARG);
-    CHECK(lr_bfv_decrypt(dec, with_null, 1, sk, pt, 2) == LR_ERR_ARG);
-    CHECK(lr_bfv_decrypt(dec, with_foreign, 1, sk, pt, 2) == LR_ERR_ARG);
-    CHECK(lr_bfv_decrypt(dec, ct, 1, foreign, pt, 2) == LR_ERR_ARG);
-    CHECK(lr_bfv_decrypt(dec, ct, 1, sk, pt, 0) == LR_ERR_SHAPE && lr_bfv_decrypt(dec, ct, 1, sk, pt, 3) == LR_ERR_SHAPE);
-    CHECK(lr_bfv_decrypt(dec, ct, 1, sk, pt, 1) == LR_ERR_SHAPE);
-    CHECK(lr_bfv_decrypt(dec, with_narrow, 1, sk, pt, 2) == LR_ERR_SHAPE);
-    CHECK(lr_bfv_decrypt(dec, ct, 1, narrow, pt, 2) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_decrypt(dec, ct, -1, sk, pt, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(nullptr, ct, 1, sk, pt, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(dec, nullptr, 1, sk, pt, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(dec, ct, 1, nullptr, pt, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(dec, ct, 1, sk, nullptr, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(dec, with_null, 1, sk, pt, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(dec, with_foreign, 1, sk, pt, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(dec, ct, 1, foreign, pt, 2) == LR_ERR_ARG);
+    REFUSED(lr_bfv_decrypt(dec, ct, 1, sk, pt, 0) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_decrypt(dec, ct, 1, sk, pt, 3) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_decrypt(dec, ct, 1, sk, pt, 1) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_decrypt(dec, with_narrow, 1, sk, pt, 2) == LR_ERR_SHAPE);
+    REFUSED(lr_bfv_decrypt(dec, ct, 1, narrow, pt, 2) == LR_ERR_SHAPE);
     count += 2 + 11 + 6 + 8 + 13;
     CHECK(launches() - before == 5);                                                               // only the one accepted call launched anything
     OK(lr_bfv_encrypt_pk(enc, 0, pk0, pk1, u, u, u, u, pt, 2, c0, c1));                            // the handles stay usable
@@ -270,6 +281,10 @@ int main() {
         calls += threaded.load();
     }
     CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
+    CHECK((int)g_refusal_log.size() == refused);
+    std::printf("refusal messages begin\n");
+    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
+    std::printf("refusal messages end\n");
     std::printf("bfv_encryptor: calls %d, refusals %d, failures %d\n", calls, refused, g_fail.load());
     return g_fail.load() ? 1 : 0;
 }

@@ -33,6 +33,13 @@ static std::atomic<int> g_fail{0};
         }                                                                                                        \
     } while (0)
 #define OK(x) CHECK((x) == LR_OK)
+// a refused call: the code as CHECK sees it, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
+static std::vector<std::string> g_refusal_log;
+#define REFUSED(cond)                                    \
+    do {                                                 \
+        CHECK(cond);                                     \
+        g_refusal_log.push_back(lr_last_error_string()); \
+    } while (0)
 
 // DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
 static const uint64_t Qm[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 1099516280833ull};
@@ -203,19 +210,19 @@ static int refusals() {
     lr_collective *col = nullptr, *none = nullptr;
     const Counts before = snap();
     // creation
-    CHECK(lr_collective_create(nullptr, r.p, 1, &none) == LR_ERR_ARG);
-    CHECK(lr_collective_create(r.q, r.p, 1, nullptr) == LR_ERR_ARG);
-    CHECK(lr_collective_create(r.q, nullptr, 1, &none) == LR_ERR_ARG && none == nullptr);   // ctxP is required
+    REFUSED(lr_collective_create(nullptr, r.p, 1, &none) == LR_ERR_ARG);
+    REFUSED(lr_collective_create(r.q, r.p, 1, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_collective_create(r.q, nullptr, 1, &none) == LR_ERR_ARG && none == nullptr);   // ctxP is required
     CHECK(std::string(lr_last_error_string()).find("modulus P is empty") != std::string::npos);
-    CHECK(lr_collective_create(r.q, r.p, 0, &none) == LR_ERR_ARG && none == nullptr);
-    CHECK(lr_collective_create(r.q, r.p, 65536, &none) == LR_ERR_ARG);
-    CHECK(lr_collective_create(small, smallp, 1, &none) == LR_ERR_ARG);                // N < 8
-    CHECK(lr_collective_create(r.q, big, 1, &none) == LR_ERR_ARG);                     // ctxP with another N
-    CHECK(lr_collective_create(r.q, dev1, 1, &none) == LR_ERR_ARG);                    // ctxP on another device
+    REFUSED(lr_collective_create(r.q, r.p, 0, &none) == LR_ERR_ARG && none == nullptr);
+    REFUSED(lr_collective_create(r.q, r.p, 65536, &none) == LR_ERR_ARG);
+    REFUSED(lr_collective_create(small, smallp, 1, &none) == LR_ERR_ARG);                // N < 8
+    REFUSED(lr_collective_create(r.q, big, 1, &none) == LR_ERR_ARG);                     // ctxP with another N
+    REFUSED(lr_collective_create(r.q, dev1, 1, &none) == LR_ERR_ARG);                    // ctxP on another device
     lr_options bad;
     OK(lr_options_init(&bad));
     bad.version = 99;
-    CHECK(lr_collective_create_ex(r.q, r.p, 1, &bad, &none) == LR_ERR_ARG);
+    REFUSED(lr_collective_create_ex(r.q, r.p, 1, &bad, &none) == LR_ERR_ARG);
     count += 9;
     OK(lr_collective_create(r.q, r.p, 2, &col));
     lr_poly *sk = poly(r.q, rows, 1), *sk3 = poly(r.q, rows, 3), *pk0 = poly(r.q, rows, 1), *pk1 = poly(r.q, rows, 1), *pkq = poly(r.q, nq, 1);
@@ -234,86 +241,86 @@ static int refusals() {
     std::vector<uint8_t> b((size_t)3 * N, 0);
     const uint8_t *u = b.data();
     // NULL arguments
-    CHECK(lr_collective_ckks_cks_share(nullptr, top, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share(col, top, nullptr, sk, c1, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share_device(col, top, sk, nullptr, c1, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, nullptr, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share_device(col, top, sk, sk, c1, nullptr, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, nullptr) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_cks_share(nullptr, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_cks_share_device(col, sk, sk, c1, nullptr, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_cks_share(col, sk, sk, c1, u, 2, nullptr) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share(col, top, nullptr, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share(col, top, sk, nullptr, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share_device(col, top, sk, pk0, pk1, c1, nullptr, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share_device(col, top, sk, pk0, pk1, c1, u, u, u, nullptr, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, nullptr) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_pcks_share(col, sk, pk0, nullptr, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_pcks_share_device(col, sk, pk0, pk1, nullptr, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_pcks_share_device(col, sk, pk0, pk1, c1, u, nullptr, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(nullptr, top, nullptr, two, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, nullptr, nullptr, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, nullptr, with_null, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, nullptr, two, 2, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(nullptr, top, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(col, top, nullptr, sk, c1, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share_device(col, top, sk, nullptr, c1, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, nullptr, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share_device(col, top, sk, sk, c1, nullptr, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_cks_share(nullptr, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_cks_share_device(col, sk, sk, c1, nullptr, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_cks_share(col, sk, sk, c1, u, 2, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share(col, top, nullptr, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share(col, top, sk, nullptr, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share_device(col, top, sk, pk0, pk1, c1, nullptr, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share_device(col, top, sk, pk0, pk1, c1, u, u, u, nullptr, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_pcks_share(col, sk, pk0, nullptr, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_pcks_share_device(col, sk, pk0, pk1, nullptr, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_pcks_share_device(col, sk, pk0, pk1, c1, u, nullptr, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(nullptr, top, nullptr, two, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, nullptr, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, with_null, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, two, 2, nullptr) == LR_ERR_ARG);
     count += 21;
     // a poly of another context, an output that shares memory with an input or with the other output, a partial overlap in the fold
-    CHECK(lr_collective_ckks_cks_share(col, top, foreign1, sk, c1, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, foreign1, c1, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_cks_share(col, sk, sk, foreign, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_cks_share(col, sk, sk, c1, u, 2, foreign) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, c1) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_cks_share_device(col, o0, sk, c1, u, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, head, u, 1, inside) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share(col, top, foreign1, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share(col, top, sk, pk0, foreign1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c1, u, u, u, u, 2, o0, foreign) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share_device(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, c1, o1) == LR_ERR_ARG);
-    CHECK(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, c1) == LR_ERR_ARG);
-    CHECK(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c11, u, u, u, u, 1, head, inside) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, nullptr, with_foreign, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, foreign, two, 2, o0) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, nullptr, two, 2, foreign) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, nullptr, one_inside, 1, head) == LR_ERR_ARG);
-    CHECK(lr_collective_aggregate(col, top, inside, one11, 1, head) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(col, top, foreign1, sk, c1, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, foreign1, c1, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_cks_share(col, sk, sk, foreign, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_cks_share(col, sk, sk, c1, u, 2, foreign) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, c1) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_cks_share_device(col, o0, sk, c1, u, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, head, u, 1, inside) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share(col, top, foreign1, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share(col, top, sk, pk0, foreign1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c1, u, u, u, u, 2, o0, foreign) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share_device(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, c1, o1) == LR_ERR_ARG);
+    REFUSED(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, c1) == LR_ERR_ARG);
+    REFUSED(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c11, u, u, u, u, 1, head, inside) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, with_foreign, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, foreign, two, 2, o0) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, two, 2, foreign) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, one_inside, 1, head) == LR_ERR_ARG);
+    REFUSED(lr_collective_aggregate(col, top, inside, one11, 1, head) == LR_ERR_ARG);
     count += 19;
     // levels, batches and limbs
-    CHECK(lr_collective_ckks_cks_share(col, nq, sk, sk, c1, u, 2, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_ckks_cks_share(col, -1, sk, sk, c1, u, 2, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 0, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c13, u, 3, o3) == LR_ERR_SHAPE);      // above max_batch
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 1, o0) == LR_ERR_SHAPE);       // differs from the polys'
-    CHECK(lr_collective_ckks_cks_share(col, top, sk3, sk, c1, u, 2, o0) == LR_ERR_SHAPE);      // keys: batch 1 or the call's
-    CHECK(lr_collective_ckks_cks_share(col, top, narrow1, sk, c1, u, 2, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c11, u, 2, o0) == LR_ERR_SHAPE);      // c1 of batch 1
-    CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, narrow) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_ckks_cks_share(col, nq, sk, sk, c1, u, 2, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_ckks_cks_share(col, -1, sk, sk, c1, u, 2, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 0, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c13, u, 3, o3) == LR_ERR_SHAPE);      // above max_batch
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 1, o0) == LR_ERR_SHAPE);       // differs from the polys'
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk3, sk, c1, u, 2, o0) == LR_ERR_SHAPE);      // keys: batch 1 or the call's
+    REFUSED(lr_collective_ckks_cks_share(col, top, narrow1, sk, c1, u, 2, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c11, u, 2, o0) == LR_ERR_SHAPE);      // c1 of batch 1
+    REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, narrow) == LR_ERR_SHAPE);
     OK(lr_collective_ckks_cks_share(col, top - 1, sk, sk, narrow, u, 2, o0));                  // ... which is enough one level down
-    CHECK(lr_collective_bfv_cks_share(col, sk, sk, narrow, u, 2, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_bfv_cks_share(col, sk, sk, c1, u, -1, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_ckks_pcks_share(col, nq, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);
-    CHECK(lr_collective_ckks_pcks_share(col, top, sk, pkq, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);   // the public key over Q only
-    CHECK(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, narrow) == LR_ERR_SHAPE);
-    CHECK(lr_collective_bfv_pcks_share(col, sk, pk0, pkq, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);
-    CHECK(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c1, u, u, u, u, 0, o0, o1) == LR_ERR_SHAPE);
-    CHECK(lr_collective_bfv_pcks_share(col, sk3, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);
-    CHECK(lr_collective_aggregate(col, top, nullptr, two, 0, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_aggregate(col, nq, nullptr, two, 2, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_aggregate(col, top, nullptr, mixed, 2, o0) == LR_ERR_SHAPE);           // every poly has the same batch
-    CHECK(lr_collective_aggregate(col, top, c11, two, 2, o0) == LR_ERR_SHAPE);
-    CHECK(lr_collective_aggregate(col, top, nullptr, two, 2, narrow) == LR_ERR_SHAPE);
-    CHECK(lr_collective_aggregate(col, top, nullptr, one3, 1, o3) == LR_ERR_SHAPE);            // above max_batch
+    REFUSED(lr_collective_bfv_cks_share(col, sk, sk, narrow, u, 2, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_bfv_cks_share(col, sk, sk, c1, u, -1, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_ckks_pcks_share(col, nq, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_ckks_pcks_share(col, top, sk, pkq, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);   // the public key over Q only
+    REFUSED(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, narrow) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_bfv_pcks_share(col, sk, pk0, pkq, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_bfv_pcks_share(col, sk, pk0, pk1, c1, u, u, u, u, 0, o0, o1) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_bfv_pcks_share(col, sk3, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, two, 0, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_aggregate(col, nq, nullptr, two, 2, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, mixed, 2, o0) == LR_ERR_SHAPE);           // every poly has the same batch
+    REFUSED(lr_collective_aggregate(col, top, c11, two, 2, o0) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, two, 2, narrow) == LR_ERR_SHAPE);
+    REFUSED(lr_collective_aggregate(col, top, nullptr, one3, 1, o3) == LR_ERR_SHAPE);            // above max_batch
     count += 23;
     {   // the two contexts on different streams: every entry point refuses, and so does creation
         hipStream_t st = nullptr;
         CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess);
         OK(lr_context_set_stream(r.q, st));
-        CHECK(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
+        REFUSED(lr_collective_ckks_cks_share(col, top, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
         CHECK(std::string(lr_last_error_string()).find("different streams") != std::string::npos);
-        CHECK(lr_collective_bfv_cks_share_device(col, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
-        CHECK(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-        CHECK(lr_collective_bfv_pcks_share_device(col, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
-        CHECK(lr_collective_aggregate(col, top, nullptr, two, 2, o0) == LR_ERR_ARG);
-        CHECK(lr_collective_create(r.q, r.p, 1, &none) == LR_ERR_ARG && none == nullptr);
+        REFUSED(lr_collective_bfv_cks_share_device(col, sk, sk, c1, u, 2, o0) == LR_ERR_ARG);
+        REFUSED(lr_collective_ckks_pcks_share(col, top, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+        REFUSED(lr_collective_bfv_pcks_share_device(col, sk, pk0, pk1, c1, u, u, u, u, 2, o0, o1) == LR_ERR_ARG);
+        REFUSED(lr_collective_aggregate(col, top, nullptr, two, 2, o0) == LR_ERR_ARG);
+        REFUSED(lr_collective_create(r.q, r.p, 1, &none) == LR_ERR_ARG && none == nullptr);
         OK(lr_context_sync(r.q));
         OK(lr_context_set_stream(r.q, nullptr));
         CHECK(hipStreamDestroy(st) == hipSuccess);
@@ -356,6 +363,10 @@ int main() {
         calls += threaded.load();
     }
     CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
+    CHECK((int)g_refusal_log.size() == refused);
+    std::printf("refusal messages begin\n");
+    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
+    std::printf("refusal messages end\n");
     std::printf("collective: calls %d, refusals %d, failures %d\n", calls, refused, g_fail.load());
     return g_fail.load() ? 1 : 0;
 }

@@ -31,6 +31,13 @@ static std::atomic<int> g_fail{0};
         }                                                                                                        \
     } while (0)
 #define OK(x) CHECK((x) == LR_OK)
+// a refused call: the code as CHECK sees it, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
+static std::vector<std::string> g_refusal_log;
+#define REFUSED(cond)                                    \
+    do {                                                 \
+        CHECK(cond);                                     \
+        g_refusal_log.push_back(lr_last_error_string()); \
+    } while (0)
 
 // DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
 static const uint64_t Qm[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 1099516280833ull};
@@ -163,17 +170,17 @@ static int refusals() {
     lr_keygen *kg = nullptr, *none = nullptr, *no_p = nullptr;
     const unsigned long long before = lr::g_stub_launches.load() + lr::g_ckks_expand_launches.load();
     // creation
-    CHECK(lr_keygen_create(nullptr, r.p, 1, &none) == LR_ERR_ARG);
-    CHECK(lr_keygen_create(r.q, r.p, 1, nullptr) == LR_ERR_ARG);
-    CHECK(lr_keygen_create(r.q, r.p, 0, &none) == LR_ERR_ARG && none == nullptr);
-    CHECK(lr_keygen_create(r.q, r.p, 65536, &none) == LR_ERR_ARG);
-    CHECK(lr_keygen_create(small, nullptr, 1, &none) == LR_ERR_ARG);                 // N < 8
-    CHECK(lr_keygen_create(r.q, big, 1, &none) == LR_ERR_ARG);                       // ctxP with another N
-    CHECK(lr_keygen_create(r.q, dev1, 1, &none) == LR_ERR_ARG);                      // ctxP on another device
+    REFUSED(lr_keygen_create(nullptr, r.p, 1, &none) == LR_ERR_ARG);
+    REFUSED(lr_keygen_create(r.q, r.p, 1, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_keygen_create(r.q, r.p, 0, &none) == LR_ERR_ARG && none == nullptr);
+    REFUSED(lr_keygen_create(r.q, r.p, 65536, &none) == LR_ERR_ARG);
+    REFUSED(lr_keygen_create(small, nullptr, 1, &none) == LR_ERR_ARG);                 // N < 8
+    REFUSED(lr_keygen_create(r.q, big, 1, &none) == LR_ERR_ARG);                       // ctxP with another N
+    REFUSED(lr_keygen_create(r.q, dev1, 1, &none) == LR_ERR_ARG);                      // ctxP on another device
     lr_options bad;
     OK(lr_options_init(&bad));
     bad.version = 99;
-    CHECK(lr_keygen_create_ex(r.q, r.p, 1, &bad, &none) == LR_ERR_ARG);
+    REFUSED(lr_keygen_create_ex(r.q, r.p, 1, &bad, &none) == LR_ERR_ARG);
     count += 8;
     OK(lr_keygen_create(r.q, r.p, 2, &kg));
     OK(lr_keygen_create(r.q, nullptr, 2, &no_p));
@@ -193,78 +200,78 @@ static int refusals() {
     const uint8_t *u = b.data();
     const uint64_t g[3] = {5, 25, 125}, even[2] = {5, 6}, zero[2] = {0, 5};
     // a handle without P
-    CHECK(lr_keygen_switching_keys(no_p, sk, sk, u, 2, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(no_p, sk, sk, u, 2, keys) == LR_ERR_ARG);
     CHECK(std::string(lr_last_error_string()).find("modulus P is empty") != std::string::npos);
-    CHECK(lr_keygen_relin_keys(no_p, sk, 1, u, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_rotation_keys_device(no_p, sk, g, 2, u, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_relin_keys(no_p, sk, 1, u, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_rotation_keys_device(no_p, sk, g, 2, u, keys) == LR_ERR_ARG);
     OK(lr_keygen_secret_key(no_p, u, u, 2, skq));                                    // ... which serves the secret and the public key over Q
     count += 3;
     // NULL arguments
-    CHECK(lr_keygen_secret_key(nullptr, u, u, 2, sk2) == LR_ERR_ARG);
-    CHECK(lr_keygen_secret_key(kg, nullptr, u, 2, sk2) == LR_ERR_ARG);
-    CHECK(lr_keygen_secret_key_device(kg, u, nullptr, 2, sk2) == LR_ERR_ARG);
-    CHECK(lr_keygen_secret_key(kg, u, u, 2, nullptr) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, nullptr, u, 2, pk0, pk1) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key_device(kg, sk, nullptr, 2, pk0, pk1) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, sk, u, 2, nullptr, pk1) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, sk, u, 2, pk0, nullptr) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, nullptr, sk, u, 2, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, sk, nullptr, u, 2, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys_device(kg, sk, sk, nullptr, 2, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 2, nullptr) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_null) == LR_ERR_ARG);
-    CHECK(lr_keygen_relin_keys(kg, nullptr, 2, u, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_relin_keys_device(kg, sk, 2, nullptr, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_rotation_keys(kg, sk, nullptr, 2, u, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_rotation_keys_device(kg, sk, g, 2, u, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_keygen_secret_key(nullptr, u, u, 2, sk2) == LR_ERR_ARG);
+    REFUSED(lr_keygen_secret_key(kg, nullptr, u, 2, sk2) == LR_ERR_ARG);
+    REFUSED(lr_keygen_secret_key_device(kg, u, nullptr, 2, sk2) == LR_ERR_ARG);
+    REFUSED(lr_keygen_secret_key(kg, u, u, 2, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, nullptr, u, 2, pk0, pk1) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key_device(kg, sk, nullptr, 2, pk0, pk1) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, sk, u, 2, nullptr, pk1) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, sk, u, 2, pk0, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, nullptr, sk, u, 2, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, sk, nullptr, u, 2, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys_device(kg, sk, sk, nullptr, 2, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 2, nullptr) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_null) == LR_ERR_ARG);
+    REFUSED(lr_keygen_relin_keys(kg, nullptr, 2, u, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_relin_keys_device(kg, sk, 2, nullptr, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_rotation_keys(kg, sk, nullptr, 2, u, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_rotation_keys_device(kg, sk, g, 2, u, nullptr) == LR_ERR_ARG);
     count += 17;
     // a poly of another context, an output that is an input or another output, an even Galois element
-    CHECK(lr_keygen_secret_key(kg, u, u, 2, foreign) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, foreign1, u, 2, pk0, pk1) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, sk, u, 2, foreign, pk1) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, sk, u, 2, pk0, foreign) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, sk, u, 2, pk0, pk0) == LR_ERR_ARG);
-    CHECK(lr_keygen_public_key(kg, sk2, u, 2, sk2, pk1) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, foreign1, sk, u, 2, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, sk, foreign1, u, 2, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_foreign) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 2, same) == LR_ERR_ARG);
-    CHECK(lr_keygen_switching_keys(kg, inside, sk, u, 1, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_relin_keys(kg, inside, 1, u, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_rotation_keys(kg, sk, even, 2, u, keys) == LR_ERR_ARG);
-    CHECK(lr_keygen_rotation_keys_device(kg, sk, zero, 2, u, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_secret_key(kg, u, u, 2, foreign) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, foreign1, u, 2, pk0, pk1) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, sk, u, 2, foreign, pk1) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, sk, u, 2, pk0, foreign) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, sk, u, 2, pk0, pk0) == LR_ERR_ARG);
+    REFUSED(lr_keygen_public_key(kg, sk2, u, 2, sk2, pk1) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, foreign1, sk, u, 2, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, sk, foreign1, u, 2, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_foreign) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 2, same) == LR_ERR_ARG);
+    REFUSED(lr_keygen_switching_keys(kg, inside, sk, u, 1, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_relin_keys(kg, inside, 1, u, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_rotation_keys(kg, sk, even, 2, u, keys) == LR_ERR_ARG);
+    REFUSED(lr_keygen_rotation_keys_device(kg, sk, zero, 2, u, keys) == LR_ERR_ARG);
     count += 14;
     // counts, batches and limbs
-    CHECK(lr_keygen_secret_key(kg, u, u, 0, sk2) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_secret_key(kg, u, u, 3, sk3) == LR_ERR_SHAPE);                   // above max_batch
-    CHECK(lr_keygen_secret_key(kg, u, u, 1, sk2) == LR_ERR_SHAPE);                   // differs from the poly's
-    CHECK(lr_keygen_secret_key(kg, u, u, 2, narrow) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_public_key(kg, sk, u, -1, pk0, pk1) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_public_key(kg, sk3, u, 2, pk0, pk1) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_public_key(kg, sk, u, 2, pk0, sk) == LR_ERR_SHAPE);              // pk1 of batch 1
-    CHECK(lr_keygen_public_key(kg, narrow1, u, 2, pk0, pk1) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_public_key(kg, sk, u, 2, narrow, pk1) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 0, keys) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 3, three) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_switching_keys(kg, sk3, sk, u, 2, keys) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_switching_keys(kg, sk, narrow1, u, 2, keys) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_narrow) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_batch) == LR_ERR_SHAPE);   // a key whose batch is not 2 beta
-    CHECK(lr_keygen_relin_keys(kg, sk, 3, u, three) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_relin_keys(kg, sk2, 2, u, keys) == LR_ERR_SHAPE);                // one secret key
-    CHECK(lr_keygen_rotation_keys(kg, sk, g, -1, u, keys) == LR_ERR_SHAPE);
-    CHECK(lr_keygen_rotation_keys(kg, sk2, g, 2, u, keys) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_secret_key(kg, u, u, 0, sk2) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_secret_key(kg, u, u, 3, sk3) == LR_ERR_SHAPE);                   // above max_batch
+    REFUSED(lr_keygen_secret_key(kg, u, u, 1, sk2) == LR_ERR_SHAPE);                   // differs from the poly's
+    REFUSED(lr_keygen_secret_key(kg, u, u, 2, narrow) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_public_key(kg, sk, u, -1, pk0, pk1) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_public_key(kg, sk3, u, 2, pk0, pk1) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_public_key(kg, sk, u, 2, pk0, sk) == LR_ERR_SHAPE);              // pk1 of batch 1
+    REFUSED(lr_keygen_public_key(kg, narrow1, u, 2, pk0, pk1) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_public_key(kg, sk, u, 2, narrow, pk1) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 0, keys) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 3, three) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_switching_keys(kg, sk3, sk, u, 2, keys) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_switching_keys(kg, sk, narrow1, u, 2, keys) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_narrow) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 2, with_batch) == LR_ERR_SHAPE);   // a key whose batch is not 2 beta
+    REFUSED(lr_keygen_relin_keys(kg, sk, 3, u, three) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_relin_keys(kg, sk2, 2, u, keys) == LR_ERR_SHAPE);                // one secret key
+    REFUSED(lr_keygen_rotation_keys(kg, sk, g, -1, u, keys) == LR_ERR_SHAPE);
+    REFUSED(lr_keygen_rotation_keys(kg, sk2, g, 2, u, keys) == LR_ERR_SHAPE);
     count += 19;
     {   // the two contexts on different streams: every entry point of a handle with a ctxP refuses
         hipStream_t st = nullptr;
         CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess);
         OK(lr_context_set_stream(r.q, st));
-        CHECK(lr_keygen_secret_key(kg, u, u, 2, sk2) == LR_ERR_ARG);
+        REFUSED(lr_keygen_secret_key(kg, u, u, 2, sk2) == LR_ERR_ARG);
         CHECK(std::string(lr_last_error_string()).find("different streams") != std::string::npos);
-        CHECK(lr_keygen_public_key_device(kg, sk, u, 2, pk0, pk1) == LR_ERR_ARG);
-        CHECK(lr_keygen_switching_keys(kg, sk, sk, u, 2, keys) == LR_ERR_ARG);
-        CHECK(lr_keygen_relin_keys_device(kg, sk, 2, u, keys) == LR_ERR_ARG);
-        CHECK(lr_keygen_rotation_keys(kg, sk, g, 2, u, keys) == LR_ERR_ARG);
+        REFUSED(lr_keygen_public_key_device(kg, sk, u, 2, pk0, pk1) == LR_ERR_ARG);
+        REFUSED(lr_keygen_switching_keys(kg, sk, sk, u, 2, keys) == LR_ERR_ARG);
+        REFUSED(lr_keygen_relin_keys_device(kg, sk, 2, u, keys) == LR_ERR_ARG);
+        REFUSED(lr_keygen_rotation_keys(kg, sk, g, 2, u, keys) == LR_ERR_ARG);
         OK(lr_keygen_secret_key(no_p, u, u, 2, skq));                                // a handle without ctxP has one stream
         OK(lr_context_sync(r.q));
         OK(lr_context_set_stream(r.q, nullptr));
@@ -307,6 +314,10 @@ int main() {
         calls += threaded.load();
     }
     CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
+    CHECK((int)g_refusal_log.size() == refused);
+    std::printf("refusal messages begin\n");
+    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
+    std::printf("refusal messages end\n");
     std::printf("keygen: calls %d, refusals %d, failures %d\n", calls, refused, g_fail.load());
     return g_fail.load() ? 1 : 0;
 }

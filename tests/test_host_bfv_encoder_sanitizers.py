@@ -5,11 +5,12 @@ first and the last word of everything a kernel would read or write, so a wrong b
 import os
 import subprocess
 
-from bfv_encoder_host_build import build_encoder_driver
+from host_stub_build import build_host_driver
 
 
 def test_bfv_encoder_host_side_under_asan_ubsan(tmp_path):
-    exe = build_encoder_driver(str(tmp_path), "bfv_encoder_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan")
+    exe = build_host_driver(str(tmp_path), "bfv_encoder_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan", units=["lr_bfv_encoder"],
+                            stubs=["bfv_encoder_stub"])
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the routes, not the caller's env
     env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)

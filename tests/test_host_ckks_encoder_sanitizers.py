@@ -6,11 +6,12 @@ everything a kernel would read or write, so a wrong buffer size, stride or batch
 import os
 import subprocess
 
-from ckks_encoder_host_build import build_ckks_encoder_driver
+from host_stub_build import build_host_driver
 
 
 def test_ckks_encoder_host_side_under_asan_ubsan(tmp_path):
-    exe = build_ckks_encoder_driver(str(tmp_path), "ckks_encoder_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan")
+    exe = build_host_driver(str(tmp_path), "ckks_encoder_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan", units=["lr_ckks_encoder"],
+                            stubs=["ckks_encoder_stub"])
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the routes, not the caller's env
     env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)

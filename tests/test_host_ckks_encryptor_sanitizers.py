@@ -9,7 +9,7 @@ import subprocess
 
 import pytest
 
-from ckks_encryptor_host_build import build_encryptor_driver
+from host_stub_build import build_host_driver, expected_refusals, refusal_messages
 
 
 @pytest.mark.parametrize("tag,flags,env", [
@@ -17,11 +17,13 @@ from ckks_encryptor_host_build import build_encryptor_driver
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_ckks_encryptor_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_encryptor_driver(str(tmp_path), "ckks_encryptor_driver", flags, tag)
+    exe = build_host_driver(str(tmp_path), "ckks_encryptor_driver", flags, tag, units=["lr_ckks_encryptor"],
+                            stubs=["bfv_encryptor_stub", "ckks_encryptor_stub"])
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the shapes, not the caller's env
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
     assert "failures 0" in res.stdout, res.stdout
+    assert refusal_messages(res.stdout) == expected_refusals("ckks_encryptor_driver")       # the texts that reach the callers, message for message
     calls = int(res.stdout.split("calls ")[1].split(",")[0])
     refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
     # 6 runs (2 degrees x 2 shapes, and 2 on threads) x 2 rounds x 3 batches x 2 forms x 2 levels x 4 entry points; 8 refusals at creation, 33 at the calls

@@ -10,7 +10,7 @@ import subprocess
 
 import pytest
 
-from collective_host_build import build_collective_driver
+from host_stub_build import build_host_driver, expected_refusals, refusal_messages
 
 
 @pytest.mark.parametrize("tag,flags,env", [
@@ -18,12 +18,14 @@ from collective_host_build import build_collective_driver
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_collective_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_collective_driver(str(tmp_path), "collective_driver", flags, tag)
+    exe = build_host_driver(str(tmp_path), "collective_driver", flags, tag, units=["lr_collective"],
+                            stubs=["bfv_encryptor_stub", "ckks_encryptor_stub", "collective_stub"])
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the shapes, not the caller's env
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     print(res.stdout)
     assert res.returncode == 0, (res.stdout[-3000:], res.stderr[-6000:])
     assert "failures 0" in res.stdout, res.stdout
+    assert refusal_messages(res.stdout) == expected_refusals("collective_driver")       # the texts that reach the callers, message for message
     assert res.stdout.count("launches ") == 2 * (1 + 7), res.stdout               # the ModDowns and seven calls, in both shapes
     calls = int(res.stdout.split("calls ")[1].split(",")[0])
     refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
