@@ -791,6 +791,74 @@ int lr_collective_bfv_pcks_share_device(lr_collective *col, const lr_poly *sk, c
 int lr_collective_aggregate(lr_collective *col, int level, const lr_poly *base /* may be NULL */, const lr_poly *const *shares, int n_shares,
                             lr_poly *out);
 
+/* The collective Refresh of dckks and dbfv for a batch of ciphertexts, device-resident, after the sampling: RefreshProtocol.GenShares,
+ * Aggregate, Decrypt, Recode and Recrypt of dckks/public_refresh.go (:43-95 after the drawing of the mask and the noise, :98, :103,
+ * :108-139, :142-147) and GenShares, Aggregate, Decrypt, Recode, Recrypt, Finalize and lift of dbfv/public_refresh.go (:105-160, :163,
+ * :169, :174-179, :182-190, :193-197, :199-205).
+ * lr_refresh owns what the two NewRefreshProtocol constructors build: three pool polys over Q||P for max_batch ciphertexts, and with a
+ * ctxP NewFastBasisExtender(contextQ, contextP), with t NewSimpleScaler(t, contextQ) and deltaMont; further 2^64 mod q_i, the constants
+ * of Recode and a pinned staging buffer with its event.  ctxP = NULL or t = 0 make a handle for the CKKS entry points only: the two BFV
+ * entry points then are LR_ERR_ARG.  max_batch outside 1 .. 65535, N < 8 and a ctxP on another device, of another N or on another stream
+ * are LR_ERR_ARG; more than 64 limbs in Q||P is LR_ERR_UNSUPPORTED.  The work is ordered on ctxQ's stream.
+ * Randomness, drawn by the caller.  e0, e1: [batch][N] bytes as for lr_collective (magnitude at most 127 in bits 0-6, sign in bit 7;
+ * both references sample with sigma = 3.19, bound 19).  CKKS mask: what ring.RandInt(Q_levelStart / 2 nParties) gives per coefficient,
+ * centred (:58-62), as a signed integer in two's complement on W little-endian 64-bit words, word planes [batch][W][N] (word w of
+ * coefficient j of member b at (b W + w) N + j); W = ceil(bitlen(Q_levelStart) / 64) is what lr_refresh_mask_words reports.  Every W-word
+ * value is in the domain and is reduced as the integer it is: out_i = big.Int.Mod(mask, q_i), Euclidean; nParties enters only the caller's
+ * bound.  A Q_levelStart of more than 32 words (2048 bits) is LR_ERR_UNSUPPORTED in every CKKS call and in lr_refresh_mask_words.  BFV
+ * mask: [batch][N] uint64, uniform below t (contextT.NewUniformPoly); lift is applied on the device, and a value >= t is fed to MRed as it
+ * is.  _device forms: the CKKS mask aligned to 8 bytes, the BFV mask to 16, else LR_ERR_ARG.
+ * sk: NTT + Montgomery form, batch 1 or the call's; |Q| limbs for CKKS, |Q| + |P| for BFV (it is read on the rows of P, :141).  Every
+ * other poly has the call's batch.
+ * lr_refresh_ckks_shares: share_decrypt = NTT(mask) + sk c1 + NTT(e0) on limbs 0 .. level_start (:66, :74, :78, :84-85), limbs above
+ *   not touched; share_recrypt = -(NTT(mask) + sk crs + NTT(e1)) over all of Q (:68, :75, :81, :88-89, :92); every addition with its
+ *   CRed in this order, Neg as q_i - x (a zero is stored as q_i).  c1: NTT domain, level_start + 1 limbs; crs: NTT domain, |Q| limbs.
+ *   Default shape: the mask is reduced and transformed once over all of Q and its first level_start + 1 rows serve both shares; e0 is
+ *   expanded on limbs 0 .. level_start only; one pass per row computes both shares.
+ * lr_refresh_ckks_recode (:108-139): in, NTT domain, canonical residues on limbs 0 .. level_start -> out, NTT domain over all of Q, of
+ *   v = the CRT of the input rows in [0, Q_ls), v >= Q_ls >> 1 => v -= Q_ls (Cmp gives 1 or 0), out_i = v mod q_i (Euclidean).  out may be
+ *   in.  The integer is held as mixed-radix digits (Garner), never as words.  Default shape: rows 0 .. level_start of out are copied from
+ *   in (v mod q_i is the input's residue there), only the new rows are computed and transformed.  level_start = |Q| - 1 is legal.
+ * lr_refresh_ckks_finalize: Decrypt's AddLvl (:104), Recode, Recrypt's Add (:144) into out0 over all of Q; out0 may be c0.  ct[1] =
+ *   crs.CopyNew() (:146) stays the caller's copy.
+ * lr_refresh_bfv_shares: share_decrypt = ModDownSplitedPQ(P InvNTT(sk NTT(c1)) + e0 on Q, e0's rows of P) + lift(mask) (:116-137, :156);
+ *   share_recrypt = ModDownPQ(InvNTT(-sk NTT(crs)) + e1 over Q||P) - lift(mask) (:140-149, :159).  c1 and the shares: coefficient domain,
+ *   |Q| limbs; crs: coefficient domain, |Q| + |P| limbs.  Deviation: the reference's rfp.hP is never zeroed (cks.hP is,
+ *   dbfv/keyswitching.go:108), so a second GenShares on one Go object accumulates unreduced noise; every call here behaves as the first
+ *   call on a fresh RefreshProtocol.  (0, sign 0) leaves the residue p_j itself in hP; the default shape writes 0 there, which changes no
+ *   bit of the ModDown's output (tests/test_oracle_refresh.py); the call-by-call shape feeds p_j literally.
+ * lr_refresh_bfv_finalize: out0 = lift(SimpleScaler.Scale(c0 + share_decrypt)) + share_recrypt (:170, :177-178, :185), out1 =
+ *   ModDownPQ(|Q| - 1, crs) (:188); out0 may be c0.
+ * lr_refresh_aggregate: lr_collective_aggregate without a base, over limbs 0 .. level: Aggregate of both protocols for n_shares parties
+ *   in their order; out may be any of the shares.
+ * Every input is left unchanged.  Refusals: LR_ERR_ARG: a null argument, a poly of another context, an output that shares memory with an
+ * input or the other output (but for the aliases named above), a misaligned _device mask, a BFV call on a CKKS-only handle, ctxQ and
+ * ctxP on different streams at the time of a call; LR_ERR_SHAPE: batch < 1 or > max_batch, a poly with too few limbs, a poly whose batch
+ * differs from the call's, a level outside 0 .. |Q| - 1, n_shares < 1; LR_ERR_UNSUPPORTED: the two named above.
+ * Host forms stage mask and noise through the pinned buffer (the caller's arrays are free on return, the call is asynchronous); _device
+ * forms take the same bytes in device memory: kernels only, no host copy, no synchronisation.  lr_options::no_epilogue selects the
+ * reference's call-by-call shape; both shapes give the same bits. */
+typedef struct lr_refresh lr_refresh;
+int lr_refresh_create(lr_context *ctxQ, lr_context *ctxP /* NULL: CKKS only */, uint64_t t /* 0: CKKS only */, int max_batch, lr_refresh **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_refresh_create_ex(lr_context *ctxQ, lr_context *ctxP, uint64_t t, int max_batch, const lr_options *opt, lr_refresh **out);
+int lr_refresh_destroy(lr_refresh *r);
+int lr_refresh_mask_words(const lr_refresh *r, int level_start, int *words);
+int lr_refresh_ckks_shares(lr_refresh *r, int level_start, const lr_poly *sk, const lr_poly *c1, const lr_poly *crs, const uint64_t *mask,
+                           const uint8_t *e0, const uint8_t *e1, int batch, lr_poly *share_decrypt, lr_poly *share_recrypt);
+int lr_refresh_ckks_shares_device(lr_refresh *r, int level_start, const lr_poly *sk, const lr_poly *c1, const lr_poly *crs, const void *mask,
+                                  const void *e0, const void *e1, int batch, lr_poly *share_decrypt, lr_poly *share_recrypt);
+int lr_refresh_ckks_recode(lr_refresh *r, int level_start, const lr_poly *in, lr_poly *out);
+int lr_refresh_ckks_finalize(lr_refresh *r, int level_start, const lr_poly *c0, const lr_poly *share_decrypt, const lr_poly *share_recrypt,
+                             lr_poly *out0);
+int lr_refresh_bfv_shares(lr_refresh *r, const lr_poly *sk, const lr_poly *c1, const lr_poly *crs, const uint64_t *mask, const uint8_t *e0,
+                          const uint8_t *e1, int batch, lr_poly *share_decrypt, lr_poly *share_recrypt);
+int lr_refresh_bfv_shares_device(lr_refresh *r, const lr_poly *sk, const lr_poly *c1, const lr_poly *crs, const void *mask, const void *e0,
+                                 const void *e1, int batch, lr_poly *share_decrypt, lr_poly *share_recrypt);
+int lr_refresh_bfv_finalize(lr_refresh *r, const lr_poly *c0, const lr_poly *crs, const lr_poly *share_decrypt, const lr_poly *share_recrypt,
+                            lr_poly *out0, lr_poly *out1);
+int lr_refresh_aggregate(lr_refresh *r, int level, const lr_poly *const *shares, int n_shares, lr_poly *out);
+
 /* ------------------------------------------------------------------ multi-device ------ */
 /* a batch of independent ciphertexts shards across the GPUs of a node by contiguous blocks (replicated contexts, tables
  * and keys, created per device with lr_context_create(..., device, ...)); nothing crosses devices but finished results.  The reference's

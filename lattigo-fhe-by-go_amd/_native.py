@@ -191,6 +191,18 @@ SYMBOLS = {
     "lr_collective_ckks_pcks_share_device": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
     "lr_collective_bfv_pcks_share_device": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
     "lr_collective_aggregate": [vp, i32, vp, C.POINTER(vp), i32, vp],
+    "lr_refresh_create": [vp, vp, u64, i32, C.POINTER(vp)],
+    "lr_refresh_create_ex": [vp, vp, u64, i32, vp, C.POINTER(vp)],
+    "lr_refresh_destroy": [vp],
+    "lr_refresh_mask_words": [vp, i32, C.POINTER(i32)],
+    "lr_refresh_ckks_shares": [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_refresh_ckks_shares_device": [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_refresh_ckks_recode": [vp, i32, vp, vp],
+    "lr_refresh_ckks_finalize": [vp, i32, vp, vp, vp, vp],
+    "lr_refresh_bfv_shares": [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_refresh_bfv_shares_device": [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_refresh_bfv_finalize": [vp, vp, vp, vp, vp, vp, vp],
+    "lr_refresh_aggregate": [vp, i32, C.POINTER(vp), i32, vp],
     "lr_bfv_decryptor_create": [vp, i32, C.POINTER(vp)],
     "lr_bfv_decryptor_destroy": [vp],
     "lr_bfv_decrypt": [vp, C.POINTER(vp), i32, vp, vp, i32],

@@ -24,26 +24,6 @@ struct lr_collective : lr_host::QpHandle {
 namespace lr_host {
 namespace {
 
-// the same words, poly for poly: what an element-wise pass may read and write at once
-bool same_poly(const lr_poly *a, const lr_poly *b) { return a->d == b->d && a->batch == b->batch && (a->batch == 1 || a->stride() == b->stride()); }
-
-int check_call(const lr_collective *h, int level, int batch) {
-    if (level < 0 || level + 1 > h->nQ) return fail(LR_ERR_SHAPE, "collective: level out of range");
-    if (batch < 1) return fail(LR_ERR_SHAPE, "collective: batch must be at least 1");
-    if (batch > h->max_batch) return fail(LR_ERR_SHAPE, "collective: batch exceeds the handle's max_batch");
-    return same_stream(h->cQ, h->cP);
-}
-
-int check_outputs(const lr_poly *const *outs, int n_outs, const lr_poly *const *ins, int n_ins) {
-    for (int o = 0; o < n_outs; ++o) {
-        for (int i = 0; i < n_ins; ++i)
-            if (overlap(outs[o], ins[i])) return fail(LR_ERR_ARG, "collective: an output shares memory with an input");
-        for (int j = 0; j < o; ++j)
-            if (overlap(outs[o], outs[j])) return fail(LR_ERR_ARG, "collective: the two outputs share memory");
-    }
-    return LR_OK;
-}
-
 // the rows of Q||P a call at `level` reads: limbs 0 .. level of Q and the rows of P; one run of rows at the top level, two below it
 struct Span { int row0, count; };
 int spans_of(const lr_collective *h, int level, Span s[2]) {
@@ -103,7 +83,7 @@ int check_cks(const lr_collective *h, int level, const lr_poly *sk_in, const lr_
     LR_TRY(h->check_poly(c1, level + 1, batch, false, "the ciphertext"));
     LR_TRY(h->check_poly(share, level + 1, batch, false, "the share"));
     const lr_poly *outs[1] = {share}, *ins[3] = {sk_in, sk_out, c1};
-    return check_outputs(outs, 1, ins, 3);
+    return check_outputs(h, outs, 1, ins, 3);
 }
 
 // CKSProtocol.GenShare of dckks (dckks/keyswitching.go:62-94)
@@ -171,7 +151,7 @@ int check_pcks(const lr_collective *h, int level, const lr_poly *sk, const lr_po
     LR_TRY(h->check_poly(o0, level + 1, batch, false, "the share"));
     LR_TRY(h->check_poly(o1, level + 1, batch, false, "the share"));
     const lr_poly *outs[2] = {o0, o1}, *ins[4] = {sk, pk0, pk1, c1};
-    return check_outputs(outs, 2, ins, 4);
+    return check_outputs(h, outs, 2, ins, 4);
 }
 
 // SampleTernaryMontgomeryNTT over Q||P (dckks/public_keyswitching.go:68, dbfv :116) into P.p[2]
@@ -281,64 +261,6 @@ int bfv_pcks_share(lr_collective *h, const lr_poly *sk, const lr_poly *pk0, cons
     return run_ewise(cQ, LR_ADD, h->nQ, batch, o0->d, o0->stride(), P.p[2], P.stride, o0->d, o0->stride(), nullptr);  // :144
 }
 
-// AggregateShares over n_shares parties and KeySwitch's Add (dckks/keyswitching.go:99-108 and its three twins)
-int aggregate(lr_collective *h, int level, const lr_poly *base, const lr_poly *const *shares, int n_shares, lr_poly *out) {
-    if (!h || !shares || !out) return fail(LR_ERR_ARG, "null argument");
-    if (n_shares < 1) return fail(LR_ERR_SHAPE, "collective: n_shares must be at least 1");
-    const int batch = out->batch;
-    LR_TRY(check_call(h, level, batch));
-    LR_TRY(h->check_poly(out, level + 1, batch, false, "the output"));
-    if (base) {
-        LR_TRY(h->check_poly(base, level + 1, batch, false, "the base"));
-        if (overlap(out, base) && !same_poly(out, base)) return fail(LR_ERR_ARG, "collective: the output overlaps the base without being it");
-    }
-    for (int k = 0; k < n_shares; ++k) {
-        if (!shares[k]) return fail(LR_ERR_ARG, "null argument");
-        LR_TRY(h->check_poly(shares[k], level + 1, batch, false, "a share"));
-        if (overlap(out, shares[k]) && !same_poly(out, shares[k])) return fail(LR_ERR_ARG, "collective: the output overlaps a share without being it");
-    }
-    LR_HIP(hipSetDevice(h->device));
-    lr_context *cQ = h->cQ;
-    const Pools P = pools_of(h, h->d_pool, batch);
-    const int L1 = level + 1;
-    if (h->call_by_call) {     // n_shares - 1 Context.Add calls, then KeySwitch's; the running sum lives in the pool: out may be base or a share
-        const u64 *acc = shares[0]->d;
-        long long acc_stride = shares[0]->stride();
-        for (int k = 1; k < n_shares; ++k) {
-            const bool last = k == n_shares - 1 && !base;
-            u64 *dst = last ? out->d : P.p[0];
-            const long long dst_stride = last ? out->stride() : P.stride;
-            LR_TRY(run_ewise(cQ, LR_ADD, L1, batch, acc, acc_stride, shares[k]->d, shares[k]->stride(), dst, dst_stride, nullptr));
-            acc = dst;
-            acc_stride = dst_stride;
-        }
-        if (base) return run_ewise(cQ, LR_ADD, L1, batch, base->d, base->stride(), acc, acc_stride, out->d, out->stride(), nullptr);
-        if (n_shares == 1) return run_ewise(cQ, LR_COPY, L1, batch, acc, acc_stride, nullptr, 0, out->d, out->stride(), nullptr);
-        return LR_OK;
-    }
-    // kFoldSharesPerLaunch shares per pass; a further pass takes the running sum, in the pool, as its first term
-    for (int first = 0; first < n_shares;) {
-        FoldLaunch F;
-        std::memset(&F, 0, sizeof F);
-        int count = 0;
-        if (first > 0) F.share[count++] = FoldShareRef{P.p[0], P.stride};
-        while (count < kFoldSharesPerLaunch && first < n_shares) {
-            F.share[count++] = FoldShareRef{shares[first]->d, shares[first]->stride()};
-            ++first;
-        }
-        const bool last = first == n_shares;
-        F.count = count;
-        F.base = last && base ? base->d : nullptr;
-        F.base_stride = base ? base->stride() : 0;
-        F.out = last ? out->d : P.p[0];
-        F.out_stride = last ? out->stride() : P.stride;
-        F.n = (int)cQ->h.N;
-        F.lp = h->d_lp;
-        LR_HIP(launch_fold(F, L1, batch, cQ->stream));
-    }
-    return LR_OK;
-}
-
 }  // namespace
 }  // namespace lr_host
 
@@ -424,5 +346,5 @@ extern "C" int lr_collective_bfv_pcks_share_device(lr_collective *h, const lr_po
     });
 }
 extern "C" int lr_collective_aggregate(lr_collective *h, int level, const lr_poly *base, const lr_poly *const *shares, int n_shares, lr_poly *out) {
-    return guarded([&]() -> int { return aggregate(h, level, base, shares, n_shares, out); });
+    return guarded([&]() -> int { return fold_shares(h, h ? h->d_pool : nullptr, level, base, shares, n_shares, out); });
 }

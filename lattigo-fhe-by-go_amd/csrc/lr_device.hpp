@@ -542,6 +542,65 @@ struct FoldLaunch {
 };
 hipError_t launch_fold(const FoldLaunch &L, int limbs, int batch, hipStream_t stream);
 
+// ---- dckks / dbfv Refresh (lr_refresh.hip): RefreshProtocol.GenShares, Recode, Recrypt, Finalize ----
+// out[b][i][j] = big.Int.Mod(mask[b][j], q_i) for i < limbs: SetCoefficientsBigint(Lvl) (ring/ring_context.go:343-367) of a signed integer
+// in two's complement on `words` little-endian 64-bit words, word planes [batch][words][N]
+struct RefreshMaskLaunch {
+    const u64 *mask;
+    u64 *out;
+    long long out_stride;
+    int n, words;
+    LimbScalars two64;                 // 2^64 mod q_i
+    const LimbParams *lp;
+};
+hipError_t launch_refresh_mask(const RefreshMaskLaunch &L, int limbs, int batch, hipStream_t stream);
+// dckks GenShares :78-92 on one row of Q, NTT domain.  Rows below dec_limbs: dec = CRed(CRed(mask + MRed(sk, c1)) + e0); every row:
+// rec = q - CRed(CRed(mask + MRed(sk, crs)) + e1)
+struct RefreshCkksShareLaunch {
+    const u64 *mask, *e0, *e1, *sk, *c1, *crs;
+    u64 *dec, *rec;
+    long long r_stride, sk_stride, c1_stride, crs_stride, dec_stride, rec_stride;   // r_stride: of mask, e0 and e1 (sk: 0 = broadcast)
+    int n, dec_limbs;
+    const LimbParams *lp;
+};
+hipError_t launch_refresh_ckks_share(const RefreshCkksShareLaunch &L, int limbs, int batch, hipStream_t stream);
+// dckks Recode :114-136 per coefficient, coefficient domain: v = the CRT of rows 0 .. ls of `in` in [0, Q_ls) as mixed-radix digits (Garner),
+// v >= Q_ls >> 1 => v -= Q_ls, out[i] = v mod q_i (Euclidean) for rows row0 .. limbs - 1 of `out`
+struct RefreshRecodeLaunch {
+    const u64 *in;
+    u64 *out;
+    long long in_stride, out_stride;
+    int n, ls, row0, limbs;
+    const u64 *qmod;                   // [limbs][limbs]: q_m mod q_k at [k][m]
+    const u64 *ginv;                   // [limbs]: (q_0 ... q_(k-1))^-1 mod q_k
+    const u64 *hdig;                   // [ls + 1]: the mixed-radix digits of Q_ls >> 1
+    const u64 *qls;                    // [limbs]: Q_ls mod q_i
+    const LimbParams *lp;
+};
+hipError_t launch_refresh_recode(const RefreshRecodeLaunch &L, int batch, hipStream_t stream);
+// dbfv GenShares :117-122 and :141-142 on one row of Q||P, NTT domain, in place: rows of Q: a = MRed(MRed(sk, a), MForm(P mod q));
+// every row: b = q - MRed(sk, b) (Neg: a zero becomes q)
+struct RefreshBfvProductLaunch {
+    const u64 *sk;
+    u64 *a, *b;
+    long long sk_stride, stride;
+    int n, nQ;
+    LimbScalars pmont;
+    const LimbParams *lp;              // of contextQP
+};
+hipError_t launch_refresh_bfv_product(const RefreshBfvProductLaunch &L, int rows, int batch, hipStream_t stream);
+// dbfv lift :199-205 and what follows it: m = MRed(row, deltaMont_i); dec = CRed(dec + m) and, with rec, rec = CRed(rec + q - m) (GenShares
+// :153-159); plus: dec = CRed(m + plus) (Recode's lift and Recrypt's Add, :178-185)
+struct RefreshBfvLiftLaunch {
+    const u64 *row, *plus;             // row: [batch][N]
+    u64 *dec, *rec;
+    long long plus_stride, dec_stride, rec_stride;
+    int n;
+    const u64 *delta_mont;             // [limbs]
+    const LimbParams *lp;
+};
+hipError_t launch_refresh_bfv_lift(const RefreshBfvLiftLaunch &L, int limbs, int batch, hipStream_t stream);
+
 // ---- ckks.Encoder (lr_ckks_encode.hip): Encode / Decode of ckks/encoder.go for a batch of plaintexts ----
 struct Cplx { double re, im; };                 // a complex128 as Go lays it out
 constexpr int kCkksFusedMaxLogSlots = 13;       // the fused kernels hold 16 * slots bytes in one CU's LDS: 128 KiB of the 160

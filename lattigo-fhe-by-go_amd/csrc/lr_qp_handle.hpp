@@ -1,5 +1,5 @@
 // lr_qp_handle.hpp -- what the handles that sample over Q||P from the samplers' compact bytes share: lr_bfv_encryptor, lr_ckks_encryptor,
-// lr_keygen and lr_collective derive from QpHandle and include this header; nothing else does.  Here, once: the two contexts and their
+// lr_keygen, lr_collective and lr_refresh derive from QpHandle and include this header; nothing else does.  Here, once: the two contexts and their
 // limb constants side by side, the Montgomery scalars of the ternary sampler and of MulScalarBigint(P), the staging of host randomness
 // through a pinned buffer, the checks every creation and every call repeat, a Context call and a transform of contextQP as two launches,
 // and the one place where each of TernaryLaunch, Mul2Launch, CkksExpandLaunch and NoiseLaunch is filled.  What composes these into a
@@ -253,6 +253,88 @@ inline int noise_qp(QpHandle *h, int add, int comps, const unsigned char *const 
     L.add = add;
     L.lp = h->d_lp;
     LR_HIP(launch_bfv_noise(L, comps, rows, batch, h->cQ->stream));
+    return LR_OK;
+}
+
+// the same words, poly for poly: what an element-wise pass may read and write at once
+inline bool same_poly(const lr_poly *a, const lr_poly *b) { return a->d == b->d && a->batch == b->batch && (a->batch == 1 || a->stride() == b->stride()); }
+
+// the outputs of a share call against its inputs and against each other; output 0 may be the input `may_be` as a whole poly
+inline int check_outputs(const QpHandle *h, const lr_poly *const *outs, int n_outs, const lr_poly *const *ins, int n_ins, const lr_poly *may_be = nullptr) {
+    for (int o = 0; o < n_outs; ++o) {
+        for (int i = 0; i < n_ins; ++i)
+            if (overlap(outs[o], ins[i]) && !(ins[i] == may_be && o == 0 && same_poly(outs[o], ins[i])))
+                return h->refuse(LR_ERR_ARG, "an output shares memory with an input");
+        for (int j = 0; j < o; ++j)
+            if (overlap(outs[o], outs[j])) return h->refuse(LR_ERR_ARG, "the two outputs share memory");
+    }
+    return LR_OK;
+}
+
+// what every call of lr_collective and lr_refresh refuses first: the level, the batch, two contexts on two streams
+inline int check_call(const QpHandle *h, int level, int batch) {
+    if (level < 0 || level + 1 > h->nQ) return h->refuse(LR_ERR_SHAPE, "level out of range");
+    if (batch < 1) return h->refuse(LR_ERR_SHAPE, "batch must be at least 1");
+    if (batch > h->max_batch) return h->refuse(LR_ERR_SHAPE, "batch exceeds the handle's max_batch");
+    return h->cP ? same_stream(h->cQ, h->cP) : LR_OK;
+}
+
+// AggregateShares over n_shares parties and, with a base, KeySwitch's Add (dckks/keyswitching.go:99-108 and its three twins; Aggregate of
+// both RefreshProtocols): lr_collective_aggregate and lr_refresh_aggregate.  `pool` holds one poly over Q||P per member of the batch.
+inline int fold_shares(QpHandle *h, u64 *pool, int level, const lr_poly *base, const lr_poly *const *shares, int n_shares, lr_poly *out) {
+    if (!h || !shares || !out) return fail(LR_ERR_ARG, "null argument");
+    if (n_shares < 1) return h->refuse(LR_ERR_SHAPE, "n_shares must be at least 1");
+    const int batch = out->batch;
+    LR_TRY(check_call(h, level, batch));
+    LR_TRY(h->check_poly(out, level + 1, batch, false, "the output"));
+    if (base) {
+        LR_TRY(h->check_poly(base, level + 1, batch, false, "the base"));
+        if (overlap(out, base) && !same_poly(out, base)) return h->refuse(LR_ERR_ARG, "the output overlaps the base without being it");
+    }
+    for (int k = 0; k < n_shares; ++k) {
+        if (!shares[k]) return fail(LR_ERR_ARG, "null argument");
+        LR_TRY(h->check_poly(shares[k], level + 1, batch, false, "a share"));
+        if (overlap(out, shares[k]) && !same_poly(out, shares[k])) return h->refuse(LR_ERR_ARG, "the output overlaps a share without being it");
+    }
+    LR_HIP(hipSetDevice(h->device));
+    lr_context *cQ = h->cQ;
+    const Pools P = pools_of(h, pool, batch);
+    const int L1 = level + 1;
+    if (h->call_by_call) {     // n_shares - 1 Context.Add calls, then KeySwitch's; the running sum lives in the pool: out may be base or a share
+        const u64 *acc = shares[0]->d;
+        long long acc_stride = shares[0]->stride();
+        for (int k = 1; k < n_shares; ++k) {
+            const bool last = k == n_shares - 1 && !base;
+            u64 *dst = last ? out->d : P.p[0];
+            const long long dst_stride = last ? out->stride() : P.stride;
+            LR_TRY(run_ewise(cQ, LR_ADD, L1, batch, acc, acc_stride, shares[k]->d, shares[k]->stride(), dst, dst_stride, nullptr));
+            acc = dst;
+            acc_stride = dst_stride;
+        }
+        if (base) return run_ewise(cQ, LR_ADD, L1, batch, base->d, base->stride(), acc, acc_stride, out->d, out->stride(), nullptr);
+        if (n_shares == 1) return run_ewise(cQ, LR_COPY, L1, batch, acc, acc_stride, nullptr, 0, out->d, out->stride(), nullptr);
+        return LR_OK;
+    }
+    // kFoldSharesPerLaunch shares per pass; a further pass takes the running sum, in the pool, as its first term
+    for (int first = 0; first < n_shares;) {
+        FoldLaunch F;
+        std::memset(&F, 0, sizeof F);
+        int count = 0;
+        if (first > 0) F.share[count++] = FoldShareRef{P.p[0], P.stride};
+        while (count < kFoldSharesPerLaunch && first < n_shares) {
+            F.share[count++] = FoldShareRef{shares[first]->d, shares[first]->stride()};
+            ++first;
+        }
+        const bool last = first == n_shares;
+        F.count = count;
+        F.base = last && base ? base->d : nullptr;
+        F.base_stride = base ? base->stride() : 0;
+        F.out = last ? out->d : P.p[0];
+        F.out_stride = last ? out->stride() : P.stride;
+        F.n = (int)cQ->h.N;
+        F.lp = h->d_lp;
+        LR_HIP(launch_fold(F, L1, batch, cQ->stream));
+    }
     return LR_OK;
 }
 

@@ -843,7 +843,7 @@ def NewBfvEncoder(contextQ, t, max_batch=1, options=None):  # bfv.NewEncoder, bf
 
 
 class _QpHandle:
-    """What BfvEncryptor, CkksEncryptor, KeyGenerator and Collective share (csrc/lr_qp_handle.hpp): a handle over contextQ and contextP
+    """What BfvEncryptor, CkksEncryptor, KeyGenerator, Collective and Refresh share (csrc/lr_qp_handle.hpp): a handle over contextQ and contextP
     with a max_batch, made by <_abi>_create / <_abi>_create_ex and freed by <_abi>_destroy, and the check of the compact randomness'
     size.  contextP None goes to the library as NULL: it says which handles and which calls need a P."""
 
@@ -1246,6 +1246,87 @@ class Collective(_QpHandle):
 
 def NewCollective(contextQ, contextP, max_batch=1, options=None):  # NewCKSProtocol / NewPCKSProtocol of dckks and dbfv
     return Collective(contextQ, contextP, max_batch, options)
+
+
+class Refresh(_QpHandle):
+    """RefreshProtocol of dckks and dbfv (dckks/public_refresh.go, dbfv/public_refresh.go) for a batch of ciphertexts on the device
+    (lr_refresh), after the sampling.  e = (e0, e1), uint8 [batch, N] each, the encryptors' bytes.  CKKS mask: uint64 [batch, W, N] word
+    planes of signed integers, W = MaskWords(levelStart) (sampling.mask_word_planes packs Python integers); BFV mask: uint64 [batch, N]
+    below t.  sk: Poly of contextQ in NTT + Montgomery form, batch 1 or the call's, over Q (CKKS) or Q||P (BFV).  CKKS polys are in the NTT
+    domain, BFV polys in the coefficient domain (crs over Q||P).  contextP None or t = 0: the CKKS entry points only.  The batch of a call
+    is that of its output."""
+
+    _abi = "lr_refresh"
+
+    def __init__(self, contextQ, contextP=None, t=0, max_batch=1, options=None):
+        self.contextQ, self.contextP, self.t, self.max_batch = contextQ, contextP, int(t), int(max_batch)
+        h = C.c_void_p()
+        hP = None if contextP is None else contextP.h
+        if options is None:
+            check(lib().lr_refresh_create(contextQ.h, hP, self.t, max_batch, C.byref(h)))
+        else:
+            check(lib().lr_refresh_create_ex(contextQ.h, hP, self.t, max_batch, C.byref(options), C.byref(h)))
+        self.h = h
+
+    def MaskWords(self, levelStart):
+        w = C.c_int()
+        check(lib().lr_refresh_mask_words(self.h, levelStart, C.byref(w)))
+        return w.value
+
+    def _random(self, mask, e, batch, mask_words):
+        N = self.contextQ.N
+        m = np.ascontiguousarray(mask, dtype=np.uint64)
+        if m.size != batch * mask_words * N:
+            raise LatticeRingError(3, "expected %d x %d x %d mask words, got %s" % (batch, mask_words, N, m.shape))      # LR_ERR_SHAPE
+        arrays = [m, self._bytes(e[0], batch, N), self._bytes(e[1], batch, N)]
+        return arrays, [a.ctypes.data_as(C.c_void_p) for a in arrays]
+
+    def CkksGenShares(self, sk, levelStart, c1, crs, mask, e, shares):  # dckks/public_refresh.go:43; shares = (shareDecrypt, shareRecrypt)
+        batch = shares[0].batch
+        keep, p = self._random(mask, e, batch, self.MaskWords(levelStart))
+        check(lib().lr_refresh_ckks_shares(self.h, levelStart, sk.h, c1.h, crs.h, p[0], p[1], p[2], batch, shares[0].h, shares[1].h))
+        return shares
+
+    def CkksRecode(self, levelStart, polIn, polOut):  # :108
+        check(lib().lr_refresh_ckks_recode(self.h, levelStart, polIn.h, polOut.h))
+        return polOut
+
+    def CkksFinalize(self, levelStart, c0, shares, out0):  # Decrypt :103, Recode :108, Recrypt :142
+        check(lib().lr_refresh_ckks_finalize(self.h, levelStart, c0.h, shares[0].h, shares[1].h, out0.h))
+        return out0
+
+    def BfvGenShares(self, sk, c1, crs, mask, e, shares):  # dbfv/public_refresh.go:105
+        batch = shares[0].batch
+        keep, p = self._random(mask, e, batch, 1)
+        check(lib().lr_refresh_bfv_shares(self.h, sk.h, c1.h, crs.h, p[0], p[1], p[2], batch, shares[0].h, shares[1].h))
+        return shares
+
+    def BfvFinalize(self, c0, crs, shares, ctOut):  # :193; ctOut = (out0, out1)
+        check(lib().lr_refresh_bfv_finalize(self.h, c0.h, crs.h, shares[0].h, shares[1].h, ctOut[0].h, ctOut[1].h))
+        return ctOut
+
+    def Aggregate(self, shares, out, level):
+        """Aggregate over all the parties' shares in their order; out may be one of the shares"""
+        hs = (C.c_void_p * len(shares))(*[s.h.value for s in shares])
+        check(lib().lr_refresh_aggregate(self.h, level, hs, len(shares), out.h))
+        return out
+
+    # the same with the randomness in device memory (pointers); stream-ordered
+    def CkksGenSharesDevice(self, sk, levelStart, c1, crs, mask_ptr, e_ptrs, shares):
+        v = C.c_void_p
+        check(lib().lr_refresh_ckks_shares_device(self.h, levelStart, sk.h, c1.h, crs.h, v(mask_ptr), v(e_ptrs[0]), v(e_ptrs[1]),
+                                                  shares[0].batch, shares[0].h, shares[1].h))
+        return shares
+
+    def BfvGenSharesDevice(self, sk, c1, crs, mask_ptr, e_ptrs, shares):
+        v = C.c_void_p
+        check(lib().lr_refresh_bfv_shares_device(self.h, sk.h, c1.h, crs.h, v(mask_ptr), v(e_ptrs[0]), v(e_ptrs[1]), shares[0].batch,
+                                                 shares[0].h, shares[1].h))
+        return shares
+
+
+def NewRefresh(contextQ, contextP=None, t=0, max_batch=1, options=None):  # NewRefreshProtocol of dckks and dbfv
+    return Refresh(contextQ, contextP, t, max_batch, options)
 
 
 class BfvBatcher:

@@ -53,3 +53,20 @@ def random_u64(shape, seed=DEFAULT_SEED):
     """Full-range 64-bit values (NewPolyUniform, ring/ring_object.go:26-47)."""
     n = int(np.prod(shape))
     return splitmix64(seed, n).reshape(shape)
+
+
+def mask_word_planes(values, words):
+    """Python integers -> the CKKS mask of lr_refresh: two's complement on `words` little-endian 64-bit words, as word planes.  values:
+    [N] or [batch][N] integers in [-2^(64 words - 1), 2^(64 words - 1)); returns uint64 [words, N] or [batch, words, N]."""
+    if len(values) and not isinstance(values[0], (int, np.integer)):
+        return np.stack([mask_word_planes(v, words) for v in values])
+    lo, hi = -(1 << (64 * words - 1)), 1 << (64 * words - 1)
+    out = np.empty((words, len(values)), dtype=np.uint64)
+    for j, v in enumerate(values):
+        v = int(v)
+        if not lo <= v < hi:
+            raise ValueError("mask coefficient %d does not fit %d words" % (j, words))
+        v &= (1 << (64 * words)) - 1
+        for w in range(words):
+            out[w, j] = (v >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+    return out

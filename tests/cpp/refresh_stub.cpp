@@ -1,0 +1,112 @@
+// Stand-ins for the launchers of lr_refresh.hip, for the CPU-sanitizer build of the Refresh handle's host side
+// (tests/test_host_refresh_sanitizers.py); the expansions, the fold, lift and the scaler it shares with other handles are served by
+// ckks_encryptor_stub.cpp, bfv_encryptor_stub.cpp, collective_stub.cpp, bfv_encoder_stub.cpp and hipstub/stub_launch.cpp, which stay as
+// they are.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.  A stub counts its launch and touches the first and the last
+// byte of everything the real kernel would read or write at the addresses the launch names: "device" memory is malloc'ed at its exact
+// size, so a wrong size, stride, level or word count in the host code is an AddressSanitizer report.
+#include <atomic>
+
+#include "lr_device.hpp"
+
+namespace lr {
+
+std::atomic<unsigned long long> g_refresh_mask_launches{0}, g_refresh_share_launches{0}, g_refresh_recode_launches{0}, g_refresh_product_launches{0},
+    g_refresh_lift_launches{0};
+
+namespace {
+thread_local volatile u64 t_sink;
+template <class T>
+void rd(const T *p, long long count) {
+    if (count <= 0) return;
+    t_sink = (u64)((const volatile unsigned char *)p)[0];
+    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
+}
+void wr(u64 *p, long long count) {
+    if (count <= 0) return;
+    p[0] = p[0];
+    p[count - 1] = p[count - 1];
+}
+}  // namespace
+
+hipError_t launch_refresh_mask(const RefreshMaskLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || L.words < 1 || L.words > kCkksCrtMaxWords || limbs > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    g_refresh_mask_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    rd(L.mask, (long long)batch * L.words * L.n);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) wr(L.out + b * L.out_stride + (long long)i * L.n, L.n);
+    return hipSuccess;
+}
+
+hipError_t launch_refresh_ckks_share(const RefreshCkksShareLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || limbs > kMaxLimbs || L.dec_limbs < 1 || L.dec_limbs > limbs || batch > 65535) return hipErrorInvalidValue;
+    g_refresh_share_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.mask + b * L.r_stride + row, L.n);
+            rd(L.e1 + b * L.r_stride + row, L.n);
+            rd(L.sk + b * L.sk_stride + row, L.n);
+            rd(L.crs + b * L.crs_stride + row, L.n);
+            wr(L.rec + b * L.rec_stride + row, L.n);
+            if (i < L.dec_limbs) {
+                rd(L.e0 + b * L.r_stride + row, L.n);
+                rd(L.c1 + b * L.c1_stride + row, L.n);
+                wr(L.dec + b * L.dec_stride + row, L.n);
+            }
+        }
+    return hipSuccess;
+}
+
+hipError_t launch_refresh_recode(const RefreshRecodeLaunch &L, int batch, hipStream_t) {
+    if (batch <= 0 || L.row0 >= L.limbs) return hipSuccess;
+    if (L.n < 2 || L.limbs > kMaxLimbs || L.ls < 0 || L.ls >= L.limbs || L.row0 < 0 || batch > 65535) return hipErrorInvalidValue;
+    g_refresh_recode_launches.fetch_add(1);
+    rd(L.lp, L.limbs);
+    rd(L.qmod, (long long)L.limbs * L.limbs);
+    rd(L.ginv, L.limbs);
+    rd(L.hdig, L.ls + 1);
+    rd(L.qls, L.limbs);
+    for (int b = 0; b < batch; ++b) {
+        for (int i = 0; i <= L.ls; ++i) rd(L.in + b * L.in_stride + (long long)i * L.n, L.n);
+        for (int i = L.row0; i < L.limbs; ++i) wr(L.out + b * L.out_stride + (long long)i * L.n, L.n);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_refresh_bfv_product(const RefreshBfvProductLaunch &L, int rows, int batch, hipStream_t) {
+    if (rows <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || rows > kMaxLimbs || L.nQ < 1 || L.nQ > rows || batch > 65535) return hipErrorInvalidValue;
+    g_refresh_product_launches.fetch_add(1);
+    rd(L.lp, rows);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < rows; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.sk + b * L.sk_stride + row, L.n);
+            if (i < L.nQ) wr(L.a + b * L.stride + row, L.n);
+            wr(L.b + b * L.stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+hipError_t launch_refresh_bfv_lift(const RefreshBfvLiftLaunch &L, int limbs, int batch, hipStream_t) {
+    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535 || !L.dec || (L.plus == nullptr) == (L.rec == nullptr)) return hipErrorInvalidValue;
+    g_refresh_lift_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    rd(L.delta_mont, limbs);
+    rd(L.row, (long long)batch * L.n);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            wr(L.dec + b * L.dec_stride + row, L.n);
+            if (L.rec) wr(L.rec + b * L.rec_stride + row, L.n);
+            if (L.plus) rd(L.plus + b * L.plus_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+}  // namespace lr
