@@ -859,6 +859,107 @@ int lr_refresh_bfv_finalize(lr_refresh *r, const lr_poly *c0, const lr_poly *crs
                             lr_poly *out0, lr_poly *out1);
 int lr_refresh_aggregate(lr_refresh *r, int level, const lr_poly *const *shares, int n_shares, lr_poly *out);
 
+/* The collective key setup of dckks and dbfv for a batch of parties, device-resident, after the sampling: CKGProtocol.GenShare
+ * (dbfv/publickey_gen.go:54-57), the rounds and GenRelinearizationKey of RKGProtocol (dbfv/relinkey_gen.go:215-355) and of
+ * RKGProtocolNaive (dbfv/relinkey_gen_naive.go:59-200), RTGProtocol.genShare and Finalize (dbfv/rotkey_gen.go:139-215), and every
+ * Aggregate* of the four as one n-ary fold.  The dckks twins compute the same lines except where noted.  lr_setup owns what the four
+ * New*Protocol constructors build -- polypool / tmpPoly over Q||P -- plus a pool for the transformed samples of one pass of up to 32
+ * parties, MForm(P mod q_j), the matrixTernaryMontgomery rows of every limb and a pinned staging buffer with its event.  ctxP == NULL is
+ * the reference's "P is empty": only lr_setup_ckg_share and lr_setup_aggregate (batch 1) work, over Q; every other entry point is
+ * LR_ERR_ARG.  max_batch outside 1 .. 65535, N < 8 (a bit plane is N / 8 bytes) and a ctxP on another device or of another N are
+ * LR_ERR_ARG.  The work is ordered on ctxQ's stream.
+ * Every poly is a poly of ctxQ with |Q| + |P| limbs in contextQP's order, in the NTT domain.  sk, u (lr_keygen_secret_key is
+ * NewEphemeralKey's SampleTernaryMontgomeryNTTNew) and pk0, pk1 are in Montgomery form, as lr_keygen writes them; crs and crp are used as
+ * the reference uses them, without an MForm, until a finalize step says otherwise.  beta = ceil(|Q| / |P|); digit i owns rows i |P| ..
+ * min((i + 1) |P|, |Q|) - 1 (the reference's digit loop with its break; its three spellings of the break give the same rows).
+ * Layout: a share of beta polys is one lr_poly of batch beta, member i = share[i]; a share of beta pairs is one lr_poly of batch 2 beta,
+ * member 2 i = [i][0], member 2 i + 1 = [i][1] -- exactly the key image lr_ckks_switch_keys and lr_bfv_relinearize read, so the finalize
+ * steps write keys in place.  crp is one poly of batch beta, read only.  A call serves n_parties parties (RTG: n_keys Galois elements),
+ * 1 <= n <= max_batch; sk and u have batch n, or batch 1 where one key serves the call; the outputs come through a pointer array and need
+ * not be contiguous.  More than 32 parties run as further passes over the pool.
+ * Randomness, drawn by the caller in the order the reference draws it: a noise poly is [N] bytes, magnitude (at most 127) in bits 0-6,
+ * sign in bit 7 (ring/gaussianSampler.go:247: sign 1 -> coeff, sign 0 -> q_j - coeff), one byte deciding the coefficient on every row of
+ * Q||P; a ternary poly is two bit planes of [N / 8] bytes as for lr_keygen_secret_key.
+ * lr_setup_ckg_share: share = CRed(NTT(e) + (q - MRed(sk, crs))) on every row; e = [batch][N]; sk and crs have batch 1 or the call's.
+ *   GenPublicKey is a Set and needs no call: the aggregate share is pk0, crs is pk1.
+ * lr_setup_rkg_round1 (:215-259): share[i] = NTT(e_i); on the rows digit i owns CRed(. + InvMForm(MulScalarBigint(sk, P))); on every row
+ *   CRed(. + (q - MRed(u, crp[i]))).  e = [n][beta][N].
+ * lr_setup_rkg_round2 (:277-299): [i][0] = CRed(MRed(round1[i], sk) + NTT(e1_i)), [i][1] = CRed(NTT(e2_i) + MRed(sk, crp[i])); e =
+ *   [n][beta][2][N], e1_i before e2_i; round1 = the aggregate, one poly of batch beta shared by the call.
+ * lr_setup_rkg_round3 (:322-333): share[i] = CRed(NTT(e_i) + MRed(CRed((u + q) - sk), round2[i][1])); e = [n][beta][N]; round2 = the
+ *   aggregate, batch 2 beta.
+ * lr_setup_rkg_key (:343-355): evk[i][0] = MForm(CRed(round2[i][0] + round3[i])), evk[i][1] = MForm(round2[i][1]); evk_out may be round2
+ *   itself (in place).
+ * lr_setup_rkg_naive_round1 (relinkey_gen_naive.go:59-110): [i][0] = CRed(CRed(NTT(e_i0) + [rows of digit i] InvMForm(P sk)) + MRed(pk0,
+ *   u_i)), [i][1] = CRed(NTT(e_i1) + MRed(pk1, u_i)), u_i = SampleTernaryMontgomeryNTT(0.5) over Q||P; e = [n][beta][2][N] (the reference
+ *   draws the noise of every digit before the first ternary), the planes [n][beta][N / 8].  scheme = LR_SETUP_BFV: these lines.  scheme =
+ *   LR_SETUP_CKKS: dckks/relinkey_gen_naive.go:73-75 draws both noise polys into shareOut[i][0] -- the second draw overwrites the first --
+ *   and shareOut[i][1] gets no noise, MulCoeffsMontgomeryAndAdd landing on whatever the share held.  The device takes the same
+ *   [beta][2][N] bytes, uses e[i][1] for [i][0] and nothing for [i][1], and treats the share as freshly allocated (zero): every call
+ *   behaves as the first call on shares from AllocateShares, the convention lr_refresh set for rfp.hP.  Another scheme is LR_ERR_ARG.
+ * lr_setup_rkg_naive_round2 (:135-166): [i][c] = CRed(CRed(MRed(round1[i][c], sk) + MRed(pk_c, v_i)) + NTT(e_ic)); the same in dckks.
+ * lr_setup_rkg_naive_key (:187-200): MForm of both halves; evk_out may be round2 itself.  pk0, pk1: batch 1.
+ * lr_setup_rtg_share (rotkey_gen.go:139-184) for Galois element g_k: share_k[i] = NTT(e_ki); on the rows digit i owns CRed(. +
+ *   InvMForm(MulScalarBigint(PermuteNTT(sk, g_k), P))); on every row MForm(CRed(. + (q - MRed(crp[i], sk)))).  e = [n_keys][beta][N]; sk
+ *   has batch 1; the elements are read on the host during the call and reduced modulo 2 N.  The map from (rotation type, k) to an element
+ *   stays with the caller, as for lr_keygen_rotation_keys.
+ * lr_setup_rtg_key (:205-215): member 2 i = share[i], member 2 i + 1 = MForm(crp[i]).
+ * lr_setup_aggregate: acc = shares[0]; acc = CRed(acc + shares[k]) for k = 1 .. n_shares - 1 in this order, over ALL rows of Q||P, for
+ *   polys of batch 1, beta or 2 beta (all the same): every Aggregate* body of the four protocols.  One pass reads up to 32 shares; more
+ *   run as further passes over the running sum.  out may be one of the shares; a partial overlap is LR_ERR_ARG.
+ * Every input is left unchanged.  Refusals: LR_ERR_ARG: a null argument, a poly of another context, an output that overlaps an input or
+ * another output (but for the two in-place cases above), ctxQ and ctxP on different streams at the time of a call, an even Galois
+ * element, an unknown scheme, a P-protocol on a handle without ctxP; LR_ERR_SHAPE: n < 1 or n > max_batch, n_shares < 1, a poly with
+ * fewer than |Q| + |P| limbs, a share whose batch is not beta or 2 beta as required, a key poly whose batch is neither 1 nor n;
+ * LR_ERR_UNSUPPORTED, at creation: more than 64 limbs in Q||P; N > 2^30 (the RTG kernel's Galois index is computed in 32 bits).  The
+ * second cannot be reached today: no context of such a degree can be made (its tables alone are 16 GiB per limb), so no test tries it.
+ * Memory: the pool is sized for the widest call, the naive rounds: 3 beta min(max_batch, 32) + 1 polys over Q||P (two noise polys and a
+ * ternary per party and digit, and polypool), plus max(2 beta, 1) for the fold -- at PN15QP880 (21 rows, beta 6) 5.25 MiB per poly, about
+ * 3.0 GiB for max_batch >= 32 and 163 MiB for max_batch = 1; the staging buffer adds max_batch beta (2 N + N / 4) bytes, pinned and on
+ * the device.  A caller that makes one handle per protocol object (the Go overlays do, with max_batch 1) pays the small figure each.
+ * The host forms stage the bytes through the pinned buffer: the caller's arrays are free on return, the call is asynchronous.  The
+ * _device forms take the same bytes in device memory: kernels only, no host copy, no synchronisation.
+ * lr_options::no_epilogue selects the reference's call-by-call shape (one launch per Context call; a sampler's write into a share is a
+ * copy out of the pool); both shapes give the same bits. */
+typedef struct lr_setup lr_setup;
+enum { LR_SETUP_BFV = 0, LR_SETUP_CKKS = 1 };
+int lr_setup_create(lr_context *ctxQ, lr_context *ctxP, int max_batch, lr_setup **out);
+/* the same with explicit options; NULL = the options of ctxQ */
+int lr_setup_create_ex(lr_context *ctxQ, lr_context *ctxP, int max_batch, const lr_options *opt, lr_setup **out);
+int lr_setup_destroy(lr_setup *s);
+int lr_setup_ckg_share(lr_setup *s, const lr_poly *sk, const lr_poly *crs, const uint8_t *e, int batch, lr_poly *share_out);
+int lr_setup_ckg_share_device(lr_setup *s, const lr_poly *sk, const lr_poly *crs, const void *e, int batch, lr_poly *share_out);
+int lr_setup_rkg_round1(lr_setup *s, const lr_poly *u, const lr_poly *sk, const lr_poly *crp, const uint8_t *e, int n_parties,
+                        lr_poly *const *shares);
+int lr_setup_rkg_round1_device(lr_setup *s, const lr_poly *u, const lr_poly *sk, const lr_poly *crp, const void *e, int n_parties,
+                               lr_poly *const *shares);
+int lr_setup_rkg_round2(lr_setup *s, const lr_poly *round1, const lr_poly *sk, const lr_poly *crp, const uint8_t *e, int n_parties,
+                        lr_poly *const *shares);
+int lr_setup_rkg_round2_device(lr_setup *s, const lr_poly *round1, const lr_poly *sk, const lr_poly *crp, const void *e, int n_parties,
+                               lr_poly *const *shares);
+int lr_setup_rkg_round3(lr_setup *s, const lr_poly *round2, const lr_poly *u, const lr_poly *sk, const uint8_t *e, int n_parties,
+                        lr_poly *const *shares);
+int lr_setup_rkg_round3_device(lr_setup *s, const lr_poly *round2, const lr_poly *u, const lr_poly *sk, const void *e, int n_parties,
+                               lr_poly *const *shares);
+int lr_setup_rkg_key(lr_setup *s, const lr_poly *round2, const lr_poly *round3, lr_poly *evk_out);
+int lr_setup_rkg_naive_round1(lr_setup *s, int scheme, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const uint8_t *e,
+                              const uint8_t *u_coeff_bits, const uint8_t *u_sign_bits, int n_parties, lr_poly *const *shares);
+int lr_setup_rkg_naive_round1_device(lr_setup *s, int scheme, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1, const void *e,
+                                     const void *u_coeff_bits, const void *u_sign_bits, int n_parties, lr_poly *const *shares);
+int lr_setup_rkg_naive_round2(lr_setup *s, const lr_poly *round1, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1,
+                              const uint8_t *v_coeff_bits, const uint8_t *v_sign_bits, const uint8_t *e, int n_parties,
+                              lr_poly *const *shares);
+int lr_setup_rkg_naive_round2_device(lr_setup *s, const lr_poly *round1, const lr_poly *sk, const lr_poly *pk0, const lr_poly *pk1,
+                                     const void *v_coeff_bits, const void *v_sign_bits, const void *e, int n_parties,
+                                     lr_poly *const *shares);
+int lr_setup_rkg_naive_key(lr_setup *s, const lr_poly *round2, lr_poly *evk_out);
+int lr_setup_rtg_share(lr_setup *s, const lr_poly *sk, const uint64_t *galois_elements, int n_keys, const lr_poly *crp, const uint8_t *e,
+                       lr_poly *const *shares);
+int lr_setup_rtg_share_device(lr_setup *s, const lr_poly *sk, const uint64_t *galois_elements, int n_keys, const lr_poly *crp, const void *e,
+                              lr_poly *const *shares);
+int lr_setup_rtg_key(lr_setup *s, const lr_poly *share, const lr_poly *crp, lr_poly *rotkey_out);
+int lr_setup_aggregate(lr_setup *s, const lr_poly *const *shares, int n_shares, lr_poly *out);
+
 /* ------------------------------------------------------------------ multi-device ------ */
 /* a batch of independent ciphertexts shards across the GPUs of a node by contiguous blocks (replicated contexts, tables
  * and keys, created per device with lr_context_create(..., device, ...)); nothing crosses devices but finished results.  The reference's

@@ -457,4 +457,100 @@ class Collective {
     lr_collective *h_ = nullptr;
 };
 
+// CKGProtocol, RKGProtocol, RKGProtocolNaive and RTGProtocol of dckks and dbfv (dbfv/publickey_gen.go, relinkey_gen.go,
+// relinkey_gen_naive.go, rotkey_gen.go and their dckks twins) for batches of parties, after the sampling: the randomness in BfvEncryptor's
+// compact form, every poly over Q||P in the NTT domain, a share of beta polys a Poly of batch beta, a share of beta pairs one of batch
+// 2 beta -- the key image the key switch reads.  contextP == nullptr: "P is empty", only CkgShare and Aggregate
+class Setup {
+  public:
+    Setup(const Context *contextQ, const Context *contextP, int max_batch = 1, const lr_options *options = nullptr) {
+        check(lr_setup_create_ex(contextQ->handle(), contextP ? contextP->handle() : nullptr, max_batch, options, &h_));
+    }
+    ~Setup() { lr_setup_destroy(h_); }
+    Setup(const Setup &) = delete;
+    Setup &operator=(const Setup &) = delete;
+    typedef std::vector<uint8_t> Bytes;
+    void CkgShare(const Poly *sk, const Poly *crs, const Bytes &e, int batch, Poly *share) {                                       // publickey_gen.go:54
+        check(lr_setup_ckg_share(h_, sk->handle(), crs->handle(), e.data(), batch, share->handle()));
+    }
+    void RkgRound1(const Poly *u, const Poly *sk, const Poly *crp, const Bytes &e, const std::vector<Poly *> &shares) {            // relinkey_gen.go:215
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_round1(h_, u->handle(), sk->handle(), crp->handle(), e.data(), (int)hs.size(), hs.data()));
+    }
+    void RkgRound2(const Poly *round1, const Poly *sk, const Poly *crp, const Bytes &e, const std::vector<Poly *> &shares) {       // :277
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_round2(h_, round1->handle(), sk->handle(), crp->handle(), e.data(), (int)hs.size(), hs.data()));
+    }
+    void RkgRound3(const Poly *round2, const Poly *u, const Poly *sk, const Bytes &e, const std::vector<Poly *> &shares) {         // :322
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_round3(h_, round2->handle(), u->handle(), sk->handle(), e.data(), (int)hs.size(), hs.data()));
+    }
+    void RkgKey(const Poly *round2, const Poly *round3, Poly *evk) { check(lr_setup_rkg_key(h_, round2->handle(), round3->handle(), evk->handle())); }   // :343
+    void RkgNaiveRound1(int scheme, const Poly *sk, const Poly *pk0, const Poly *pk1, const Bytes &e, const Bytes &u_coeff_bits,
+                        const Bytes &u_sign_bits, const std::vector<Poly *> &shares) {                                             // relinkey_gen_naive.go:59
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_naive_round1(h_, scheme, sk->handle(), pk0->handle(), pk1->handle(), e.data(), u_coeff_bits.data(), u_sign_bits.data(),
+                                        (int)hs.size(), hs.data()));
+    }
+    void RkgNaiveRound2(const Poly *round1, const Poly *sk, const Poly *pk0, const Poly *pk1, const Bytes &v_coeff_bits, const Bytes &v_sign_bits,
+                        const Bytes &e, const std::vector<Poly *> &shares) {                                                       // :135
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_naive_round2(h_, round1->handle(), sk->handle(), pk0->handle(), pk1->handle(), v_coeff_bits.data(), v_sign_bits.data(),
+                                        e.data(), (int)hs.size(), hs.data()));
+    }
+    void RkgNaiveKey(const Poly *round2, Poly *evk) { check(lr_setup_rkg_naive_key(h_, round2->handle(), evk->handle())); }        // :187
+    void RtgShare(const Poly *sk, const std::vector<uint64_t> &galois_elements, const Poly *crp, const Bytes &e,
+                  const std::vector<Poly *> &shares) {                                                                             // rotkey_gen.go:139
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rtg_share(h_, sk->handle(), galois_elements.data(), (int)hs.size(), crp->handle(), e.data(), hs.data()));
+    }
+    void RtgKey(const Poly *share, const Poly *crp, Poly *rotkey) { check(lr_setup_rtg_key(h_, share->handle(), crp->handle(), rotkey->handle())); }   // :205
+    // every Aggregate* of the four protocols over all of Q||P; out may be one of the shares
+    void Aggregate(const std::vector<const Poly *> &shares, Poly *out) {
+        std::vector<const lr_poly *> hs;
+        for (const Poly *s : shares) hs.push_back(s->handle());
+        check(lr_setup_aggregate(h_, hs.data(), (int)hs.size(), out->handle()));
+    }
+    // the same bytes in device memory: stream-ordered, no host copy
+    void CkgShareDevice(const Poly *sk, const Poly *crs, const void *e, int batch, Poly *share) {
+        check(lr_setup_ckg_share_device(h_, sk->handle(), crs->handle(), e, batch, share->handle()));
+    }
+    void RkgRound1Device(const Poly *u, const Poly *sk, const Poly *crp, const void *e, const std::vector<Poly *> &shares) {
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_round1_device(h_, u->handle(), sk->handle(), crp->handle(), e, (int)hs.size(), hs.data()));
+    }
+    void RkgRound2Device(const Poly *round1, const Poly *sk, const Poly *crp, const void *e, const std::vector<Poly *> &shares) {
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_round2_device(h_, round1->handle(), sk->handle(), crp->handle(), e, (int)hs.size(), hs.data()));
+    }
+    void RkgRound3Device(const Poly *round2, const Poly *u, const Poly *sk, const void *e, const std::vector<Poly *> &shares) {
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_round3_device(h_, round2->handle(), u->handle(), sk->handle(), e, (int)hs.size(), hs.data()));
+    }
+    void RkgNaiveRound1Device(int scheme, const Poly *sk, const Poly *pk0, const Poly *pk1, const void *e, const void *u_coeff_bits,
+                              const void *u_sign_bits, const std::vector<Poly *> &shares) {
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_naive_round1_device(h_, scheme, sk->handle(), pk0->handle(), pk1->handle(), e, u_coeff_bits, u_sign_bits, (int)hs.size(),
+                                               hs.data()));
+    }
+    void RkgNaiveRound2Device(const Poly *round1, const Poly *sk, const Poly *pk0, const Poly *pk1, const void *v_coeff_bits, const void *v_sign_bits,
+                              const void *e, const std::vector<Poly *> &shares) {
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rkg_naive_round2_device(h_, round1->handle(), sk->handle(), pk0->handle(), pk1->handle(), v_coeff_bits, v_sign_bits, e,
+                                               (int)hs.size(), hs.data()));
+    }
+    void RtgShareDevice(const Poly *sk, const std::vector<uint64_t> &galois_elements, const Poly *crp, const void *e, const std::vector<Poly *> &shares) {
+        std::vector<lr_poly *> hs = handles(shares);
+        check(lr_setup_rtg_share_device(h_, sk->handle(), galois_elements.data(), (int)hs.size(), crp->handle(), e, hs.data()));
+    }
+
+  private:
+    static std::vector<lr_poly *> handles(const std::vector<Poly *> &shares) {
+        std::vector<lr_poly *> hs;
+        for (Poly *s : shares) hs.push_back(s->handle());
+        return hs;
+    }
+    lr_setup *h_ = nullptr;
+};
+
 }  // namespace ring

@@ -203,6 +203,27 @@ SYMBOLS = {
     "lr_refresh_bfv_shares_device": [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
     "lr_refresh_bfv_finalize": [vp, vp, vp, vp, vp, vp, vp],
     "lr_refresh_aggregate": [vp, i32, C.POINTER(vp), i32, vp],
+    "lr_setup_create": [vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_create_ex": [vp, vp, i32, vp, C.POINTER(vp)],
+    "lr_setup_destroy": [vp],
+    "lr_setup_ckg_share": [vp, vp, vp, vp, i32, vp],
+    "lr_setup_ckg_share_device": [vp, vp, vp, vp, i32, vp],
+    "lr_setup_rkg_round1": [vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_round1_device": [vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_round2": [vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_round2_device": [vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_round3": [vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_round3_device": [vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_key": [vp, vp, vp, vp],
+    "lr_setup_rkg_naive_round1": [vp, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_naive_round1_device": [vp, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_naive_round2": [vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_naive_round2_device": [vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
+    "lr_setup_rkg_naive_key": [vp, vp, vp],
+    "lr_setup_rtg_share": [vp, vp, u64p, i32, vp, vp, C.POINTER(vp)],
+    "lr_setup_rtg_share_device": [vp, vp, u64p, i32, vp, vp, C.POINTER(vp)],
+    "lr_setup_rtg_key": [vp, vp, vp, vp],
+    "lr_setup_aggregate": [vp, C.POINTER(vp), i32, vp],
     "lr_bfv_decryptor_create": [vp, i32, C.POINTER(vp)],
     "lr_bfv_decryptor_destroy": [vp],
     "lr_bfv_decrypt": [vp, C.POINTER(vp), i32, vp, vp, i32],

@@ -542,6 +542,56 @@ struct FoldLaunch {
 };
 hipError_t launch_fold(const FoldLaunch &L, int limbs, int batch, hipStream_t stream);
 
+// ---- dckks / dbfv collective key setup (lr_setup.hip): CKGProtocol, RKGProtocol, RKGProtocolNaive, RTGProtocol ----
+constexpr int kSetupPartiesPerLaunch = 32;   // parties (RTG: Galois elements) whose share addresses travel in one launch's kernel arguments
+// CKGProtocol.GenShare (dbfv/publickey_gen.go:54-57): share = CRed(share + (q - MRed(sk, crs))), share holding NTT(e) on entry
+struct SetupCkgLaunch {
+    const u64 *sk, *crs;
+    u64 *share;
+    long long sk_stride, crs_stride, share_stride;   // between parties (sk, crs: 0 = shared)
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_setup_ckg(const SetupCkgLaunch &L, int rows, int batch, hipStream_t stream);
+// what the share kernels of RKG, the naive RKG and RTG read: z = party * beta + digit on blockIdx.z, every row of Q||P.  e = the
+// transformed noise, `per` polys per z (item z * per + c); t = the transformed ternary of item z; out[party] = the party's share,
+// member digit (a share of polys) or members 2 digit and 2 digit + 1 (a share of pairs).  Digit i owns rows i alpha .. min((i + 1)
+// alpha, nQ) - 1; there skP = InvMForm(MRed(sk, MForm(P mod q))) is added (dbfv/relinkey_gen.go:223-250).
+struct SetupShareLaunch {
+    const u64 *e, *t;
+    long long e_stride, t_stride;
+    const u64 *sk, *u;
+    long long sk_stride, u_stride;                 // between parties (0 = one key for the call)
+    const u64 *crp;                                // member digit: crp[digit]
+    long long crp_stride;
+    const u64 *in;                                 // the aggregate of the round before: member digit, or members 2 digit, 2 digit + 1
+    long long in_stride;
+    const u64 *pk0, *pk1;                          // the collective public key (naive RKG)
+    KeygenKeyRef out[kSetupPartiesPerLaunch];
+    u32 gen[kSetupPartiesPerLaunch];               // RTG: Galois elements modulo 2 N, odd
+    int n, logn, nQ, alpha, beta;
+    int quirk;                                     // naive round one, dckks: e[i][1] is the noise of [i][0], [i][1] has none
+    LimbScalars pmont;                             // MForm(P mod q) per limb of Q
+    const LimbParams *lp;                          // of contextQP
+};
+enum SetupShareKind { kSetupRkg1, kSetupRkg2, kSetupRkg3, kSetupNaive1, kSetupNaive2, kSetupRtg };
+hipError_t launch_setup_share(int kind, const SetupShareLaunch &L, int rows, int parties, hipStream_t stream);
+// the finalize steps over the beta digits of one key image (member 2 i = [i][0], 2 i + 1 = [i][1]), z = digit:
+//   RKG    (dbfv/relinkey_gen.go:343-354): evk[i][0] = MForm(CRed(round2[i][0] + round3[i])), evk[i][1] = MForm(round2[i][1])
+//   naive  (dbfv/relinkey_gen_naive.go:187-200): the same without a round3
+//   RTG    (dbfv/rotkey_gen.go:205-214): key[i][0] = share[i], key[i][1] = MForm(crp[i])
+// Element-wise: evk may be round2 as a whole poly.
+struct SetupKeyLaunch {
+    const u64 *pairs;                              // round2: members 2 i, 2 i + 1; nullptr: RTG
+    const u64 *polys;                              // round3, or RTG's share; nullptr: naive
+    const u64 *crp;                                // RTG only
+    u64 *key;
+    long long pairs_stride, polys_stride, crp_stride, key_stride;
+    int n;
+    const LimbParams *lp;
+};
+hipError_t launch_setup_key(const SetupKeyLaunch &L, int rows, int beta, hipStream_t stream);
+
 // ---- dckks / dbfv Refresh (lr_refresh.hip): RefreshProtocol.GenShares, Recode, Recrypt, Finalize ----
 // out[b][i][j] = big.Int.Mod(mask[b][j], q_i) for i < limbs: SetCoefficientsBigint(Lvl) (ring/ring_context.go:343-367) of a signed integer
 // in two's complement on `words` little-endian 64-bit words, word planes [batch][words][N]

@@ -279,27 +279,28 @@ inline int check_call(const QpHandle *h, int level, int batch) {
     return h->cP ? same_stream(h->cQ, h->cP) : LR_OK;
 }
 
-// AggregateShares over n_shares parties and, with a base, KeySwitch's Add (dckks/keyswitching.go:99-108 and its three twins; Aggregate of
-// both RefreshProtocols): lr_collective_aggregate and lr_refresh_aggregate.  `pool` holds one poly over Q||P per member of the batch.
-inline int fold_shares(QpHandle *h, u64 *pool, int level, const lr_poly *base, const lr_poly *const *shares, int n_shares, lr_poly *out) {
-    if (!h || !shares || !out) return fail(LR_ERR_ARG, "null argument");
-    if (n_shares < 1) return h->refuse(LR_ERR_SHAPE, "n_shares must be at least 1");
-    const int batch = out->batch;
-    LR_TRY(check_call(h, level, batch));
-    LR_TRY(h->check_poly(out, level + 1, batch, false, "the output"));
+// The n-ary fold behind every Aggregate*: acc = shares[0]; acc = CRed(acc + shares[k]) in the shares' order; out = base ? CRed(base + acc) :
+// acc, over limbs 0 .. q_limbs - 1 of Q and, with_p, the rows of P.  `pool` holds one poly over Q||P per member of the batch.  The checks
+// that do not depend on which rows are folded are here; the level (lr_collective, lr_refresh) or the batch (lr_setup) is the caller's.
+inline int fold_rows(QpHandle *h, u64 *pool, int q_limbs, bool with_p, const lr_poly *base, const lr_poly *const *shares, int n_shares, lr_poly *out) {
+    const int batch = out->batch, limbs = q_limbs + (with_p ? h->nP : 0);
+    LR_TRY(h->check_poly(out, limbs, batch, false, "the output"));
     if (base) {
-        LR_TRY(h->check_poly(base, level + 1, batch, false, "the base"));
+        LR_TRY(h->check_poly(base, limbs, batch, false, "the base"));
         if (overlap(out, base) && !same_poly(out, base)) return h->refuse(LR_ERR_ARG, "the output overlaps the base without being it");
     }
     for (int k = 0; k < n_shares; ++k) {
         if (!shares[k]) return fail(LR_ERR_ARG, "null argument");
-        LR_TRY(h->check_poly(shares[k], level + 1, batch, false, "a share"));
+        LR_TRY(h->check_poly(shares[k], limbs, batch, false, "a share"));
         if (overlap(out, shares[k]) && !same_poly(out, shares[k])) return h->refuse(LR_ERR_ARG, "the output overlaps a share without being it");
     }
     LR_HIP(hipSetDevice(h->device));
     lr_context *cQ = h->cQ;
     const Pools P = pools_of(h, pool, batch);
-    const int L1 = level + 1;
+    const auto add = [&](int op, const u64 *a, long long a_stride, const u64 *b, long long b_stride, u64 *dst, long long dst_stride) -> int {
+        if (with_p) return ewise_qp(h, true, op, batch, a, a_stride, b, b_stride, dst, dst_stride);
+        return run_ewise(cQ, op, q_limbs, batch, a, a_stride, b, b_stride, dst, dst_stride, nullptr);
+    };
     if (h->call_by_call) {     // n_shares - 1 Context.Add calls, then KeySwitch's; the running sum lives in the pool: out may be base or a share
         const u64 *acc = shares[0]->d;
         long long acc_stride = shares[0]->stride();
@@ -307,12 +308,12 @@ inline int fold_shares(QpHandle *h, u64 *pool, int level, const lr_poly *base, c
             const bool last = k == n_shares - 1 && !base;
             u64 *dst = last ? out->d : P.p[0];
             const long long dst_stride = last ? out->stride() : P.stride;
-            LR_TRY(run_ewise(cQ, LR_ADD, L1, batch, acc, acc_stride, shares[k]->d, shares[k]->stride(), dst, dst_stride, nullptr));
+            LR_TRY(add(LR_ADD, acc, acc_stride, shares[k]->d, shares[k]->stride(), dst, dst_stride));
             acc = dst;
             acc_stride = dst_stride;
         }
-        if (base) return run_ewise(cQ, LR_ADD, L1, batch, base->d, base->stride(), acc, acc_stride, out->d, out->stride(), nullptr);
-        if (n_shares == 1) return run_ewise(cQ, LR_COPY, L1, batch, acc, acc_stride, nullptr, 0, out->d, out->stride(), nullptr);
+        if (base) return add(LR_ADD, base->d, base->stride(), acc, acc_stride, out->d, out->stride());
+        if (n_shares == 1) return add(LR_COPY, acc, acc_stride, nullptr, 0, out->d, out->stride());
         return LR_OK;
     }
     // kFoldSharesPerLaunch shares per pass; a further pass takes the running sum, in the pool, as its first term
@@ -333,9 +334,18 @@ inline int fold_shares(QpHandle *h, u64 *pool, int level, const lr_poly *base, c
         F.out_stride = last ? out->stride() : P.stride;
         F.n = (int)cQ->h.N;
         F.lp = h->d_lp;
-        LR_HIP(launch_fold(F, L1, batch, cQ->stream));
+        LR_HIP(launch_fold(F, limbs, batch, cQ->stream));
     }
     return LR_OK;
+}
+
+// AggregateShares over n_shares parties and, with a base, KeySwitch's Add (dckks/keyswitching.go:99-108 and its three twins; Aggregate of
+// both RefreshProtocols): lr_collective_aggregate and lr_refresh_aggregate, over limbs 0 .. level of Q
+inline int fold_shares(QpHandle *h, u64 *pool, int level, const lr_poly *base, const lr_poly *const *shares, int n_shares, lr_poly *out) {
+    if (!h || !shares || !out) return fail(LR_ERR_ARG, "null argument");
+    if (n_shares < 1) return h->refuse(LR_ERR_SHAPE, "n_shares must be at least 1");
+    LR_TRY(check_call(h, level, out->batch));
+    return fold_rows(h, pool, level + 1, false, base, shares, n_shares, out);
 }
 
 }  // namespace lr_host

@@ -1329,6 +1329,140 @@ def NewRefresh(contextQ, contextP=None, t=0, max_batch=1, options=None):  # NewR
     return Refresh(contextQ, contextP, t, max_batch, options)
 
 
+class Setup(_QpHandle):
+    """The collective key setup of dckks and dbfv on the device (lr_setup), after the sampling: CKGProtocol, RKGProtocol (three rounds),
+    RKGProtocolNaive (two rounds) and RTGProtocol (dbfv/publickey_gen.go, relinkey_gen.go, relinkey_gen_naive.go, rotkey_gen.go and their
+    dckks twins) for n parties per call.  Every Poly is one of contextQ over Q||P in the NTT domain; sk, u and pk are in Montgomery form,
+    crs and crp are not.  A share of beta polys is a Poly of batch beta, a share of beta pairs one of batch 2 beta (member 2 i = [i][0],
+    2 i + 1 = [i][1]): the image CkksPlan.NewSwitchingKey allocates, so RkgKey, RkgNaiveKey and RtgKey write keys the key switch reads.
+    e = uint8 [..., N] per sampled poly (magnitude in the low 7 bits, sign in bit 7), bits = (coeff_bits, sign_bits), uint8 [..., N / 8]
+    each.  n is the number of output shares; sk and u have batch n or 1.  contextP None: only CkgShare and Aggregate, over Q."""
+
+    _abi = "lr_setup"
+    BFV, CKKS = 0, 1
+
+    @property
+    def beta(self):
+        if self.contextP is None:
+            raise LatticeRingError(4, "collective setup: modulus P is empty: only CKG and its aggregation work over Q")      # LR_ERR_ARG
+        return -(-len(self.contextQ.Modulus) // len(self.contextP.Modulus))
+
+    @property
+    def rows(self):
+        return len(self.contextQ.Modulus) + (len(self.contextP.Modulus) if self.contextP else 0)
+
+    def NewPoly(self, batch=1):
+        """`batch` polys over Q||P: a key, a CKG share, crs"""
+        return Poly(self.contextQ, self.rows, batch)
+
+    def NewShare(self):
+        """a share of beta polys: RKG rounds one and three, an RTG share, crp"""
+        return Poly(self.contextQ, self.rows, self.beta)
+
+    def NewPairShare(self):
+        """a share of beta pairs: RKG round two, both naive rounds, and every finished key"""
+        return Poly(self.contextQ, self.rows, 2 * self.beta)
+
+    @staticmethod
+    def _ptrs(polys):
+        return (C.c_void_p * len(polys))(*[p.h.value for p in polys])
+
+    def CkgShare(self, sk, crs, e, shareOut):  # CKGProtocol.GenShare, dbfv/publickey_gen.go:54
+        eb = self._bytes(e, shareOut.batch, self.contextQ.N)
+        check(lib().lr_setup_ckg_share(self.h, sk.h, crs.h, eb.ctypes.data_as(C.c_void_p), shareOut.batch, shareOut.h))
+        return shareOut
+
+    def RkgRound1(self, u, sk, crp, e, shares):  # GenShareRoundOne, dbfv/relinkey_gen.go:215
+        eb = self._bytes(e, len(shares) * self.beta, self.contextQ.N)
+        check(lib().lr_setup_rkg_round1(self.h, u.h, sk.h, crp.h, eb.ctypes.data_as(C.c_void_p), len(shares), self._ptrs(shares)))
+        return shares
+
+    def RkgRound2(self, round1, sk, crp, e, shares):  # GenShareRoundTwo, :277; e = [n, beta, 2, N]
+        eb = self._bytes(e, len(shares) * self.beta * 2, self.contextQ.N)
+        check(lib().lr_setup_rkg_round2(self.h, round1.h, sk.h, crp.h, eb.ctypes.data_as(C.c_void_p), len(shares), self._ptrs(shares)))
+        return shares
+
+    def RkgRound3(self, round2, u, sk, e, shares):  # GenShareRoundThree, :322
+        eb = self._bytes(e, len(shares) * self.beta, self.contextQ.N)
+        check(lib().lr_setup_rkg_round3(self.h, round2.h, u.h, sk.h, eb.ctypes.data_as(C.c_void_p), len(shares), self._ptrs(shares)))
+        return shares
+
+    def RkgKey(self, round2, round3, evkOut):  # GenRelinearizationKey, :343; evkOut may be round2
+        check(lib().lr_setup_rkg_key(self.h, round2.h, round3.h, evkOut.h))
+        return evkOut
+
+    def RkgNaiveRound1(self, scheme, sk, pk, e, u_bits, shares):  # dbfv/relinkey_gen_naive.go:59, dckks/relinkey_gen_naive.go:59
+        n, N = len(shares), self.contextQ.N
+        eb, c, s = self._bytes(e, n * self.beta * 2, N), self._bytes(u_bits[0], n * self.beta, N // 8), self._bytes(u_bits[1], n * self.beta, N // 8)
+        v = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().lr_setup_rkg_naive_round1(self.h, scheme, sk.h, pk[0].h, pk[1].h, v(eb), v(c), v(s), n, self._ptrs(shares)))
+        return shares
+
+    def RkgNaiveRound2(self, round1, sk, pk, v_bits, e, shares):  # :135
+        n, N = len(shares), self.contextQ.N
+        eb, c, s = self._bytes(e, n * self.beta * 2, N), self._bytes(v_bits[0], n * self.beta, N // 8), self._bytes(v_bits[1], n * self.beta, N // 8)
+        v = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().lr_setup_rkg_naive_round2(self.h, round1.h, sk.h, pk[0].h, pk[1].h, v(c), v(s), v(eb), n, self._ptrs(shares)))
+        return shares
+
+    def RkgNaiveKey(self, round2, evkOut):  # :187; evkOut may be round2
+        check(lib().lr_setup_rkg_naive_key(self.h, round2.h, evkOut.h))
+        return evkOut
+
+    def RtgShare(self, sk, galois_elements, crp, e, shares):  # RTGProtocol.genShare, dbfv/rotkey_gen.go:139, for each Galois element
+        if len(galois_elements) != len(shares):
+            raise LatticeRingError(3, "one share per Galois element")
+        eb = self._bytes(e, len(shares) * self.beta, self.contextQ.N)
+        check(lib().lr_setup_rtg_share(self.h, sk.h, _u64(galois_elements), len(shares), crp.h, eb.ctypes.data_as(C.c_void_p), self._ptrs(shares)))
+        return shares
+
+    def RtgKey(self, share, crp, rotKeyOut):  # Finalize, :205
+        check(lib().lr_setup_rtg_key(self.h, share.h, crp.h, rotKeyOut.h))
+        return rotKeyOut
+
+    def Aggregate(self, shares, out):
+        """every Aggregate* of the four protocols over all the parties' shares in their order, over all of Q||P; out may be a share"""
+        check(lib().lr_setup_aggregate(self.h, self._ptrs(shares), len(shares), out.h))
+        return out
+
+    # the same with the randomness in device memory (pointers, e.g. a torch uint8 tensor's data_ptr()); stream-ordered
+    def CkgShareDevice(self, sk, crs, e_ptr, shareOut):
+        check(lib().lr_setup_ckg_share_device(self.h, sk.h, crs.h, C.c_void_p(e_ptr), shareOut.batch, shareOut.h))
+        return shareOut
+
+    def RkgRound1Device(self, u, sk, crp, e_ptr, shares):
+        check(lib().lr_setup_rkg_round1_device(self.h, u.h, sk.h, crp.h, C.c_void_p(e_ptr), len(shares), self._ptrs(shares)))
+        return shares
+
+    def RkgRound2Device(self, round1, sk, crp, e_ptr, shares):
+        check(lib().lr_setup_rkg_round2_device(self.h, round1.h, sk.h, crp.h, C.c_void_p(e_ptr), len(shares), self._ptrs(shares)))
+        return shares
+
+    def RkgRound3Device(self, round2, u, sk, e_ptr, shares):
+        check(lib().lr_setup_rkg_round3_device(self.h, round2.h, u.h, sk.h, C.c_void_p(e_ptr), len(shares), self._ptrs(shares)))
+        return shares
+
+    def RkgNaiveRound1Device(self, scheme, sk, pk, e_ptr, u_bits_ptrs, shares):
+        v = C.c_void_p
+        check(lib().lr_setup_rkg_naive_round1_device(self.h, scheme, sk.h, pk[0].h, pk[1].h, v(e_ptr), v(u_bits_ptrs[0]), v(u_bits_ptrs[1]),
+                                                     len(shares), self._ptrs(shares)))
+        return shares
+
+    def RkgNaiveRound2Device(self, round1, sk, pk, v_bits_ptrs, e_ptr, shares):
+        v = C.c_void_p
+        check(lib().lr_setup_rkg_naive_round2_device(self.h, round1.h, sk.h, pk[0].h, pk[1].h, v(v_bits_ptrs[0]), v(v_bits_ptrs[1]), v(e_ptr),
+                                                     len(shares), self._ptrs(shares)))
+        return shares
+
+    def RtgShareDevice(self, sk, galois_elements, crp, e_ptr, shares):
+        check(lib().lr_setup_rtg_share_device(self.h, sk.h, _u64(galois_elements), len(shares), crp.h, C.c_void_p(e_ptr), self._ptrs(shares)))
+        return shares
+
+
+def NewSetup(contextQ, contextP, max_batch=1, options=None):  # NewCKGProtocol / NewEkgProtocol / NewEkgProtocolNaive / NewRotKGProtocol
+    return Setup(contextQ, contextP, max_batch, options)
+
+
 class BfvBatcher:
     """Merges the Mul and Relinearize calls of concurrent BFV evaluators -- the reference's own pooled workload: every task of
     examples/dbfv/psi/psi.go:215-233 calls evaluator.Mul and evaluator.Relinearize on one ciphertext pair -- into batched launches

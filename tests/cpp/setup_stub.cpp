@@ -1,0 +1,96 @@
+// Stand-ins for the launchers of lr_setup.hip, for the CPU-sanitizer build of the collective setup's host side
+// (tests/test_host_setup_sanitizers.py); the expansion it shares with the CKKS encryptor is served by ckks_encryptor_stub.cpp and the fold
+// by collective_stub.cpp, which stay as they are.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.  A stub counts its
+// launch and touches the first and the last byte of everything the real kernel would read or write at the addresses the launch names:
+// "device" memory is malloc'ed at its exact size, so a wrong size, stride, digit or party count in the host code is an AddressSanitizer
+// report.
+#include <atomic>
+
+#include "lr_device.hpp"
+
+namespace lr {
+
+std::atomic<unsigned long long> g_setup_ckg_launches{0}, g_setup_share_launches{0}, g_setup_key_launches{0};
+
+namespace {
+thread_local volatile u64 t_sink;
+template <class T>
+void rd(const T *p, long long count) {
+    if (count <= 0) return;
+    t_sink = (u64)((const volatile unsigned char *)p)[0];
+    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
+}
+void wr(u64 *p, long long count) {
+    if (count <= 0) return;
+    p[0] = p[0];
+    p[count - 1] = p[count - 1];
+}
+}  // namespace
+
+hipError_t launch_setup_ckg(const SetupCkgLaunch &L, int rows, int batch, hipStream_t) {
+    if (rows <= 0 || batch <= 0) return hipSuccess;
+    if (L.n < 2 || rows > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    g_setup_ckg_launches.fetch_add(1);
+    rd(L.lp, rows);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < rows; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.sk + b * L.sk_stride + row, L.n);
+            rd(L.crs + b * L.crs_stride + row, L.n);
+            wr(L.share + b * L.share_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+hipError_t launch_setup_share(int kind, const SetupShareLaunch &L, int rows, int parties, hipStream_t) {
+    if (rows <= 0 || parties <= 0) return hipSuccess;
+    if (L.n < 2 || L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || rows > kMaxLimbs || parties > kSetupPartiesPerLaunch || L.beta < 1 ||
+        L.beta > kMaxLimbs || L.alpha < 1 || L.nQ < 1 || L.nQ > rows || kind < kSetupRkg1 || kind > kSetupRtg)
+        return hipErrorInvalidValue;
+    g_setup_share_launches.fetch_add(1);
+    rd(L.lp, rows);
+    const bool pairs = kind == kSetupRkg2 || kind == kSetupNaive1 || kind == kSetupNaive2;
+    const int per = pairs ? 2 : 1;
+    for (int k = 0; k < parties; ++k) {
+        if (kind == kSetupRtg && (!(L.gen[k] & 1u) || L.gen[k] >= 2u * (u32)L.n)) return hipErrorInvalidValue;
+        for (int d = 0; d < L.beta; ++d)
+            for (int i = 0; i < rows; ++i) {
+                const long long row = (long long)i * L.n, z = (long long)k * L.beta + d;
+                for (int c = 0; c < per; ++c) {
+                    rd(L.e + (z * per + c) * L.e_stride + row, L.n);
+                    wr(L.out[k].base + (long long)(per * d + c) * L.out[k].stride + row, L.n);
+                }
+                rd(L.sk + (kind == kSetupRtg ? 0 : k * L.sk_stride) + row, L.n);
+                if (kind == kSetupRkg1 || kind == kSetupRkg3) rd(L.u + k * L.u_stride + row, L.n);
+                if (kind == kSetupRkg1 || kind == kSetupRkg2 || kind == kSetupRtg) rd(L.crp + d * L.crp_stride + row, L.n);
+                if (kind == kSetupRkg2) rd(L.in + d * L.in_stride + row, L.n);
+                if (kind == kSetupRkg3) rd(L.in + (2 * d + 1) * L.in_stride + row, L.n);
+                if (kind == kSetupNaive2) rd(L.in + 2 * d * L.in_stride + row, L.n), rd(L.in + (2 * d + 1) * L.in_stride + row, L.n);
+                if (kind == kSetupNaive1 || kind == kSetupNaive2) {
+                    rd(L.t + z * L.t_stride + row, L.n);
+                    rd(L.pk0 + row, L.n);
+                    rd(L.pk1 + row, L.n);
+                }
+            }
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_setup_key(const SetupKeyLaunch &L, int rows, int beta, hipStream_t) {
+    if (rows <= 0 || beta <= 0) return hipSuccess;
+    if (L.n < 2 || rows > kMaxLimbs || beta > kMaxLimbs || (!L.pairs && (!L.polys || !L.crp))) return hipErrorInvalidValue;
+    g_setup_key_launches.fetch_add(1);
+    rd(L.lp, rows);
+    for (int d = 0; d < beta; ++d)
+        for (int i = 0; i < rows; ++i) {
+            const long long row = (long long)i * L.n;
+            if (L.pairs) rd(L.pairs + 2 * d * L.pairs_stride + row, L.n), rd(L.pairs + (2 * d + 1) * L.pairs_stride + row, L.n);
+            if (L.polys) rd(L.polys + d * L.polys_stride + row, L.n);
+            if (L.crp) rd(L.crp + d * L.crp_stride + row, L.n);
+            wr(L.key + 2 * d * L.key_stride + row, L.n);
+            wr(L.key + (2 * d + 1) * L.key_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+}  // namespace lr
