@@ -35,8 +35,9 @@ extern "C" int lr_bfv_plan_create_ex(lr_context *cQ, lr_context *cM, uint64_t t,
     return guarded([&]() -> int {
     if (!cQ || !cM || !out) return fail(LR_ERR_ARG, "null argument");
     *out = nullptr;
-    Options parsed;
-    LR_TRY(options_from_public(options, &parsed));
+    Options parsed = cQ->opt;                                   // options == NULL: the options of ctxQ, as the header says
+    if (options) LR_TRY(options_from_public(options, &parsed));
+    else parsed.apply_env();
     if (max_batch < 1) return fail(LR_ERR_ARG, "max_batch must be >= 1");
     LR_TRY(same_degree(cQ, cM));
     std::unique_ptr<lr_bfv_plan> p(new lr_bfv_plan());

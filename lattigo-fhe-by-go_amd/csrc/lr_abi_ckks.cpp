@@ -21,8 +21,9 @@ extern "C" int lr_ckks_plan_create_ex(lr_context *cQ, lr_context *cP, int max_ba
     return guarded([&]() -> int {
     if (!cQ || !cP || !out) return fail(LR_ERR_ARG, "null argument");
     *out = nullptr;
-    Options parsed;
-    LR_TRY(options_from_public(options, &parsed));
+    Options parsed = cQ->opt;                                   // options == NULL: the options of ctxQ, as the header says
+    if (options) LR_TRY(options_from_public(options, &parsed));
+    else parsed.apply_env();
     if (max_batch < 1) return fail(LR_ERR_ARG, "max_batch must be >= 1");
     LR_TRY(same_degree(cQ, cP));
     std::unique_ptr<lr_ckks_plan> p(new lr_ckks_plan());

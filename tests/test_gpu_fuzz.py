@@ -4,21 +4,9 @@ degrees that run on the whole-limb kernel, moduli of mixed sizes, the key-switch
 import numpy as np
 import pytest
 
-import limit_moduli as lm
+from handle_fuzz_shapes import _ckks_size_moduli, _moduli  # the two modulus pools, shared with the handles' fuzz
 
 pytestmark = pytest.mark.gpu
-
-
-def _moduli(pkg, rng, logn, count):
-    """a random mix of modulus sizes that are NTT-friendly for this degree"""
-    pool = list(pkg.params.Qi60()[-8:]) + list(pkg.params.Pi60()[-4:])
-    pool += pkg.params.GenerateNTTPrimes(40, logn, 3) + pkg.params.GenerateNTTPrimes(50, logn, 2) + pkg.params.GenerateNTTPrimes(34, logn, 1)
-    # ... and the primes next to every admission bound (tests/limit_moduli.py)
-    pool += [lm.below(61, logn), lm.above(60, logn), lm.below(60, logn), lm.above(57, logn), lm.below(57, logn), lm.above(46, logn), lm.below(46, logn),
-             lm.above(33, logn), lm.below(33, logn), lm.above(32, logn), lm.below(32, logn)]
-    pool = sorted(set(pool))
-    idx = rng.choice(len(pool), size=count, replace=False)
-    return [pool[i] for i in idx]
 
 
 @pytest.mark.parametrize("seed", range(28))
@@ -113,19 +101,6 @@ def test_key_switch_fuzz(gpu_pkg, oracle, seed):
     for b in range(batch):
         w0, w1 = oplan.switch_keys(level, cx[b], evk.reshape(beta, 2, nq + np_, N))
         assert np.array_equal(g0[b], w0) and np.array_equal(g1[b], w1), (logn, nq, np_, level, b)
-
-
-def _ckks_size_moduli(pkg, rng, logn, count):
-    """moduli between 30 and 56 bits: contexts that select the dual assembly kernels (FP64 body below 2^46 next to the integer one)"""
-    pool = []
-    for bits in (30, 34, 40, 45, 46, 50, 56):
-        pool += pkg.params.GenerateNTTPrimes(bits, logn, 2)
-    # ... and the limit primes of that range (tests/limit_moduli.py): the top of the dual kernels' integer body, both sides of the FP64 body's
-    # limit, both sides of 2^33 and 2^32 (FP64 limbs either way)
-    pool += [lm.below(57, logn), lm.above(46, logn), lm.below(46, logn), lm.above(33, logn), lm.below(33, logn), lm.above(32, logn), lm.below(32, logn)]
-    pool = sorted(set(pool))
-    idx = rng.choice(len(pool), size=count, replace=False)
-    return [pool[i] for i in idx]
 
 
 @pytest.mark.parametrize("seed", range(12))

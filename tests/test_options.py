@@ -121,3 +121,45 @@ def test_plan_options_and_thresholds(gpu_pkg, oracle):
         bo = (cq.NewPoly(1), cq.NewPoly(1), cq.NewPoly(1))
         bplan.Mul((mk(0), mk(1)), (mk(2), mk(3)), bo)
         assert all(np.array_equal(bo[k].get(), bwant[k]) for k in range(3)), fields
+
+
+@pytest.mark.gpu
+def test_a_plan_made_without_options_inherits_those_of_its_context(gpu_pkg, oracle):
+    """lr_ckks_plan_create / lr_bfv_plan_create with options == NULL take "the options of ctxQ": no_ext_group set on the contexts only keeps
+    the digits' extensions one launch each (lr_ckks_plan_stats says which path ran), where the same plan on default contexts groups them;
+    bfv_no_gather on the contexts only is accepted by a BFV plan made the same way; same bits every way"""
+    import gc
+    ring, params, sampling = gpu_pkg.ring, gpu_pkg.params, gpu_pkg.sampling
+    N, nq, np_, batch = 1 << 12, 10, 4, 2
+    _, Qf, Pf = params.ckks_moduli("PN16QP1761")
+    Q, P = list(Qf[:nq]), list(Pf[:np_])
+    level, beta = nq - 1, -(-nq // np_)
+    evk = sampling.uniform_poly(Q + P, N, 2 * beta, seed=3)
+    cx = sampling.uniform_poly(Q, N, batch, seed=4).reshape(batch, nq, N)
+    oplan = oracle.CkksPlan(oracle.Context(N, Q), oracle.Context(N, P))
+    want = [oplan.switch_keys(level, cx[b], evk.reshape(beta, 2, nq + np_, N)) for b in range(batch)]
+    grouped = {}
+    for on_context in (False, True):
+        gc.collect()
+        opt = ring.Options(no_ext_group=1) if on_context else None
+        cQ, cP = ring.NewContextWithParams(N, Q, options=opt), ring.NewContextWithParams(N, P, options=opt)
+        plan = ring.CkksPlan(cQ, cP, batch)                               # no options of its own
+        p0, p1 = cQ.NewPoly(batch), cQ.NewPoly(batch)
+        plan.SwitchKeysInPlace(level, cQ.NewPoly(batch).set(cx), plan.NewSwitchingKey().set(evk), p0, p1)
+        g0, g1 = p0.get().reshape(batch, nq, N), p1.get().reshape(batch, nq, N)
+        for b in range(batch):
+            assert np.array_equal(g0[b], want[b][0]) and np.array_equal(g1[b], want[b][1]), (on_context, b)
+        grouped[on_context] = plan.Stats()["grouped_extensions"]
+        del plan
+    assert grouped[False] > 0 and grouped[True] == 0, grouped
+    bN, bQ, _, bM = params.bfv_moduli("PN12QP109")
+    bQ, bM = list(bQ), list(bM)
+    bops = [sampling.uniform_poly(bQ, bN, 1, seed=20 + k) for k in range(4)]
+    bwant = oracle.BfvPlan(oracle.Context(bN, bQ), oracle.Context(bN, bM), 65537).mul(np.stack([bops[0][0], bops[1][0]]), np.stack([bops[2][0], bops[3][0]]))
+    opt = ring.Options(bfv_no_gather=1, bfv_no_ext_epilogue=1)
+    cq, cm = ring.NewContextWithParams(bN, bQ, options=opt), ring.NewContextWithParams(bN, bM, options=opt)
+    bplan = ring.BfvPlan(cq, cm, 65537, 1)
+    mk = lambda k: cq.NewPoly(1).set(bops[k])
+    bo = (cq.NewPoly(1), cq.NewPoly(1), cq.NewPoly(1))
+    bplan.Mul((mk(0), mk(1)), (mk(2), mk(3)), bo)
+    assert all(np.array_equal(bo[k].get(), bwant[k]) for k in range(3))
