@@ -570,9 +570,7 @@ __global__ __launch_bounds__(256) void div_selftest_kernel(u64 seed, int per_thr
 }
 
 hipError_t launch_div_selftest(u64 seed, int blocks, int per_thread, unsigned long long *d_mismatches, hipStream_t stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(div_selftest_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, seed, per_thread, d_mismatches);
-    return hipGetLastError();
+    return launch_kernel(div_selftest_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, seed, per_thread, d_mismatches);
 }
 
 hipError_t launch_ext(const ExtLaunch &L, int n_in, int batch, hipStream_t stream) {

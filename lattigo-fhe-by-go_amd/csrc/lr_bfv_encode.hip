@@ -145,9 +145,7 @@ hipError_t launch_bfv_encode_fused(const EncodeLaunch &L, int batch, hipStream_t
     static std::atomic<bool> configured[64];
     const hipError_t e = allow_lds(bfv_encode_fused_kernel, configured);
     if (e != hipSuccess) return e;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(bfv_encode_fused_kernel, dim3((unsigned)batch), dim3(kEncThreads), sizeof(u32) << L.tab.logn, stream, L);
-    return hipGetLastError();
+    return launch_kernel(bfv_encode_fused_kernel, dim3((unsigned)batch), dim3(kEncThreads), sizeof(u32) << L.tab.logn, stream, L);
 }
 
 hipError_t launch_bfv_decode_fused(const DecodeLaunch &L, int batch, hipStream_t stream) {
@@ -156,34 +154,26 @@ hipError_t launch_bfv_decode_fused(const DecodeLaunch &L, int batch, hipStream_t
     static std::atomic<bool> configured[64];
     const hipError_t e = allow_lds(bfv_decode_fused_kernel, configured);
     if (e != hipSuccess) return e;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(bfv_decode_fused_kernel, dim3((unsigned)batch), dim3(kEncThreads), sizeof(u32) << L.tab.logn, stream, L);
-    return hipGetLastError();
+    return launch_kernel(bfv_decode_fused_kernel, dim3((unsigned)batch), dim3(kEncThreads), sizeof(u32) << L.tab.logn, stream, L);
 }
 
 hipError_t launch_bfv_slot_scatter(const EncoderTables &tab, const void *values, long long n_values, int is_signed, u64 *row, int batch, hipStream_t stream) {
     if (n_values < 0 || n_values > tab.n || batch > 65535) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(bfv_slot_scatter_kernel, dim3((unsigned)((tab.n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, tab, values, n_values, is_signed, row);
-    return hipGetLastError();
+    return launch_kernel(bfv_slot_scatter_kernel, dim3((unsigned)((tab.n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, tab, values, n_values, is_signed, row);
 }
 
 hipError_t launch_bfv_lift(const u64 *row, int n, u64 *out, long long out_stride, int limbs, const LimbParams *lp, const u64 *delta_mont, int batch,
                            hipStream_t stream) {
     if (batch > 65535) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(bfv_lift_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, row, n, out, out_stride, limbs, lp, delta_mont);
-    return hipGetLastError();
+    return launch_kernel(bfv_lift_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, row, n, out, out_stride, limbs, lp, delta_mont);
 }
 
 hipError_t launch_bfv_slot_gather(const EncoderTables &tab, const u64 *row, void *values, int is_signed, int batch, hipStream_t stream) {
     if (batch > 65535) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(bfv_slot_gather_kernel, dim3((unsigned)((tab.n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, tab, row, values, is_signed);
-    return hipGetLastError();
+    return launch_kernel(bfv_slot_gather_kernel, dim3((unsigned)((tab.n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, tab, row, values, is_signed);
 }
 
 }  // namespace lr

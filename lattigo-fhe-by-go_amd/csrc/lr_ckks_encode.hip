@@ -328,17 +328,13 @@ hipError_t launch_ckks_encode_fused(const CkksEncTables &tab, const Cplx *values
     static std::atomic<bool> configured[64];
     const hipError_t e = allow_lds(ckks_encode_fused_kernel, configured);
     if (e != hipSuccess) return e;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ckks_encode_fused_kernel, dim3((unsigned)batch), dim3(kCkksThreads), sizeof(Cplx) << logslots, stream, tab, values, logslots, S);
-    return hipGetLastError();
+    return launch_kernel(ckks_encode_fused_kernel, dim3((unsigned)batch), dim3(kCkksThreads), sizeof(Cplx) << logslots, stream, tab, values, logslots, S);
 }
 
 hipError_t launch_ckks_dif_stage(const CkksEncTables &tab, const Cplx *src, Cplx *dst, int logslots, int loglen, int batch, hipStream_t stream) {
     if (!shape_ok(tab, logslots, batch) || loglen < 1 || loglen > logslots || !src || !dst) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ckks_dif_stage_kernel, dim3(blocks256(1ll << (logslots - 1)), (unsigned)batch), dim3(256), 0, stream, tab, src, dst, logslots, loglen);
-    return hipGetLastError();
+    return launch_kernel(ckks_dif_stage_kernel, dim3(blocks256(1ll << (logslots - 1)), (unsigned)batch), dim3(256), 0, stream, tab, src, dst, logslots, loglen);
 }
 
 hipError_t launch_ckks_dif_tile(const CkksEncTables &tab, const Cplx *src, Cplx *dst, int logslots, int logtile, int batch, hipStream_t stream) {
@@ -347,27 +343,20 @@ hipError_t launch_ckks_dif_tile(const CkksEncTables &tab, const Cplx *src, Cplx 
     static std::atomic<bool> configured[64];
     const hipError_t e = allow_lds(ckks_dif_tile_kernel, configured);
     if (e != hipSuccess) return e;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ckks_dif_tile_kernel, dim3(1u << (logslots - logtile), (unsigned)batch), dim3(lds_threads(logtile)), sizeof(Cplx) << logtile, stream, tab, src,
-                       dst, logslots, logtile);
-    return hipGetLastError();
+    return launch_kernel(ckks_dif_tile_kernel, dim3(1u << (logslots - logtile), (unsigned)batch), dim3(lds_threads(logtile)), sizeof(Cplx) << logtile, stream, tab, src, dst, logslots, logtile);
 }
 
 hipError_t launch_ckks_scale_up(const CkksEncTables &tab, const Cplx *src, int logslots, const CkksScaleUp &S, int batch, hipStream_t stream) {
     if (!shape_ok(tab, logslots, batch) || !src || !S.out || S.limbs < 1) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ckks_scale_up_kernel, dim3(blocks256(tab.n), (unsigned)batch), dim3(256), 0, stream, tab, src, logslots, S);
-    return hipGetLastError();
+    return launch_kernel(ckks_scale_up_kernel, dim3(blocks256(tab.n), (unsigned)batch), dim3(256), 0, stream, tab, src, logslots, S);
 }
 
 hipError_t launch_ckks_crt_to_double(const CkksEncTables &tab, const CkksCrt &P, int logslots, double *dbuf, int batch, hipStream_t stream) {
     if (!shape_ok(tab, logslots, batch) || P.limbs < 1 || P.words < 1 || P.words > kCkksCrtMaxWords || P.qhat_stride < P.words || !P.pool || !dbuf)
         return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ckks_crt_to_double_kernel, dim3(blocks256(2ll << logslots), (unsigned)batch), dim3(256), 0, stream, tab, P, logslots, dbuf);
-    return hipGetLastError();
+    return launch_kernel(ckks_crt_to_double_kernel, dim3(blocks256(2ll << logslots), (unsigned)batch), dim3(256), 0, stream, tab, P, logslots, dbuf);
 }
 
 hipError_t launch_ckks_dit_tile(const CkksEncTables &tab, const double *dbuf, Cplx *dst, int logslots, int logtile, int batch, hipStream_t stream) {
@@ -376,18 +365,13 @@ hipError_t launch_ckks_dit_tile(const CkksEncTables &tab, const double *dbuf, Cp
     static std::atomic<bool> configured[64];
     const hipError_t e = allow_lds(ckks_dit_tile_kernel, configured);
     if (e != hipSuccess) return e;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ckks_dit_tile_kernel, dim3(1u << (logslots - logtile), (unsigned)batch), dim3(lds_threads(logtile)), sizeof(Cplx) << logtile, stream, tab, dbuf,
-                       dst, logslots, logtile);
-    return hipGetLastError();
+    return launch_kernel(ckks_dit_tile_kernel, dim3(1u << (logslots - logtile), (unsigned)batch), dim3(lds_threads(logtile)), sizeof(Cplx) << logtile, stream, tab, dbuf, dst, logslots, logtile);
 }
 
 hipError_t launch_ckks_dit_stage(const CkksEncTables &tab, const Cplx *src, Cplx *dst, int logslots, int loglen, int batch, hipStream_t stream) {
     if (!shape_ok(tab, logslots, batch) || loglen < 1 || loglen > logslots || !src || !dst) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ckks_dit_stage_kernel, dim3(blocks256(1ll << (logslots - 1)), (unsigned)batch), dim3(256), 0, stream, tab, src, dst, logslots, loglen);
-    return hipGetLastError();
+    return launch_kernel(ckks_dit_stage_kernel, dim3(blocks256(1ll << (logslots - 1)), (unsigned)batch), dim3(256), 0, stream, tab, src, dst, logslots, loglen);
 }
 
 }  // namespace lr

@@ -24,6 +24,12 @@ struct LimbParams {
 
 constexpr int kMaxLimbs = 64;
 
+// What a launcher decides from its arguments before it touches the device.  A family's rule is written once, as the launch_verdict next to
+// its launch struct; the launcher and its stand-in under tests/cpp both ask it, so the host sanitizer builds check the product's rule.
+enum LaunchVerdict { kLaunchGo = 0, kLaunchEmpty, kLaunchRefuse };     // empty: nothing to do, hipSuccess; refuse: hipErrorInvalidValue
+inline LaunchVerdict launch_verdict(bool empty, bool bad) { return empty ? kLaunchEmpty : bad ? kLaunchRefuse : kLaunchGo; }
+inline hipError_t verdict_error(LaunchVerdict v) { return v == kLaunchRefuse ? hipErrorInvalidValue : hipSuccess; }
+
 // The library's configuration, one copy per handle, fixed when the handle is created: the internal image of the public lr_options
 // (include/lattigo_ring.h; from_public / to_public in lr_abi_core.cpp).  A deployment configures through lr_options and the *_create_ex
 // entry points; the LR_* environment variables named below are a TEST-ONLY override of the same fields, read in exactly one place
@@ -197,6 +203,10 @@ struct TensorDegLaunch {
 };
 // d0, d1 >= 0, 1 <= d0 + d1 <= 5, (d0, d1) != (1, 1) (that is launch_tensor); square only with d0 == d1 == 2; else hipErrorInvalidValue
 hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool square, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const TensorDegLaunch &, int d0, int d1, bool square, int limbs, int batch) {      // (refusals first: a bad degree is an error at any size)
+    const bool bad = d0 < 0 || d1 < 0 || d0 + d1 < 1 || d0 + d1 > kTensorMaxDegree || (d0 == 1 && d1 == 1) || (square && !(d0 == 2 && d1 == 2));
+    return bad ? kLaunchRefuse : (limbs <= 0 || batch <= 0) ? kLaunchEmpty : kLaunchGo;
+}
 
 // decryptor.Decrypt (ckks/decryptor.go:53-78) in one pass: Horner evaluation of ct[0..degree] at the secret key with the reference's
 // element operations and reduction cadence -- acc = ct[degree]; for i = degree..1: acc = CRed(MRed(acc, sk) + ct[i-1]), BRedAdd when
@@ -395,6 +405,9 @@ struct TernaryLaunch {
     LimbScalars one, minus_one;                    // rows 1 and 2 of the matrix, per limb of the launch
 };
 hipError_t launch_bfv_ternary(const TernaryLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const TernaryLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 8 || limbs > kMaxLimbs);
+}
 // the Gaussian samplers' (magnitude, sign) bytes: low 7 bits the magnitude c, bit 7 the sign; the residue is the reference's
 // (ring/gaussianSampler.go:247,271): sign 1 -> c, sign 0 -> q - c (so (0, sign 0) is q).  add = 1: out = CRed(x + residue) (Context.Add,
 // SampleAndAdd), then CRed(. + plus) where a component has a `plus` (the Context.Add of the plaintext that ends encrypt); add = 0: out =
@@ -409,6 +422,9 @@ struct NoiseLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_bfv_noise(const NoiseLaunch &L, int comps, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const NoiseLaunch &L, int comps, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0 || comps <= 0, comps > 2 || L.n < 2 || (long long)comps * limbs > 65535);
+}
 // out = q - MRed(a, b): Neg(MulCoeffsMontgomery(crp, sk)) of skEncryptor.encrypt (bfv/encryptor.go:314-315, 326-327) in one pass; a zero
 // product gives q, as Context.Neg does
 struct NegMulLaunch {
@@ -419,6 +435,7 @@ struct NegMulLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_bfv_negmul(const NegMulLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const NegMulLaunch &L, int limbs, int batch) { return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2); }
 
 // ---- ckks.Encryptor (lr_ckks_encrypt.hip): the fast forms of ckks/encryptor.go around one forward transform ----
 // the operands of that transform in one launch: `ternary` (0 or 1) polys from the two bit planes (as TernaryLaunch), then `noises` (0 .. 2)
@@ -434,6 +451,10 @@ struct CkksExpandLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_ckks_expand(const CkksExpandLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const CkksExpandLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0 || L.ternary + L.noises <= 0,
+                          L.n < 8 || limbs > kMaxLimbs || L.ternary < 0 || L.ternary > 1 || L.noises < 0 || L.noises > 2 || batch > 65535);
+}
 // pkEncryptor.encrypt, fast (ckks/encryptor.go:187-200, :234): out_k = CRed(MRed(u, pk_k) + e_k), out0 = CRed(out0 + pt); u, e0, e1 are
 // the transformed polys of one expansion (poly stride r_stride)
 struct CkksPkFastLaunch {
@@ -444,6 +465,7 @@ struct CkksPkFastLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_ckks_pk_fast(const CkksPkFastLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const CkksPkFastLaunch &L, int limbs, int batch) { return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || batch > 65535); }
 // skEncryptor.encrypt, fast (ckks/encryptor.go:324-330, :359): out0 = CRed(CRed((q - MRed(crp, sk)) + e) + pt), out1 = crp
 struct CkksSkFastLaunch {
     const u64 *crp, *sk, *e, *pt;
@@ -453,6 +475,7 @@ struct CkksSkFastLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_ckks_sk_fast(const CkksSkFastLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const CkksSkFastLaunch &L, int limbs, int batch) { return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || batch > 65535); }
 
 // ---- KeyGenerator (lr_keygen.hip): newSwitchingKey and GenPublicKey of ckks/keygen.go and bfv/keygen.go around one forward transform ----
 constexpr int kKeygenKeysPerLaunch = 32;   // keys whose addresses and Galois elements travel in one launch's kernel arguments
@@ -472,6 +495,10 @@ struct KeygenSkInLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_keygen_skin(const KeygenSkInLaunch &L, int limbs, int keys, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const KeygenSkInLaunch &L, int limbs, int keys) {
+    return launch_verdict(limbs <= 0 || keys <= 0,
+                          L.n < 2 || L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || limbs > kMaxLimbs || keys > kKeygenKeysPerLaunch);
+}
 // out[k] = P sk^(first + k + 2) over the rows of Q, k < keys: GenRelinKey's running product
 struct KeygenPowersLaunch {
     const u64 *sk;
@@ -482,6 +509,7 @@ struct KeygenPowersLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_keygen_powers(const KeygenPowersLaunch &L, int limbs, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const KeygenPowersLaunch &L, int limbs) { return launch_verdict(limbs <= 0 || L.keys <= 0, L.n < 2 || limbs > kMaxLimbs || L.first < 0); }
 // evakey[i][0] = CRed(CRed(MForm(e) + [row in digit i] P skIn) + (q - MRed(evakey[i][1], skOut))) for `keys` keys x beta digits, every row of
 // Q||P; e = the transformed noise of item k * beta + i
 struct KeygenFinishLaunch {
@@ -492,6 +520,10 @@ struct KeygenFinishLaunch {
     const LimbParams *lp;                          // of contextQP
 };
 hipError_t launch_keygen_finish(const KeygenFinishLaunch &L, int rows, int keys, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const KeygenFinishLaunch &L, int rows, int keys) {
+    return launch_verdict(rows <= 0 || keys <= 0, L.n < 2 || rows > kMaxLimbs || keys > kKeygenKeysPerLaunch || L.beta < 1 || L.beta > kMaxLimbs ||
+                                                      L.alpha < 1 || L.nQ < 1 || L.nQ > rows);
+}
 // pk0 = q - CRed(pk0 + MRed(sk, pk1)), pk0 holding NTT(e) on entry: GenPublicKey (ckks/keygen.go:144-148)
 struct KeygenPkLaunch {
     const u64 *sk, *pk1;
@@ -501,6 +533,7 @@ struct KeygenPkLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_keygen_pk(const KeygenPkLaunch &L, int rows, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const KeygenPkLaunch &L, int rows, int batch) { return launch_verdict(rows <= 0 || batch <= 0, L.n < 2 || rows > kMaxLimbs || batch > 65535); }
 
 // ---- dckks / dbfv collective key switching (lr_collective.hip): CKSProtocol, PCKSProtocol, AggregateShares, KeySwitch ----
 constexpr int kFoldSharesPerLaunch = 32;   // shares whose addresses and strides travel in one launch's kernel arguments
@@ -516,6 +549,7 @@ struct CksShareLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_cks_share(const CksShareLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const CksShareLaunch &L, int limbs, int batch) { return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || limbs > kMaxLimbs || batch > 65535); }
 // out0 = CRed(out0 + MRed(c1, sk)): MulCoeffsMontgomeryAndAddLvl at the end of PCKSProtocol.GenShare (dckks/public_keyswitching.go:90)
 struct PcksAddendLaunch {
     const u64 *c1, *sk;
@@ -525,6 +559,7 @@ struct PcksAddendLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_pcks_addend(const PcksAddendLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const PcksAddendLaunch &L, int limbs, int batch) { return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || limbs > kMaxLimbs || batch > 65535); }
 // acc = share[0]; acc = CRed(acc + share[k]) for k = 1 .. count - 1 in this order; out = base ? CRed(base + acc) : acc.  Element-wise: out
 // may be base or any share as a whole poly.
 struct FoldShareRef {
@@ -541,6 +576,9 @@ struct FoldLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_fold(const FoldLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const FoldLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || limbs > kMaxLimbs || batch > 65535 || L.count < 1 || L.count > kFoldSharesPerLaunch);
+}
 
 // ---- dckks / dbfv collective key setup (lr_setup.hip): CKGProtocol, RKGProtocol, RKGProtocolNaive, RTGProtocol ----
 constexpr int kSetupPartiesPerLaunch = 32;   // parties (RTG: Galois elements) whose share addresses travel in one launch's kernel arguments
@@ -553,6 +591,7 @@ struct SetupCkgLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_setup_ckg(const SetupCkgLaunch &L, int rows, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const SetupCkgLaunch &L, int rows, int batch) { return launch_verdict(rows <= 0 || batch <= 0, L.n < 2 || rows > kMaxLimbs || batch > 65535); }
 // what the share kernels of RKG, the naive RKG and RTG read: z = party * beta + digit on blockIdx.z, every row of Q||P.  e = the
 // transformed noise, `per` polys per z (item z * per + c); t = the transformed ternary of item z; out[party] = the party's share,
 // member digit (a share of polys) or members 2 digit and 2 digit + 1 (a share of pairs).  Digit i owns rows i alpha .. min((i + 1)
@@ -576,6 +615,12 @@ struct SetupShareLaunch {
 };
 enum SetupShareKind { kSetupRkg1, kSetupRkg2, kSetupRkg3, kSetupNaive1, kSetupNaive2, kSetupRtg };
 hipError_t launch_setup_share(int kind, const SetupShareLaunch &L, int rows, int parties, hipStream_t stream);
+// (the kind is the launcher's own switch: an unknown one is refused there)
+inline LaunchVerdict launch_verdict(const SetupShareLaunch &L, int rows, int parties) {
+    return launch_verdict(rows <= 0 || parties <= 0, L.n < 2 || L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || rows > kMaxLimbs ||
+                                                         parties > kSetupPartiesPerLaunch || L.beta < 1 || L.beta > kMaxLimbs || L.alpha < 1 ||
+                                                         L.nQ < 1 || L.nQ > rows);
+}
 // the finalize steps over the beta digits of one key image (member 2 i = [i][0], 2 i + 1 = [i][1]), z = digit:
 //   RKG    (dbfv/relinkey_gen.go:343-354): evk[i][0] = MForm(CRed(round2[i][0] + round3[i])), evk[i][1] = MForm(round2[i][1])
 //   naive  (dbfv/relinkey_gen_naive.go:187-200): the same without a round3
@@ -591,8 +636,12 @@ struct SetupKeyLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_setup_key(const SetupKeyLaunch &L, int rows, int beta, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const SetupKeyLaunch &L, int rows, int beta) {
+    return launch_verdict(rows <= 0 || beta <= 0, L.n < 2 || rows > kMaxLimbs || beta > kMaxLimbs || (!L.pairs && (!L.polys || !L.crp)));
+}
 
 // ---- dckks / dbfv Refresh (lr_refresh.hip): RefreshProtocol.GenShares, Recode, Recrypt, Finalize ----
+constexpr int kCkksCrtMaxWords = 32;            // 64-bit words of the largest Q the CKKS decoder's CRT takes (2048 bits), and of a Refresh mask
 // out[b][i][j] = big.Int.Mod(mask[b][j], q_i) for i < limbs: SetCoefficientsBigint(Lvl) (ring/ring_context.go:343-367) of a signed integer
 // in two's complement on `words` little-endian 64-bit words, word planes [batch][words][N]
 struct RefreshMaskLaunch {
@@ -604,6 +653,9 @@ struct RefreshMaskLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_refresh_mask(const RefreshMaskLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const RefreshMaskLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || L.words < 1 || L.words > kCkksCrtMaxWords || limbs > kMaxLimbs || batch > 65535);
+}
 // dckks GenShares :78-92 on one row of Q, NTT domain.  Rows below dec_limbs: dec = CRed(CRed(mask + MRed(sk, c1)) + e0); every row:
 // rec = q - CRed(CRed(mask + MRed(sk, crs)) + e1)
 struct RefreshCkksShareLaunch {
@@ -614,6 +666,9 @@ struct RefreshCkksShareLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_refresh_ckks_share(const RefreshCkksShareLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const RefreshCkksShareLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || limbs > kMaxLimbs || L.dec_limbs < 1 || L.dec_limbs > limbs || batch > 65535);
+}
 // dckks Recode :114-136 per coefficient, coefficient domain: v = the CRT of rows 0 .. ls of `in` in [0, Q_ls) as mixed-radix digits (Garner),
 // v >= Q_ls >> 1 => v -= Q_ls, out[i] = v mod q_i (Euclidean) for rows row0 .. limbs - 1 of `out`
 struct RefreshRecodeLaunch {
@@ -628,6 +683,9 @@ struct RefreshRecodeLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_refresh_recode(const RefreshRecodeLaunch &L, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const RefreshRecodeLaunch &L, int batch) {
+    return launch_verdict(batch <= 0 || L.row0 >= L.limbs, L.n < 2 || L.limbs > kMaxLimbs || L.ls < 0 || L.ls >= L.limbs || L.row0 < 0 || batch > 65535);
+}
 // dbfv GenShares :117-122 and :141-142 on one row of Q||P, NTT domain, in place: rows of Q: a = MRed(MRed(sk, a), MForm(P mod q));
 // every row: b = q - MRed(sk, b) (Neg: a zero becomes q)
 struct RefreshBfvProductLaunch {
@@ -639,6 +697,9 @@ struct RefreshBfvProductLaunch {
     const LimbParams *lp;              // of contextQP
 };
 hipError_t launch_refresh_bfv_product(const RefreshBfvProductLaunch &L, int rows, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const RefreshBfvProductLaunch &L, int rows, int batch) {
+    return launch_verdict(rows <= 0 || batch <= 0, L.n < 2 || rows > kMaxLimbs || L.nQ < 1 || L.nQ > rows || batch > 65535);
+}
 // dbfv lift :199-205 and what follows it: m = MRed(row, deltaMont_i); dec = CRed(dec + m) and, with rec, rec = CRed(rec + q - m) (GenShares
 // :153-159); plus: dec = CRed(m + plus) (Recode's lift and Recrypt's Add, :178-185)
 struct RefreshBfvLiftLaunch {
@@ -650,13 +711,15 @@ struct RefreshBfvLiftLaunch {
     const LimbParams *lp;
 };
 hipError_t launch_refresh_bfv_lift(const RefreshBfvLiftLaunch &L, int limbs, int batch, hipStream_t stream);
+inline LaunchVerdict launch_verdict(const RefreshBfvLiftLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || limbs > kMaxLimbs || batch > 65535 || !L.dec || (L.plus == nullptr) == (L.rec == nullptr));
+}
 
 // ---- ckks.Encoder (lr_ckks_encode.hip): Encode / Decode of ckks/encoder.go for a batch of plaintexts ----
 struct Cplx { double re, im; };                 // a complex128 as Go lays it out
 constexpr int kCkksFusedMaxLogSlots = 13;       // the fused kernels hold 16 * slots bytes in one CU's LDS: 128 KiB of the 160
 constexpr int kCkksOneKernelBatch = 256;        // fused Encode as ONE kernel from this batch on: a workgroup per CU of the MI355X (below)
 constexpr int kCkksTileMaxLog = 11;             // the tiled route's LDS tile, at most 2^11 slots (32 KiB)
-constexpr int kCkksCrtMaxWords = 32;            // 64-bit words of the largest Q the decoder's CRT takes (2048 bits)
 // NewEncoder's tables (ckks/encoder.go:37-53): roots[0 .. m] with m = 2 N, rotGroup[j] = 5^j mod m for j < N / 2
 struct CkksEncTables {
     const Cplx *roots;     // [2 N + 1]
@@ -795,6 +858,14 @@ __device__ __forceinline__ void st_stream(ulonglong2 *p, ulonglong2 v) {
     t.x = v.x;
     t.y = v.y;
     __builtin_nontemporal_store(t, reinterpret_cast<lr_u64x2 *>(p));
+}
+
+// The launch every launcher ends on: drop stale (non-sticky) errors of unrelated earlier calls, launch, and return this launch's own error.
+template <class Kernel, class... Args>
+inline hipError_t launch_kernel(Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args &...args) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+    return hipGetLastError();
 }
 #endif
 

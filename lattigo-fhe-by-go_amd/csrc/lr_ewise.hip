@@ -1,12 +1,11 @@
 // lr_ewise.hip -- the coefficient-wise family of ring/ring.go as one templated streaming kernel.
 //
-// HBM-bound (16-24 B per coefficient): 16 B per lane per access, limb index on blockIdx.y so the
-// per-modulus constants are wave-uniform (SGPRs), batch on blockIdx.z.  An operand whose batch
+// HBM-bound (16-24 B per coefficient): streaming passes (lr_stream.hpp), batch on blockIdx.z.  An operand whose batch
 // is 1 is broadcast (poly stride 0).
 #include <atomic>
 
 #include "lattigo_ring.h"
-#include "lr_device.hpp"
+#include "lr_stream.hpp"
 
 namespace lr {
 
@@ -59,11 +58,11 @@ __global__ __launch_bounds__(256) void ewise_kernel(EwiseLaunch L) {
     const LimbParams lp = L.lp[limb];
     const u64 s = L.has_scalars ? L.scalars.v[limb] : 0;
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(L.a + b * L.a_stride + row);
-    const ulonglong2 *pb = reads_b(OP) ? reinterpret_cast<const ulonglong2 *>(L.b + b * L.b_stride + row) : nullptr;
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(L.out + b * L.out_stride + row);
+    const ulonglong2 *pa = row_in(L.a, b, L.a_stride, row);
+    const ulonglong2 *pb = reads_b(OP) ? row_in(L.b, b, L.b_stride, row) : nullptr;
+    ulonglong2 *po = row_out(L.out, b, L.out_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         const ulonglong2 x = ld_stream(pa + e);
         ulonglong2 y = make_ulonglong2(0, 0), z = make_ulonglong2(0, 0);
         if constexpr (reads_b(OP)) y = ld_stream(pb + e);
@@ -76,14 +75,7 @@ __global__ __launch_bounds__(256) void ewise_kernel(EwiseLaunch L) {
 
 template <int OP>
 static hipError_t launch_one(const EwiseLaunch &L, int limbs, int batch, hipStream_t stream) {
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();  // drop stale (non-sticky) errors of unrelated earlier calls
-    hipLaunchKernelGGL(ewise_kernel<OP>, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(ewise_kernel<OP>, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 hipError_t launch_ewise(int op, const EwiseLaunch &L, int limbs, int batch, hipStream_t stream) {
@@ -131,11 +123,11 @@ __global__ __launch_bounds__(256) void submul_kernel(SubMulLaunch L) {
     const u64 c = L.consts[limb];
     const u64 add = L.addend.v[limb];
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(L.a + b * L.a_stride + row);
+    const ulonglong2 *pa = row_in(L.a, b, L.a_stride, row);
     const ulonglong2 *pb = reinterpret_cast<const ulonglong2 *>(L.b + b * L.b_stride + (long long)limb * L.b_row_stride);
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(L.out + b * L.out_stride + row);
+    ulonglong2 *po = row_out(L.out, b, L.out_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         const ulonglong2 x = ld_stream(pa + e);
         ulonglong2 y = ld_stream(pb + e);
         if (L.reduce_b) {
@@ -144,7 +136,7 @@ __global__ __launch_bounds__(256) void submul_kernel(SubMulLaunch L) {
         }
         ulonglong2 r = make_ulonglong2(mred(x.x + (lp.q - y.x), c, lp.q, lp.qinv), mred(x.y + (lp.q - y.y), c, lp.q, lp.qinv));
         if (L.plus) {
-            const ulonglong2 p = ld_stream(reinterpret_cast<const ulonglong2 *>(L.plus + b * L.plus_stride + row) + e);
+            const ulonglong2 p = ld_stream(row_in(L.plus, b, L.plus_stride, row) + e);
             r.x = cred(p.x + r.x, lp.q);
             r.y = cred(p.y + r.y, lp.q);
         }
@@ -171,11 +163,11 @@ __global__ __launch_bounds__(256) void tensor_kernel(TensorLaunch L) {
     const ulonglong2 *pa1 = reinterpret_cast<const ulonglong2 *>((tb ? tb[1] : L.a1 + b * L.a1_stride) + row);
     const ulonglong2 *pb0 = reinterpret_cast<const ulonglong2 *>((tb ? tb[2] : L.b0 + b * L.b0_stride) + row);
     const ulonglong2 *pb1 = reinterpret_cast<const ulonglong2 *>((tb ? tb[3] : L.b1 + b * L.b1_stride) + row);
-    ulonglong2 *pc0 = reinterpret_cast<ulonglong2 *>(L.c0 + b * L.c_stride + row);
-    ulonglong2 *pc1 = reinterpret_cast<ulonglong2 *>(L.c1 + b * L.c1_stride + row);
-    ulonglong2 *pc2 = reinterpret_cast<ulonglong2 *>(L.c2 + b * L.c2_stride + row);
+    ulonglong2 *pc0 = row_out(L.c0, b, L.c_stride, row);
+    ulonglong2 *pc1 = row_out(L.c1, b, L.c1_stride, row);
+    ulonglong2 *pc2 = row_out(L.c2, b, L.c2_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         // (the squaring case -- ct0 == ct1, ckks/evaluator.go:1083, bfv/evaluator.go:334 -- reads its one operand once: block-uniform)
         const ulonglong2 a0 = ld_stream(pa0 + e), a1 = ld_stream(pa1 + e);
         const ulonglong2 b0 = pb0 == pa0 ? a0 : ld_stream(pb0 + e), b1 = pb1 == pa1 ? a1 : ld_stream(pb1 + e);
@@ -239,7 +231,7 @@ __global__ __launch_bounds__(256) void tensor_deg_kernel(TensorDegLaunch L) {
     const long long off = (long long)blockIdx.z * L.stride + (long long)limb * L.n;
     const LimbParams lp = L.lp[limb];
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         ulonglong2 va[D0 + 1], vb[NB + 1];
 #pragma unroll
         for (int i = 0; i <= D0; ++i) va[i] = ld_stream(reinterpret_cast<const ulonglong2 *>(L.a[i] + off) + e);
@@ -272,14 +264,14 @@ __global__ __launch_bounds__(256) void horner_kernel(HornerLaunch L) {
     const LimbParams lp = L.lp[limb];
     const u64 q = lp.q;
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(L.sk + b * L.sk_stride + row);
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(L.out + b * L.out_stride + row);
+    const ulonglong2 *ps = row_in(L.sk, b, L.sk_stride, row);
+    ulonglong2 *po = row_out(L.out, b, L.out_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         const ulonglong2 s = L.degree > 0 ? ps[e] : make_ulonglong2(0, 0);        // (the key is shared by the batch: through the caches)
-        ulonglong2 acc = ld_stream(reinterpret_cast<const ulonglong2 *>(L.ct[L.degree] + b * L.ct_stride[L.degree] + row) + e);    // :61 CopyLvl
+        ulonglong2 acc = ld_stream(row_in(L.ct[L.degree], b, L.ct_stride[L.degree], row) + e);    // :61 CopyLvl
         for (int i = L.degree; i > 0; --i) {
-            const ulonglong2 c = ld_stream(reinterpret_cast<const ulonglong2 *>(L.ct[i - 1] + b * L.ct_stride[i - 1] + row) + e);
+            const ulonglong2 c = ld_stream(row_in(L.ct[i - 1], b, L.ct_stride[i - 1], row) + e);
             acc.x = cred(mred(acc.x, s.x, q, lp.qinv) + c.x, q);                 // :67-68
             acc.y = cred(mred(acc.y, s.y, q, lp.qinv) + c.y, q);
             if ((i & 7) == 7) {                                                  // :70-72
@@ -298,14 +290,7 @@ __global__ __launch_bounds__(256) void horner_kernel(HornerLaunch L) {
 hipError_t launch_horner(const HornerLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
     if (L.degree < 0 || L.degree > kHornerMaxDegree) return hipErrorInvalidValue;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(horner_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(horner_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 __global__ __launch_bounds__(256) void bswap_kernel(const u64 *in, u64 *out, size_t words) {
@@ -317,9 +302,7 @@ hipError_t launch_bswap(const u64 *in, u64 *out, size_t words, hipStream_t strea
     if (words == 0) return hipSuccess;
     size_t blocks = (words + 255) / 256;
     if (blocks > 65535) blocks = 65535;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(bswap_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, in, out, words);
-    return hipGetLastError();
+    return launch_kernel(bswap_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, in, out, words);
 }
 
 __global__ __launch_bounds__(256) void scalar_pair_kernel(ScalarPairLaunch L) {
@@ -328,10 +311,10 @@ __global__ __launch_bounds__(256) void scalar_pair_kernel(ScalarPairLaunch L) {
     const LimbParams lp = L.lp[limb];
     const u64 q = lp.q, s1 = L.sub.v[limb], s2 = L.mul.v[limb];
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *pi = reinterpret_cast<const ulonglong2 *>(L.in + b * L.in_stride + row);
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(L.out + b * L.out_stride + row);
+    const ulonglong2 *pi = row_in(L.in, b, L.in_stride, row);
+    ulonglong2 *po = row_out(L.out, b, L.out_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         const ulonglong2 x = ld_stream(pi + e);
         st_stream(po + e, make_ulonglong2(mred(cred(x.x + (q - s1), q), s2, q, lp.qinv), mred(cred(x.y + (q - s1), q), s2, q, lp.qinv)));
     }
@@ -339,14 +322,7 @@ __global__ __launch_bounds__(256) void scalar_pair_kernel(ScalarPairLaunch L) {
 
 hipError_t launch_scalar_pair(const ScalarPairLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(scalar_pair_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(scalar_pair_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // GaloisLaunch::gen carries the shift (mod 2N)
@@ -359,7 +335,7 @@ __global__ __launch_bounds__(256) void monomial_kernel(GaloisLaunch L) {
     const int n = L.n;
     const bool flip = L.gen >= (u64)n;           // X^N = -1: the whole polynomial changes sign first (:700-707)
     const int shift = (int)(L.gen % (u64)n);
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
+    LR_FOR_PAIRS(j, n) {
         if (L.gen == 0) {
             po[j] = pi[j];                         // :669-678
             continue;
@@ -373,12 +349,7 @@ __global__ __launch_bounds__(256) void monomial_kernel(GaloisLaunch L) {
 
 hipError_t launch_monomial(const GaloisLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    int gx = (L.n + 255) / 256;
-    if (gx > 64) gx = 64;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(monomial_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(monomial_kernel, coeff_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // ring_scaling.go:275-300.  `a` accumulates without reduction and wraps modulo 2^64 exactly like the reference's uint64.
@@ -420,27 +391,17 @@ hipError_t launch_simple_scale(const ScaleLaunch &L, int batch, hipStream_t stre
     if (batch <= 0 || L.limbs_out <= 0) return hipSuccess;
     int gx = (L.n + 255) / 256;
     if (gx > 1024) gx = 1024;
-    const dim3 grid((unsigned)gx, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(simple_scale_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(simple_scale_kernel, dim3((unsigned)gx, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 hipError_t launch_tensor(const TensorLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(tensor_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(tensor_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool square, int limbs, int batch, hipStream_t stream) {
-    if (d0 < 0 || d1 < 0 || d0 + d1 < 1 || d0 + d1 > kTensorMaxDegree) return hipErrorInvalidValue;
-    if (square && !(d0 == 2 && d1 == 2)) return hipErrorInvalidValue;
+    const LaunchVerdict v = launch_verdict(L, d0, d1, square, limbs, batch);
+    if (v == kLaunchRefuse) return hipErrorInvalidValue;
     using K = void (*)(TensorDegLaunch);
     // [d0][d1] for d0 + d1 <= 5; (1, 1) is tensor_kernel's (bfv/evaluator.go:320-369)
     static const K table[kTensorMaxDegree + 1][kTensorMaxDegree + 1] = {
@@ -454,14 +415,7 @@ hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool squa
     const K k = square ? tensor_deg_kernel<2, 2, true> : table[d0][d1];
     if (!k) return hipErrorInvalidValue;
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(k, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 __global__ __launch_bounds__(256) void scatter_kernel(ScatterLaunch L) {
@@ -469,23 +423,16 @@ __global__ __launch_bounds__(256) void scatter_kernel(ScatterLaunch L) {
     const long long b = blockIdx.z;
     const int pairs = L.n >> 1;
     for (int k = 0; k < L.per_poly; ++k) {
-        const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(L.src[k] + b * L.stride + row);
+        const ulonglong2 *ps = row_in(L.src[k], b, L.stride, row);
         ulonglong2 *pd = reinterpret_cast<ulonglong2 *>(L.table[b * L.per_poly + k] + row);
-        for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) st_stream(pd + e, ld_stream(ps + e));
+        LR_FOR_PAIRS(e, pairs) st_stream(pd + e, ld_stream(ps + e));
     }
 }
 
 hipError_t launch_scatter(const ScatterLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
     if (L.per_poly < 1 || L.per_poly > 4) return hipErrorInvalidValue;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(scatter_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(scatter_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // pkEncryptor.encrypt, ckks/encryptor.go:209-211: MulCoeffsMontgomery(u, pk[0]) and (u, pk[1]) in one pass over u
@@ -494,30 +441,22 @@ __global__ __launch_bounds__(256) void mul2_kernel(Mul2Launch L) {
     const long long b = blockIdx.z;
     const LimbParams lp = L.lp[limb];
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(L.a + b * L.a_stride + row);
-    const ulonglong2 *pb0 = reinterpret_cast<const ulonglong2 *>(L.b0 + b * L.b0_stride + row);
-    const ulonglong2 *pb1 = reinterpret_cast<const ulonglong2 *>(L.b1 + b * L.b1_stride + row);
-    ulonglong2 *po0 = reinterpret_cast<ulonglong2 *>(L.out0 + b * L.out0_stride + row);
-    ulonglong2 *po1 = reinterpret_cast<ulonglong2 *>(L.out1 + b * L.out1_stride + row);
+    const ulonglong2 *pa = row_in(L.a, b, L.a_stride, row);
+    const ulonglong2 *pb0 = row_in(L.b0, b, L.b0_stride, row);
+    const ulonglong2 *pb1 = row_in(L.b1, b, L.b1_stride, row);
+    ulonglong2 *po0 = row_out(L.out0, b, L.out0_stride, row);
+    ulonglong2 *po1 = row_out(L.out1, b, L.out1_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
-        const ulonglong2 a = ld_stream(pa + e);
-        const ulonglong2 k0 = L.b0_stride ? ld_stream(pb0 + e) : pb0[e], k1 = L.b1_stride ? ld_stream(pb1 + e) : pb1[e];     // (a key shared by the batch: through the caches)
-        st_stream(po0 + e, make_ulonglong2(mred(a.x, k0.x, lp.q, lp.qinv), mred(a.y, k0.y, lp.q, lp.qinv)));
-        st_stream(po1 + e, make_ulonglong2(mred(a.x, k1.x, lp.q, lp.qinv), mred(a.y, k1.y, lp.q, lp.qinv)));
+    LR_FOR_PAIRS(e, pairs) {
+        const ulonglong2 a = ld_stream(pa + e), k0 = ld_shared(pb0, L.b0_stride, e), k1 = ld_shared(pb1, L.b1_stride, e);
+        st_stream(po0 + e, mul2(a, k0, lp.q, lp.qinv));
+        st_stream(po1 + e, mul2(a, k1, lp.q, lp.qinv));
     }
 }
 
 hipError_t launch_mul2(const Mul2Launch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mul2_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(mul2_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 __global__ __launch_bounds__(256) void gather_kernel(GatherLaunch L) {
@@ -526,57 +465,36 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherLaunch L) {
     const int pairs = L.n >> 1;
     for (int k = 0; k < L.per_poly; ++k) {
         const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(L.table[b * L.per_poly + k] + row);
-        ulonglong2 *pd = reinterpret_cast<ulonglong2 *>(L.dst[k] + b * L.stride + row);
-        for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) st_stream(pd + e, ld_stream(ps + e));
+        ulonglong2 *pd = row_out(L.dst[k], b, L.stride, row);
+        LR_FOR_PAIRS(e, pairs) st_stream(pd + e, ld_stream(ps + e));
     }
 }
 
 hipError_t launch_gather(const GatherLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
     if (L.per_poly < 1 || L.per_poly > 4) return hipErrorInvalidValue;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(gather_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(gather_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 __global__ __launch_bounds__(256) void multicopy_kernel(MultiCopyLaunch L) {
     const int k = blockIdx.z / L.batch;
     const long long b = blockIdx.z % L.batch;
     const long long row = (long long)blockIdx.y * L.n;
-    const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(L.src[k] + b * L.src_stride[k] + row);
-    ulonglong2 *pd = reinterpret_cast<ulonglong2 *>(L.dst[k] + b * L.dst_stride[k] + row);
+    const ulonglong2 *ps = row_in(L.src[k], b, L.src_stride[k], row);
+    ulonglong2 *pd = row_out(L.dst[k], b, L.dst_stride[k], row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) st_stream(pd + e, ld_stream(ps + e));
+    LR_FOR_PAIRS(e, pairs) st_stream(pd + e, ld_stream(ps + e));
 }
 
 hipError_t launch_multicopy(const MultiCopyLaunch &L, int limbs, hipStream_t stream) {
     if (L.count > kMultiCopyMax) return hipErrorInvalidValue;
     if (limbs <= 0 || L.batch <= 0 || L.count <= 0) return hipSuccess;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)(L.count * L.batch)), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(multicopy_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(multicopy_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)(L.count * L.batch)), dim3(256), 0, stream, L);
 }
 
 hipError_t launch_submul(const SubMulLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    const int pairs = L.n >> 1;
-    int gx = (pairs + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();  // drop stale (non-sticky) errors of unrelated earlier calls
-    hipLaunchKernelGGL(submul_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(submul_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // ---- single-limb helpers for rescale ---------------------------------------------------------
@@ -589,7 +507,7 @@ __global__ __launch_bounds__(256) void rowadd_kernel(RowAddLaunch L) {
     const u64 add = L.adds.v[row];
     const u64 *pi = L.in + b * L.in_stride;
     u64 *po = L.out + b * L.out_stride + (long long)row * L.n;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < L.n; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, L.n) {
         u64 v = pi[e] + add;
         if (L.q) v = cred(v, L.q);
         po[e] = v;
@@ -598,12 +516,7 @@ __global__ __launch_bounds__(256) void rowadd_kernel(RowAddLaunch L) {
 
 hipError_t launch_rowadd(const RowAddLaunch &L, int rows, int batch, hipStream_t stream) {
     if (rows <= 0 || batch <= 0) return hipSuccess;
-    int gx = (L.n + 255) / 256;
-    if (gx > 64) gx = 64;
-    const dim3 grid((unsigned)gx, (unsigned)rows, (unsigned)batch), block(256);
-    (void)hipGetLastError();  // drop stale (non-sticky) errors of unrelated earlier calls
-    hipLaunchKernelGGL(rowadd_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(rowadd_kernel, coeff_grid(L.n, (unsigned)rows, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // ---- half-vector scalar operations: AddConst / MultByConst / MultByConstAndAdd / MultByi / DivByi of ckks.Evaluator ------------
@@ -614,10 +527,10 @@ __global__ __launch_bounds__(256) void half_scalar_kernel(HalfScalarLaunch L) {
     const long long b = blockIdx.z;
     const LimbParams lp = L.lp[limb];
     const u64 slo = L.lo.v[limb], shi = L.hi.v[limb];
-    const ulonglong2 *pi = reinterpret_cast<const ulonglong2 *>(L.in + b * L.in_stride + (long long)limb * L.n);
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(L.out + b * L.out_stride + (long long)limb * L.n);
+    const ulonglong2 *pi = row_in(L.in, b, L.in_stride, (long long)limb * L.n);
+    ulonglong2 *po = row_out(L.out, b, L.out_stride, (long long)limb * L.n);
     const int pairs = L.n >> 1, half = L.n >> 2;       // n / 2 coefficients = n / 4 pairs per half
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         const u64 sc = e < half ? slo : shi;
         const ulonglong2 x = ld_stream(pi + e);
         ulonglong2 r;
@@ -635,12 +548,7 @@ __global__ __launch_bounds__(256) void half_scalar_kernel(HalfScalarLaunch L) {
 
 hipError_t launch_half_scalar(const HalfScalarLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    int gx = ((L.n >> 1) + 255) / 256;
-    if (gx > 64) gx = 64;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(half_scalar_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(half_scalar_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // ---- hybrid key-switch inner product (ckks/evaluator.go:1511-1552) ---------------------------------
@@ -651,17 +559,11 @@ hipError_t launch_half_scalar(const HalfScalarLaunch &L, int limbs, int batch, h
 // never travel through HBM.
 // BETA > 0: the digit count is known at compile time, so all of a coefficient pair's digit and key loads are issued
 // before the first multiply (memory-level parallelism instead of one load round trip per digit); BETA = 0: generic.
-// ring.PermuteNTT's index (ring/ring_galois.go:29-50): out[j] = in[perm_index(j)], computed on the fly (two bit reversals)
-__device__ __forceinline__ u32 perm_index(u32 j, u32 gen, int shift, u32 mask2) {
-    const u32 t1 = 2 * (__brev(j) >> shift) + 1;
-    const u32 t2 = (((gen * t1) & mask2) - 1) >> 1;
-    return __brev(t2) >> shift;
-}
 // the digit operand of a coefficient pair: the caller's own row, the permuted digit (hoisted rotations: the Galois automorphism of the
 // digits rides on the inner product's loads instead of a pass that writes permuted copies of every digit), or the plain digit
 #define LR_KEYMAC_OPERAND_SETUP                                                                                                   \
     const u32 pgen = L.perm_gen;                                                                                                  \
-    const int pshift = 32 - L.logn;                                                                                               \
+    const int plogn = L.logn;                                                                                                     \
     const u32 pmask2 = 2u * (u32)L.n - 1u;                                                                                        \
     const u64 *pc64 = reinterpret_cast<const u64 *>(pc);
 #define LR_KEYMAC_OPERAND(i_)                                                                                                     \
@@ -682,18 +584,18 @@ __global__ __launch_bounds__(256) void keymac_kernel(KeyMacLaunch L) {
     const int chunks = L.tile8 ? (int)gridDim.z * 8 : (int)gridDim.z;
     const LimbParams lp = L.lp[limb];
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *pc = reinterpret_cast<const ulonglong2 *>(L.c2 + b * L.c2_poly_stride + row);
+    const ulonglong2 *pc = row_in(L.c2, b, L.c2_poly_stride, row);
     const ulonglong2 *pk = reinterpret_cast<const ulonglong2 *>(L.key + (long long)(L.key_limb0 + limb) * L.n);
-    ulonglong2 *po0 = reinterpret_cast<ulonglong2 *>(L.out0 + b * L.out_stride + row);
-    ulonglong2 *po1 = reinterpret_cast<ulonglong2 *>(L.out1 + b * L.out1_stride + row);
+    ulonglong2 *po0 = row_out(L.out0, b, L.out_stride, row);
+    ulonglong2 *po1 = row_out(L.out1, b, L.out1_stride, row);
     const long long cd = L.c2_digit_stride >> 1, kd = L.key_poly_stride >> 1;   // in 16-byte units
-    const ulonglong2 *pown = L.alpha > 0 ? reinterpret_cast<const ulonglong2 *>(L.own + b * L.own_stride + row) : nullptr;
+    const ulonglong2 *pown = L.alpha > 0 ? row_in(L.own, b, L.own_stride, row) : nullptr;
     const int own_digit = L.alpha > 0 ? limb / L.alpha : -1;
     const int pairs = L.n >> 1;
     const int beta = BETA > 0 ? BETA : L.beta;
     LR_KEYMAC_OPERAND_SETUP
     for (int e = chunk * 256 + threadIdx.x; e < pairs; e += chunks * 256) {
-        const u32 ix0 = pgen ? perm_index(2u * (u32)e, pgen, pshift, pmask2) : 0u, ix1 = pgen ? perm_index(2u * (u32)e + 1u, pgen, pshift, pmask2) : 0u;
+        const u32 ix0 = pgen ? galois_index(2u * (u32)e, pgen, pmask2, plogn) : 0u, ix1 = pgen ? galois_index(2u * (u32)e + 1u, pgen, pmask2, plogn) : 0u;
         u64 a0x = 0, a0y = 0, a1x = 0, a1y = 0;
         if constexpr (BETA > 0) {
             // groups of at most G digits: all loads of a group are in flight before its first multiply; beyond six digits one
@@ -807,19 +709,19 @@ __device__ __forceinline__ void keymac_wide_body(const KeyMacLaunch &L, int limb
     const int chunks = L.tile8 ? (int)gridDim.z * 8 : (int)gridDim.z;
     const LimbParams lp = L.lp[limb];
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *pc = reinterpret_cast<const ulonglong2 *>(L.c2 + b * L.c2_poly_stride + row);
+    const ulonglong2 *pc = row_in(L.c2, b, L.c2_poly_stride, row);
     const ulonglong2 *pk = reinterpret_cast<const ulonglong2 *>(L.key + (long long)(L.key_limb0 + limb) * L.n);
-    ulonglong2 *po0 = reinterpret_cast<ulonglong2 *>(L.out0 + b * L.out_stride + row);
-    ulonglong2 *po1 = reinterpret_cast<ulonglong2 *>(L.out1 + b * L.out1_stride + row);
+    ulonglong2 *po0 = row_out(L.out0, b, L.out_stride, row);
+    ulonglong2 *po1 = row_out(L.out1, b, L.out1_stride, row);
     const long long cd = L.c2_digit_stride >> 1, kd = L.key_poly_stride >> 1;   // in 16-byte units
-    const ulonglong2 *pown = L.alpha > 0 ? reinterpret_cast<const ulonglong2 *>(L.own + b * L.own_stride + row) : nullptr;
+    const ulonglong2 *pown = L.alpha > 0 ? row_in(L.own, b, L.own_stride, row) : nullptr;
     const int own_digit = L.alpha > 0 ? limb / L.alpha : -1;
     const int pairs = L.n >> 1;
     const int beta = BETA > 0 ? BETA : L.beta;
     constexpr int G = BETA > 0 ? (BETA <= 6 ? BETA : (BETA + 1) / 2) : 1;      // digits whose loads are in flight together
     LR_KEYMAC_OPERAND_SETUP
     for (int e = chunk * 256 + threadIdx.x; e < pairs; e += chunks * 256) {
-        const u32 ix0 = pgen ? perm_index(2u * (u32)e, pgen, pshift, pmask2) : 0u, ix1 = pgen ? perm_index(2u * (u32)e + 1u, pgen, pshift, pmask2) : 0u;
+        const u32 ix0 = pgen ? galois_index(2u * (u32)e, pgen, pmask2, plogn) : 0u, ix1 = pgen ? galois_index(2u * (u32)e + 1u, pgen, pmask2, plogn) : 0u;
         u64 lo[4] = {0, 0, 0, 0}, mid[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
         u32 cy[4] = {0, 0, 0, 0};
         if constexpr (BETA > 0) {
@@ -875,53 +777,46 @@ __device__ __forceinline__ void keymac_wide_body(const KeyMacLaunch &L, int limb
 hipError_t launch_keymac(const KeyMacLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
     if (L.perm_gen != 0 && (L.alpha > 0 || L.logn < 1 || L.logn > 31 || (1 << L.logn) != L.n)) return hipErrorInvalidValue;   // permuted digits carry their own limbs
-    int gx = ((L.n >> 1) + 255) / 256;
-    if (gx > 64) gx = 64;
+    const int gx = pair_blocks(L.n);
     KeyMacLaunch K = L;
     K.tile8 = (gx % 8 == 0 && (long long)batch * 8 < (1ll << 31)) ? 1 : 0;
     const dim3 grid(K.tile8 ? (unsigned)batch * 8u : (unsigned)batch, (unsigned)limbs, K.tile8 ? (unsigned)gx / 8u : (unsigned)gx), block(256);
-    (void)hipGetLastError();
     if (K.wide) {
         switch (L.beta) {
 #define LR_KMW(B) \
-    case B: hipLaunchKernelGGL(keymac_wide_kernel<B>, grid, block, 0, stream, K); break;
+    case B: return launch_kernel(keymac_wide_kernel<B>, grid, block, 0, stream, K);
             LR_KMW(1) LR_KMW(2) LR_KMW(3) LR_KMW(4) LR_KMW(5) LR_KMW(6) LR_KMW(7) LR_KMW(8) LR_KMW(9) LR_KMW(10)
 #undef LR_KMW
-        default: hipLaunchKernelGGL(keymac_wide_kernel<0>, grid, block, 0, stream, K); break;
+        default: return launch_kernel(keymac_wide_kernel<0>, grid, block, 0, stream, K);
         }
-        return hipGetLastError();
     }
     switch (L.beta) {
 #define LR_KM(B) \
-    case B: hipLaunchKernelGGL(keymac_kernel<B>, grid, block, 0, stream, K); break;
+    case B: return launch_kernel(keymac_kernel<B>, grid, block, 0, stream, K);
         LR_KM(1) LR_KM(2) LR_KM(3) LR_KM(4) LR_KM(5) LR_KM(6) LR_KM(7) LR_KM(8) LR_KM(9) LR_KM(10)
 #undef LR_KM
-    default: hipLaunchKernelGGL(keymac_kernel<0>, grid, block, 0, stream, K); break;
+    default: return launch_kernel(keymac_kernel<0>, grid, block, 0, stream, K);
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_keymac_pair(const KeyMacLaunch &A, int limbs_a, const KeyMacLaunch &B, int limbs_b, int batch, hipStream_t stream) {
     if (limbs_a <= 0 || limbs_b <= 0 || batch <= 0) return hipErrorNotSupported;
     if (!A.wide || !B.wide || A.beta != B.beta || A.n != B.n || A.beta < 1 || A.beta > 10) return hipErrorNotSupported;
     if ((A.perm_gen != 0 && A.alpha > 0) || (B.perm_gen != 0 && B.alpha > 0)) return hipErrorInvalidValue;
-    int gx = ((A.n >> 1) + 255) / 256;
-    if (gx > 64) gx = 64;
+    const int gx = pair_blocks(A.n);
     KeyMacPair P;
     P.a = A;
     P.b = B;
     P.split = limbs_a;
     P.a.tile8 = P.b.tile8 = (gx % 8 == 0 && (long long)batch * 8 < (1ll << 31)) ? 1 : 0;
     const dim3 grid(P.a.tile8 ? (unsigned)batch * 8u : (unsigned)batch, (unsigned)(limbs_a + limbs_b), P.a.tile8 ? (unsigned)gx / 8u : (unsigned)gx), block(256);
-    (void)hipGetLastError();
     switch (A.beta) {
 #define LR_KMP(B_) \
-    case B_: hipLaunchKernelGGL(keymac_wide_pair_kernel<B_>, grid, block, 0, stream, P); break;
+    case B_: return launch_kernel(keymac_wide_pair_kernel<B_>, grid, block, 0, stream, P);
         LR_KMP(1) LR_KMP(2) LR_KMP(3) LR_KMP(4) LR_KMP(5) LR_KMP(6) LR_KMP(7) LR_KMP(8) LR_KMP(9) LR_KMP(10)
 #undef LR_KMP
     default: return hipErrorNotSupported;
     }
-    return hipGetLastError();
 }
 
 // ---- Galois automorphisms, ring/ring_galois.go ---------------------------------------------
@@ -936,9 +831,7 @@ __global__ __launch_bounds__(256) void permute_kernel(GaloisLaunch L) {
     const int logn = L.logn;
     for (u32 j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
         if (L.ntt_domain) {
-            const u32 t1 = 2 * (__brev(j) >> (32 - logn)) + 1;
-            const u32 t2 = ((((u32)L.gen * t1) & mask2) - 1) >> 1;
-            pout[j] = pin[__brev(t2) >> (32 - logn)];
+            pout[j] = pin[galois_index(j, (u32)L.gen, mask2, logn)];
         } else {
             const u64 raw = (u64)j * L.gen;
             const u32 idx = (u32)raw & (n - 1);
@@ -958,8 +851,8 @@ __global__ __launch_bounds__(1024) void permute_coeff_lds_kernel(GaloisLaunch L,
     const int limb = blockIdx.x;
     const long long b = blockIdx.y;
     const u32 n = (u32)L.n, mask2 = 2 * n - 1;
-    const ulonglong2 *pin = reinterpret_cast<const ulonglong2 *>(L.in + b * L.in_stride + (long long)limb * L.n);
-    ulonglong2 *pout = reinterpret_cast<ulonglong2 *>(L.out + b * L.out_stride + (long long)limb * L.n);
+    const ulonglong2 *pin = row_in(L.in, b, L.in_stride, (long long)limb * L.n);
+    ulonglong2 *pout = row_out(L.out, b, L.out_stride, (long long)limb * L.n);
     for (u32 e = threadIdx.x; e < n / 2; e += 1024) {
         const ulonglong2 v = ld_stream(pin + e);
         lr_permute_row[2 * e] = v.x;
@@ -992,18 +885,11 @@ hipError_t launch_permute(const GaloisLaunch &L, int limbs, int batch, hipStream
             state.store(hipFuncSetAttribute(reinterpret_cast<const void *>(permute_coeff_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess ? 1 : 2,
                         std::memory_order_release);
         if (state.load(std::memory_order_acquire) == 1) {
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(permute_coeff_lds_kernel, dim3((unsigned)limbs, (unsigned)batch), dim3(1024), lds, stream, L, inv);
-            return hipGetLastError();
+            return launch_kernel(permute_coeff_lds_kernel, dim3((unsigned)limbs, (unsigned)batch), dim3(1024), lds, stream, L, inv);
         }
         (void)hipGetLastError();     // (the attribute was refused: the scatter form below)
     }
-    int gx = (L.n + 255) / 256;
-    if (gx > 64) gx = 64;
-    const dim3 grid((unsigned)gx, (unsigned)limbs, (unsigned)batch), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(permute_kernel, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return launch_kernel(permute_kernel, coeff_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 }  // namespace lr

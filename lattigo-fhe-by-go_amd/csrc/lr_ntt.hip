@@ -522,9 +522,7 @@ __global__ __launch_bounds__(256) void rescale_mid_kernel(NttLaunch a, const Twi
 hipError_t launch_rescale_mid(const NttLaunch &a, const Twiddle *tw_inv, int last_mod, u64 phalf, int logn, hipStream_t stream) {
     if (a.n_items <= 0 || a.batch <= 0) return hipSuccess;
     const dim3 grid(32, (unsigned)(a.n_items * a.batch)), block(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rescale_mid_kernel, grid, block, 0, stream, a, tw_inv, last_mod, phalf, logn);
-    return hipGetLastError();
+    return launch_kernel(rescale_mid_kernel, grid, block, 0, stream, a, tw_inv, last_mod, phalf, logn);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -550,9 +548,7 @@ static hipError_t launch_fwd(const NttLaunch &a, hipStream_t stream) {
         }
     }
     const dim3 grid((unsigned)((a.n_items << a.sub_log) * a.batch)), block(1u << P::LOGT);
-    (void)hipGetLastError();  // drop stale (non-sticky) errors of unrelated earlier calls
-    hipLaunchKernelGGL(fn, grid, block, lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_kernel(fn, grid, block, lds_bytes, stream, a);
 }
 
 template <int LOGN, bool BIGQ>
@@ -575,9 +571,7 @@ static hipError_t launch_inv(const NttLaunch &a, hipStream_t stream) {
         }
     }
     const dim3 grid((unsigned)((a.n_items << a.sub_log) * a.batch)), block(1u << P::LOGT);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(fn, grid, block, lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_kernel(fn, grid, block, lds_bytes, stream, a);
 }
 
 template <int LOGN>
@@ -595,9 +589,7 @@ static hipError_t launch_big(const NttLaunch &a, bool inverse, int mode, hipStre
 hipError_t launch_ntt_top(const NttLaunch &a, int inverse, hipStream_t stream, int logn) {
     if (a.n_items <= 0 || a.batch <= 0) return hipSuccess;
     const dim3 tgrid(logn == 16 ? 64 : 32, (unsigned)(a.n_items * a.batch)), tblock(256);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ntt_top_kernel, tgrid, tblock, 0, stream, a, logn, inverse);
-    return hipGetLastError();
+    return launch_kernel(ntt_top_kernel, tgrid, tblock, 0, stream, a, logn, inverse);
 }
 
 hipError_t launch_ntt(const NttLaunch &a, int logn, bool inverse, int mode, hipStream_t stream) {
@@ -636,15 +628,11 @@ hipError_t launch_ntt(const NttLaunch &a, int logn, bool inverse, int mode, hipS
         top.in_poly_stride = a.out_poly_stride;
         top.in_limb0 = a.out_limb0;
         top.in_limb_step = a.out_limb_step;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(ntt_top_kernel, tgrid, tblock, 0, stream, top, 16, 1);
-        return hipGetLastError();
+        return launch_kernel(ntt_top_kernel, tgrid, tblock, 0, stream, top, 16, 1);
     }
     if (logn >= 1 && logn <= 11) {
         const dim3 grid((unsigned)(a.n_items * a.batch)), block(256);
-        (void)hipGetLastError();  // drop stale (non-sticky) errors of unrelated earlier calls
-    hipLaunchKernelGGL(ntt_small_kernel, grid, block, sizeof(u64) << logn, stream, a, logn, inverse ? 1 : 0);
-        return hipGetLastError();
+        return launch_kernel(ntt_small_kernel, grid, block, sizeof(u64) << logn, stream, a, logn, inverse ? 1 : 0);
     }
     return hipErrorInvalidValue;
 }

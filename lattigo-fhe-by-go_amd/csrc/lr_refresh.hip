@@ -1,25 +1,17 @@
 // lr_refresh.hip -- the kernels of the collective Refresh (lr_refresh.cpp): the reduction of the multi-word signed masks into RNS rows
 // (SetCoefficientsBigint, dckks/public_refresh.go:66-68), the fused share pass of dckks GenShares (:78-92), Recode's exact centred lift
 // from Q_levelStart to all of Q (:114-136), and for dbfv the products in front of the inverse transforms (dbfv/public_refresh.go:117-122,
-// :141-142) and lift (:199-205) with the additions that follow it.  The streaming kernels are those of lr_collective.hip: 16 B per lane
-// per access, two coefficients per lane, limb on blockIdx.y (per-modulus constants wave-uniform), batch on blockIdx.z.  The noise is
-// expanded by launch_ckks_expand and launch_bfv_noise, Aggregate is launch_fold.
+// :141-142) and lift (:199-205) with the additions that follow it.  The element passes are streaming passes (lr_stream.hpp), batch on
+// blockIdx.z.  The noise is expanded by launch_ckks_expand and launch_bfv_noise, Aggregate is launch_fold.
 //
 // Recode works on mixed-radix digits (Garner) instead of the reference's big.Int: v = d_0 + d_1 q_0 + ... + d_ls q_0 ... q_(ls-1) with
 // d_k < q_k is the same integer as PolyToBigint's, digit strings compare as the integers do, and v mod q_i is a Horner chain of word-size
 // modular steps.  No multi-word value lives in registers: the ls + 1 digits of a coefficient sit in LDS, one column per lane.
-#include "lr_device.hpp"
+#include "lr_stream.hpp"
 
 namespace lr {
 
 namespace {
-
-dim3 pair_grid(int n, unsigned y, unsigned z) {
-    int gx = ((n >> 1) + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    return dim3((unsigned)gx, y, z);
-}
 
 // (r 2^64 + w) mod q for r < q and any word w: one step of big.Int.Mod over the words from the top
 __device__ __forceinline__ u64 word_step(u64 r, u64 w, u64 two64, const LimbParams &lp) {
@@ -36,7 +28,7 @@ __global__ __launch_bounds__(256) void refresh_mask_kernel(RefreshMaskLaunch L) 
     const int n = L.n, W = L.words;
     const u64 *pm = L.mask + b * (long long)W * n;
     u64 *po = L.out + b * L.out_stride + (long long)limb * n;
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
+    LR_FOR_PAIRS(j, n) {                                         // (coeff_grid: one coefficient per lane)
         const u64 top = ld_stream(pm + (long long)(W - 1) * n + j);
         u64 r = bred_add(top, q, lp.bred_hi);
         if (top >> 63) r = cred(r + (q - two64), q);            // the top word is signed: top - 2^64
@@ -46,13 +38,8 @@ __global__ __launch_bounds__(256) void refresh_mask_kernel(RefreshMaskLaunch L) 
 }
 
 hipError_t launch_refresh_mask(const RefreshMaskLaunch &L, int limbs, int batch, hipStream_t stream) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || L.words < 1 || L.words > kCkksCrtMaxWords || limbs > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
-    int gx = (L.n + 255) / 256;
-    if (gx > 64) gx = 64;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(refresh_mask_kernel, dim3((unsigned)gx, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
-    return hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    return launch_kernel(refresh_mask_kernel, coeff_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // MulCoeffsMontgomeryAndAdd (:78, :81), Add (:85, :89) and Neg (:92) in the reference's order, each addition with its CRed; Neg is q - x:
@@ -64,34 +51,23 @@ __global__ __launch_bounds__(256) void refresh_ckks_share_kernel(RefreshCkksShar
     const u64 q = lp.q;
     const long long row = (long long)limb * L.n;
     const bool dec = limb < L.dec_limbs;
-    const ulonglong2 *pm = reinterpret_cast<const ulonglong2 *>(L.mask + b * L.r_stride + row);
-    const ulonglong2 *p0 = reinterpret_cast<const ulonglong2 *>(L.e0 + b * L.r_stride + row);
-    const ulonglong2 *p1 = reinterpret_cast<const ulonglong2 *>(L.e1 + b * L.r_stride + row);
-    const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(L.sk + b * L.sk_stride + row);
-    const ulonglong2 *pc = reinterpret_cast<const ulonglong2 *>(L.c1 + b * L.c1_stride + row);
-    const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(L.crs + b * L.crs_stride + row);
-    ulonglong2 *pd = reinterpret_cast<ulonglong2 *>(L.dec + b * L.dec_stride + row);
-    ulonglong2 *pr = reinterpret_cast<ulonglong2 *>(L.rec + b * L.rec_stride + row);
+    const ulonglong2 *pm = row_in(L.mask, b, L.r_stride, row), *p0 = row_in(L.e0, b, L.r_stride, row), *p1 = row_in(L.e1, b, L.r_stride, row);
+    const ulonglong2 *ps = row_in(L.sk, b, L.sk_stride, row), *pc = row_in(L.c1, b, L.c1_stride, row), *pa = row_in(L.crs, b, L.crs_stride, row);
+    ulonglong2 *pd = row_out(L.dec, b, L.dec_stride, row), *pr = row_out(L.rec, b, L.rec_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
-        const ulonglong2 m = ld_stream(pm + e), a = ld_stream(pa + e), e1 = ld_stream(p1 + e);
-        const ulonglong2 s = L.sk_stride ? ld_stream(ps + e) : ps[e];          // (a key shared by the batch: through the caches)
+    LR_FOR_PAIRS(e, pairs) {
+        const ulonglong2 m = ld_stream(pm + e), a = ld_stream(pa + e), e1 = ld_stream(p1 + e), s = ld_shared(ps, L.sk_stride, e);
         if (dec) {
             const ulonglong2 c = ld_stream(pc + e), e0 = ld_stream(p0 + e);
-            st_stream(pd + e, make_ulonglong2(cred(cred(m.x + mred(s.x, c.x, q, lp.qinv), q) + e0.x, q),
-                                              cred(cred(m.y + mred(s.y, c.y, q, lp.qinv), q) + e0.y, q)));
+            st_stream(pd + e, add2(muladd2(m, s, c, q, lp.qinv), e0, q));
         }
-        st_stream(pr + e, make_ulonglong2(q - cred(cred(m.x + mred(s.x, a.x, q, lp.qinv), q) + e1.x, q),
-                                          q - cred(cred(m.y + mred(s.y, a.y, q, lp.qinv), q) + e1.y, q)));
+        st_stream(pr + e, neg2(add2(muladd2(m, s, a, q, lp.qinv), e1, q), q));
     }
 }
 
 hipError_t launch_refresh_ckks_share(const RefreshCkksShareLaunch &L, int limbs, int batch, hipStream_t stream) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || L.dec_limbs < 1 || L.dec_limbs > limbs || batch > 65535) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(refresh_ckks_share_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
-    return hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    return launch_kernel(refresh_ckks_share_kernel, pair_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // One coefficient per lane, T lanes per workgroup, the digits in LDS at [k][lane].  Digit k costs k Horner steps modulo q_k, an output row
@@ -131,17 +107,13 @@ __global__ __launch_bounds__(T) void refresh_recode_kernel(RefreshRecodeLaunch L
 }
 
 hipError_t launch_refresh_recode(const RefreshRecodeLaunch &L, int batch, hipStream_t stream) {
-    if (batch <= 0 || L.row0 >= L.limbs) return hipSuccess;
-    if (L.n < 2 || L.limbs > kMaxLimbs || L.ls < 0 || L.ls >= L.limbs || L.row0 < 0 || batch > 65535) return hipErrorInvalidValue;
-    (void)hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, batch)) return verdict_error(v);
     // 32 KiB of LDS at the most: 256 lanes up to 16 digits, 64 lanes beyond
     if (L.ls + 1 <= 16)
-        hipLaunchKernelGGL(refresh_recode_kernel<256>, dim3((unsigned)((L.n + 255) / 256), (unsigned)batch), dim3(256),
-                           (size_t)(L.ls + 1) * 256 * sizeof(u64), stream, L);
-    else
-        hipLaunchKernelGGL(refresh_recode_kernel<64>, dim3((unsigned)((L.n + 63) / 64), (unsigned)batch), dim3(64),
-                           (size_t)(L.ls + 1) * 64 * sizeof(u64), stream, L);
-    return hipGetLastError();
+        return launch_kernel(refresh_recode_kernel<256>, dim3((unsigned)((L.n + 255) / 256), (unsigned)batch), dim3(256),
+                             (size_t)(L.ls + 1) * 256 * sizeof(u64), stream, L);
+    return launch_kernel(refresh_recode_kernel<64>, dim3((unsigned)((L.n + 63) / 64), (unsigned)batch), dim3(64),
+                         (size_t)(L.ls + 1) * 64 * sizeof(u64), stream, L);
 }
 
 __global__ __launch_bounds__(256) void refresh_bfv_product_kernel(RefreshBfvProductLaunch L) {
@@ -152,28 +124,19 @@ __global__ __launch_bounds__(256) void refresh_bfv_product_kernel(RefreshBfvProd
     const long long row = (long long)limb * L.n;
     const bool inQ = limb < L.nQ;
     const u64 pm = inQ ? L.pmont.v[limb] : 0;
-    const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(L.sk + b * L.sk_stride + row);
-    ulonglong2 *pa = reinterpret_cast<ulonglong2 *>(L.a + b * L.stride + row);
-    ulonglong2 *pb = reinterpret_cast<ulonglong2 *>(L.b + b * L.stride + row);
+    const ulonglong2 *ps = row_in(L.sk, b, L.sk_stride, row);
+    ulonglong2 *pa = row_out(L.a, b, L.stride, row), *pb = row_out(L.b, b, L.stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
-        const ulonglong2 s = L.sk_stride ? ld_stream(ps + e) : ps[e];
-        if (inQ) {
-            const ulonglong2 a = ld_stream(pa + e);
-            st_stream(pa + e, make_ulonglong2(mred(mred(s.x, a.x, q, lp.qinv), pm, q, lp.qinv), mred(mred(s.y, a.y, q, lp.qinv), pm, q, lp.qinv)));
-        }
-        const ulonglong2 v = ld_stream(pb + e);
-        const u64 x = mred(s.x, v.x, q, lp.qinv), y = mred(s.y, v.y, q, lp.qinv);
-        st_stream(pb + e, make_ulonglong2(q - x, q - y));                // Neg: a zero becomes q, as in skEncryptor.encrypt
+    LR_FOR_PAIRS(e, pairs) {
+        const ulonglong2 s = ld_shared(ps, L.sk_stride, e);
+        if (inQ) st_stream(pa + e, muls2(mul2(s, ld_stream(pa + e), q, lp.qinv), pm, q, lp.qinv));
+        st_stream(pb + e, neg2(mul2(s, ld_stream(pb + e), q, lp.qinv), q));                // Neg: a zero becomes q, as in skEncryptor.encrypt
     }
 }
 
 hipError_t launch_refresh_bfv_product(const RefreshBfvProductLaunch &L, int rows, int batch, hipStream_t stream) {
-    if (rows <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || L.nQ < 1 || L.nQ > rows || batch > 65535) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(refresh_bfv_product_kernel, pair_grid(L.n, (unsigned)rows, (unsigned)batch), dim3(256), 0, stream, L);
-    return hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, rows, batch)) return verdict_error(v);
+    return launch_kernel(refresh_bfv_product_kernel, pair_grid(L.n, (unsigned)rows, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // MODE 0: dec = CRed(dec + m), rec = CRed((rec + q) - m) (Add :156, Sub :159); MODE 1: dec = CRed(m + plus) (Add :185)
@@ -184,33 +147,27 @@ __global__ __launch_bounds__(256) void refresh_bfv_lift_kernel(RefreshBfvLiftLau
     const LimbParams lp = L.lp[limb];
     const u64 q = lp.q, delta = L.delta_mont[limb];
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *pm = reinterpret_cast<const ulonglong2 *>(L.row + b * (long long)L.n);
-    ulonglong2 *pd = reinterpret_cast<ulonglong2 *>(L.dec + b * L.dec_stride + row);
-    ulonglong2 *pr = MODE == 0 ? reinterpret_cast<ulonglong2 *>(L.rec + b * L.rec_stride + row) : nullptr;
-    const ulonglong2 *pp = MODE == 1 ? reinterpret_cast<const ulonglong2 *>(L.plus + b * L.plus_stride + row) : nullptr;
+    const ulonglong2 *pm = row_in(L.row, b, L.n, 0);
+    ulonglong2 *pd = row_out(L.dec, b, L.dec_stride, row);
+    ulonglong2 *pr = MODE == 0 ? row_out(L.rec, b, L.rec_stride, row) : nullptr;
+    const ulonglong2 *pp = MODE == 1 ? row_in(L.plus, b, L.plus_stride, row) : nullptr;
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
-        const ulonglong2 v = pm[e];                              // (read once per limb: through the caches)
-        const u64 mx = mred(v.x, delta, q, lp.qinv), my = mred(v.y, delta, q, lp.qinv);
+    LR_FOR_PAIRS(e, pairs) {
+        const ulonglong2 m = muls2(pm[e], delta, q, lp.qinv);    // (the row is read once per limb: through the caches)
         if constexpr (MODE == 0) {
             const ulonglong2 d = ld_stream(pd + e), r = ld_stream(pr + e);
-            st_stream(pd + e, make_ulonglong2(cred(d.x + mx, q), cred(d.y + my, q)));
-            st_stream(pr + e, make_ulonglong2(cred((r.x + q) - mx, q), cred((r.y + q) - my, q)));
+            st_stream(pd + e, add2(d, m, q));
+            st_stream(pr + e, sub2(r, m, q));
         } else {
-            const ulonglong2 p = ld_stream(pp + e);
-            st_stream(pd + e, make_ulonglong2(cred(mx + p.x, q), cred(my + p.y, q)));
+            st_stream(pd + e, add2(m, ld_stream(pp + e), q));
         }
     }
 }
 
 hipError_t launch_refresh_bfv_lift(const RefreshBfvLiftLaunch &L, int limbs, int batch, hipStream_t stream) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535 || !L.dec || (L.plus == nullptr) == (L.rec == nullptr)) return hipErrorInvalidValue;
-    (void)hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     const dim3 grid = pair_grid(L.n, (unsigned)limbs, (unsigned)batch);
-    if (L.rec) hipLaunchKernelGGL(refresh_bfv_lift_kernel<0>, grid, dim3(256), 0, stream, L);
-    else hipLaunchKernelGGL(refresh_bfv_lift_kernel<1>, grid, dim3(256), 0, stream, L);
-    return hipGetLastError();
+    return L.rec ? launch_kernel(refresh_bfv_lift_kernel<0>, grid, dim3(256), 0, stream, L) : launch_kernel(refresh_bfv_lift_kernel<1>, grid, dim3(256), 0, stream, L);
 }
 
 }  // namespace lr

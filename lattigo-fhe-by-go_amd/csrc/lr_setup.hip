@@ -1,42 +1,11 @@
 // lr_setup.hip -- the kernels of collective key setup (lr_setup.cpp): what CKGProtocol.GenShare (dbfv/publickey_gen.go:54-57), the three
 // rounds of RKGProtocol (dbfv/relinkey_gen.go:215-355), the two of RKGProtocolNaive (dbfv/relinkey_gen_naive.go:59-200) and
 // RTGProtocol.genShare / Finalize (dbfv/rotkey_gen.go:139-215) do behind the forward transform of their samples; the dckks twins compute
-// the same lines.  Streaming kernels in the manner of lr_keygen.hip: 16 B per lane per access to poly data, two coefficients per lane,
-// limb on blockIdx.y (per-modulus constants wave-uniform), party x digit on blockIdx.z, a grid-stride loop over coefficient pairs.  The
-// noise and the ternary polys are expanded by launch_ckks_expand; AggregateShare* is launch_fold.
-#include "lr_device.hpp"
+// the same lines.  Streaming passes (lr_stream.hpp), party x digit on blockIdx.z.  The noise and the ternary polys are expanded by
+// launch_ckks_expand; AggregateShare* is launch_fold.
+#include "lr_stream.hpp"
 
 namespace lr {
-
-namespace {
-
-dim3 pair_grid(int n, unsigned y, unsigned z) {
-    int gx = ((n >> 1) + 255) / 256;
-    if (gx > 64) gx = 64;
-    if (gx < 1) gx = 1;
-    return dim3((unsigned)gx, y, z);
-}
-
-// ring.PermuteNTTIndex (ring/ring_galois.go:29-52) for one position, as keygen_skin_kernel computes it
-LR_D u32 galois_index(u32 j, u32 gen, u32 mask2, int logn) {
-    const u32 t1 = 2 * (__brev(j) >> (32 - logn)) + 1;
-    const u32 t2 = (((gen * t1) & mask2) - 1) >> 1;
-    return __brev(t2) >> (32 - logn);
-}
-
-LR_D ulonglong2 add2(ulonglong2 a, ulonglong2 b, u64 q) { return make_ulonglong2(cred(a.x + b.x, q), cred(a.y + b.y, q)); }
-LR_D ulonglong2 mul2(ulonglong2 a, ulonglong2 b, u64 q, u64 qinv) { return make_ulonglong2(mred(a.x, b.x, q, qinv), mred(a.y, b.y, q, qinv)); }
-// CRed(x + (q - MRed(a, b))): MulCoeffsMontgomeryAndSub (ring/ring.go:311)
-LR_D ulonglong2 mulsub2(ulonglong2 x, ulonglong2 a, ulonglong2 b, u64 q, u64 qinv) {
-    return make_ulonglong2(cred(x.x + (q - mred(a.x, b.x, q, qinv)), q), cred(x.y + (q - mred(a.y, b.y, q, qinv)), q));
-}
-LR_D ulonglong2 mform2(ulonglong2 a, const LimbParams &lp) {
-    return make_ulonglong2(mform(a.x, lp.q, lp.bred_hi, lp.bred_lo), mform(a.y, lp.q, lp.bred_hi, lp.bred_lo));
-}
-// InvMForm(MulScalarBigint(s, P)) (dbfv/relinkey_gen.go:225-227): MRed by MForm(P mod q), then out of Montgomery form
-LR_D u64 times_p(u64 s, u64 pm, u64 q, u64 qinv) { return inv_mform(mred(s, pm, q, qinv), q, qinv); }
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void setup_ckg_kernel(SetupCkgLaunch L) {
     const int limb = blockIdx.y;
@@ -44,24 +13,18 @@ __global__ __launch_bounds__(256) void setup_ckg_kernel(SetupCkgLaunch L) {
     const LimbParams lp = L.lp[limb];
     const u64 q = lp.q;
     const long long row = (long long)limb * L.n;
-    const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(L.sk + b * L.sk_stride + row);
-    const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(L.crs + b * L.crs_stride + row);
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(L.share + b * L.share_stride + row);
+    const ulonglong2 *ps = row_in(L.sk, b, L.sk_stride, row), *pa = row_in(L.crs, b, L.crs_stride, row);
+    ulonglong2 *po = row_out(L.share, b, L.share_stride, row);
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
-        const ulonglong2 v = ld_stream(po + e);
-        const ulonglong2 s = L.sk_stride ? ld_stream(ps + e) : ps[e];      // (a poly shared by the parties: through the caches)
-        const ulonglong2 a = L.crs_stride ? ld_stream(pa + e) : pa[e];
+    LR_FOR_PAIRS(e, pairs) {
+        const ulonglong2 v = ld_stream(po + e), s = ld_shared(ps, L.sk_stride, e), a = ld_shared(pa, L.crs_stride, e);
         st_stream(po + e, mulsub2(v, s, a, q, lp.qinv));
     }
 }
 
 hipError_t launch_setup_ckg(const SetupCkgLaunch &L, int rows, int batch, hipStream_t stream) {
-    if (rows <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(setup_ckg_kernel, pair_grid(L.n, (unsigned)rows, (unsigned)batch), dim3(256), 0, stream, L);
-    return hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, rows, batch)) return verdict_error(v);
+    return launch_kernel(setup_ckg_kernel, pair_grid(L.n, (unsigned)rows, (unsigned)batch), dim3(256), 0, stream, L);
 }
 
 // One share kernel per protocol step, z = party * beta + digit, what follows the transform in one pass:
@@ -86,36 +49,33 @@ __global__ __launch_bounds__(256) void setup_share_kernel(SetupShareLaunch L) {
     const bool own = limb >= digit * L.alpha && limb < (digit + 1) * L.alpha && limb < L.nQ;     // the digit loop with its break
     const u64 pm = own ? L.pmont.v[limb] : 0;
     const KeygenKeyRef ref = L.out[k];
-    const ulonglong2 *pe = reinterpret_cast<const ulonglong2 *>(L.e + z * PER * L.e_stride + row);
-    const ulonglong2 *pe1 = reinterpret_cast<const ulonglong2 *>(L.e + (z * PER + 1) * L.e_stride + row);
+    const ulonglong2 *pe = row_in(L.e, z * PER, L.e_stride, row), *pe1 = row_in(L.e, z * PER + 1, L.e_stride, row);
     const u64 *sk = L.sk + (KIND == kSetupRtg ? 0 : (long long)k * L.sk_stride) + row;
     const ulonglong2 *ps = reinterpret_cast<const ulonglong2 *>(sk);
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(ref.base + (long long)(PER * digit) * ref.stride + row);
-    ulonglong2 *po1 = reinterpret_cast<ulonglong2 *>(ref.base + (long long)(PER * digit + 1) * ref.stride + row);
+    ulonglong2 *po = row_out(ref.base, PER * digit, ref.stride, row), *po1 = row_out(ref.base, PER * digit + 1, ref.stride, row);
     const ulonglong2 *pu = nullptr, *pa = nullptr, *pin = nullptr, *pin1 = nullptr, *pt = nullptr, *pk0 = nullptr, *pk1 = nullptr;
-    if constexpr (KIND == kSetupRkg1 || KIND == kSetupRkg3) pu = reinterpret_cast<const ulonglong2 *>(L.u + (long long)k * L.u_stride + row);
-    if constexpr (KIND == kSetupRkg1 || KIND == kSetupRkg2 || KIND == kSetupRtg)
-        pa = reinterpret_cast<const ulonglong2 *>(L.crp + (long long)digit * L.crp_stride + row);
-    if constexpr (KIND == kSetupRkg2) pin = reinterpret_cast<const ulonglong2 *>(L.in + (long long)digit * L.in_stride + row);
-    if constexpr (KIND == kSetupRkg3) pin = reinterpret_cast<const ulonglong2 *>(L.in + (long long)(2 * digit + 1) * L.in_stride + row);
+    if constexpr (KIND == kSetupRkg1 || KIND == kSetupRkg3) pu = row_in(L.u, k, L.u_stride, row);
+    if constexpr (KIND == kSetupRkg1 || KIND == kSetupRkg2 || KIND == kSetupRtg) pa = row_in(L.crp, digit, L.crp_stride, row);
+    if constexpr (KIND == kSetupRkg2) pin = row_in(L.in, digit, L.in_stride, row);
+    if constexpr (KIND == kSetupRkg3) pin = row_in(L.in, 2 * digit + 1, L.in_stride, row);
     if constexpr (KIND == kSetupNaive2) {
-        pin = reinterpret_cast<const ulonglong2 *>(L.in + (long long)(2 * digit) * L.in_stride + row);
-        pin1 = reinterpret_cast<const ulonglong2 *>(L.in + (long long)(2 * digit + 1) * L.in_stride + row);
+        pin = row_in(L.in, 2 * digit, L.in_stride, row);
+        pin1 = row_in(L.in, 2 * digit + 1, L.in_stride, row);
     }
     if constexpr (KIND == kSetupNaive1 || KIND == kSetupNaive2) {
-        pt = reinterpret_cast<const ulonglong2 *>(L.t + z * L.t_stride + row);
-        pk0 = reinterpret_cast<const ulonglong2 *>(L.pk0 + row);
-        pk1 = reinterpret_cast<const ulonglong2 *>(L.pk1 + row);
+        pt = row_in(L.t, z, L.t_stride, row);
+        pk0 = row_in(L.pk0, 0, 0, row);
+        pk1 = row_in(L.pk1, 0, 0, row);
     }
     const u32 gen = KIND == kSetupRtg ? L.gen[k] : 1u, mask2 = 2u * (u32)L.n - 1u;
     const int pairs = L.n >> 1, logn = L.logn;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         ulonglong2 x = ld_stream(pe + e);
         if constexpr (KIND == kSetupRkg1) {
             const ulonglong2 u = pu[e], a = pa[e];                            // (shared by the digits or the parties: through the caches)
             if (own) {
                 const ulonglong2 s = ps[e];
-                x = add2(x, make_ulonglong2(times_p(s.x, pm, q, qinv), times_p(s.y, pm, q, qinv)), q);
+                x = add2(x, times_p2(s.x, s.y, pm, q, qinv), q);
             }
             st_stream(po + e, mulsub2(x, u, a, q, qinv));
         } else if constexpr (KIND == kSetupRkg2) {
@@ -124,14 +84,13 @@ __global__ __launch_bounds__(256) void setup_share_kernel(SetupShareLaunch L) {
             st_stream(po1 + e, add2(e2, mul2(s, a, q, qinv), q));
         } else if constexpr (KIND == kSetupRkg3) {
             const ulonglong2 s = ps[e], u = pu[e], r = pin[e];
-            const ulonglong2 d = make_ulonglong2(cred((u.x + q) - s.x, q), cred((u.y + q) - s.y, q));
-            st_stream(po + e, add2(x, mul2(d, r, q, qinv), q));
+            st_stream(po + e, add2(x, mul2(sub2(u, s, q), r, q, qinv), q));
         } else if constexpr (KIND == kSetupNaive1) {
             const ulonglong2 t = ld_stream(pt + e), e1 = ld_stream(pe1 + e), p0 = pk0[e], p1 = pk1[e];
             ulonglong2 x0 = L.quirk ? e1 : x;
             if (own) {
                 const ulonglong2 s = ps[e];
-                x0 = add2(x0, make_ulonglong2(times_p(s.x, pm, q, qinv), times_p(s.y, pm, q, qinv)), q);
+                x0 = add2(x0, times_p2(s.x, s.y, pm, q, qinv), q);
             }
             st_stream(po + e, add2(x0, mul2(p0, t, q, qinv), q));
             st_stream(po1 + e, add2(L.quirk ? make_ulonglong2(0, 0) : e1, mul2(p1, t, q, qinv), q));
@@ -143,7 +102,7 @@ __global__ __launch_bounds__(256) void setup_share_kernel(SetupShareLaunch L) {
             const ulonglong2 s = ps[e], a = pa[e];
             if (own) {
                 const u64 g0 = sk[galois_index(2u * (u32)e, gen, mask2, logn)], g1 = sk[galois_index(2u * (u32)e + 1u, gen, mask2, logn)];
-                x = add2(x, make_ulonglong2(times_p(g0, pm, q, qinv), times_p(g1, pm, q, qinv)), q);
+                x = add2(x, times_p2(g0, g1, pm, q, qinv), q);
             }
             st_stream(po + e, mform2(mulsub2(x, a, s, q, qinv), lp));
         }
@@ -151,22 +110,17 @@ __global__ __launch_bounds__(256) void setup_share_kernel(SetupShareLaunch L) {
 }
 
 hipError_t launch_setup_share(int kind, const SetupShareLaunch &L, int rows, int parties, hipStream_t stream) {
-    if (rows <= 0 || parties <= 0) return hipSuccess;
-    if (L.n < 2 || L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || rows > kMaxLimbs || parties > kSetupPartiesPerLaunch || L.beta < 1 ||
-        L.beta > kMaxLimbs || L.alpha < 1 || L.nQ < 1 || L.nQ > rows)
-        return hipErrorInvalidValue;
-    (void)hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, rows, parties)) return verdict_error(v);
     const dim3 grid = pair_grid(L.n, (unsigned)rows, (unsigned)(parties * L.beta));
     switch (kind) {
-        case kSetupRkg1: hipLaunchKernelGGL(setup_share_kernel<kSetupRkg1>, grid, dim3(256), 0, stream, L); break;
-        case kSetupRkg2: hipLaunchKernelGGL(setup_share_kernel<kSetupRkg2>, grid, dim3(256), 0, stream, L); break;
-        case kSetupRkg3: hipLaunchKernelGGL(setup_share_kernel<kSetupRkg3>, grid, dim3(256), 0, stream, L); break;
-        case kSetupNaive1: hipLaunchKernelGGL(setup_share_kernel<kSetupNaive1>, grid, dim3(256), 0, stream, L); break;
-        case kSetupNaive2: hipLaunchKernelGGL(setup_share_kernel<kSetupNaive2>, grid, dim3(256), 0, stream, L); break;
-        case kSetupRtg: hipLaunchKernelGGL(setup_share_kernel<kSetupRtg>, grid, dim3(256), 0, stream, L); break;
+        case kSetupRkg1: return launch_kernel(setup_share_kernel<kSetupRkg1>, grid, dim3(256), 0, stream, L);
+        case kSetupRkg2: return launch_kernel(setup_share_kernel<kSetupRkg2>, grid, dim3(256), 0, stream, L);
+        case kSetupRkg3: return launch_kernel(setup_share_kernel<kSetupRkg3>, grid, dim3(256), 0, stream, L);
+        case kSetupNaive1: return launch_kernel(setup_share_kernel<kSetupNaive1>, grid, dim3(256), 0, stream, L);
+        case kSetupNaive2: return launch_kernel(setup_share_kernel<kSetupNaive2>, grid, dim3(256), 0, stream, L);
+        case kSetupRtg: return launch_kernel(setup_share_kernel<kSetupRtg>, grid, dim3(256), 0, stream, L);
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 __global__ __launch_bounds__(256) void setup_key_kernel(SetupKeyLaunch L) {
@@ -174,14 +128,13 @@ __global__ __launch_bounds__(256) void setup_key_kernel(SetupKeyLaunch L) {
     const long long i = blockIdx.z;
     const LimbParams lp = L.lp[limb];
     const long long row = (long long)limb * L.n;
-    ulonglong2 *po0 = reinterpret_cast<ulonglong2 *>(L.key + 2 * i * L.key_stride + row);
-    ulonglong2 *po1 = reinterpret_cast<ulonglong2 *>(L.key + (2 * i + 1) * L.key_stride + row);
-    const ulonglong2 *pp0 = L.pairs ? reinterpret_cast<const ulonglong2 *>(L.pairs + 2 * i * L.pairs_stride + row) : nullptr;
-    const ulonglong2 *pp1 = L.pairs ? reinterpret_cast<const ulonglong2 *>(L.pairs + (2 * i + 1) * L.pairs_stride + row) : nullptr;
-    const ulonglong2 *pv = L.polys ? reinterpret_cast<const ulonglong2 *>(L.polys + i * L.polys_stride + row) : nullptr;
-    const ulonglong2 *pa = L.crp ? reinterpret_cast<const ulonglong2 *>(L.crp + i * L.crp_stride + row) : nullptr;
+    ulonglong2 *po0 = row_out(L.key, 2 * i, L.key_stride, row), *po1 = row_out(L.key, 2 * i + 1, L.key_stride, row);
+    const ulonglong2 *pp0 = L.pairs ? row_in(L.pairs, 2 * i, L.pairs_stride, row) : nullptr;
+    const ulonglong2 *pp1 = L.pairs ? row_in(L.pairs, 2 * i + 1, L.pairs_stride, row) : nullptr;
+    const ulonglong2 *pv = L.polys ? row_in(L.polys, i, L.polys_stride, row) : nullptr;
+    const ulonglong2 *pa = L.crp ? row_in(L.crp, i, L.crp_stride, row) : nullptr;
     const int pairs = L.n >> 1;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+    LR_FOR_PAIRS(e, pairs) {
         if (pp0) {
             ulonglong2 x = ld_stream(pp0 + e);
             const ulonglong2 y = ld_stream(pp1 + e);
@@ -196,11 +149,8 @@ __global__ __launch_bounds__(256) void setup_key_kernel(SetupKeyLaunch L) {
 }
 
 hipError_t launch_setup_key(const SetupKeyLaunch &L, int rows, int beta, hipStream_t stream) {
-    if (rows <= 0 || beta <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || beta > kMaxLimbs || (!L.pairs && (!L.polys || !L.crp))) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(setup_key_kernel, pair_grid(L.n, (unsigned)rows, (unsigned)beta), dim3(256), 0, stream, L);
-    return hipGetLastError();
+    if (const LaunchVerdict v = launch_verdict(L, rows, beta)) return verdict_error(v);
+    return launch_kernel(setup_key_kernel, pair_grid(L.n, (unsigned)rows, (unsigned)beta), dim3(256), 0, stream, L);
 }
 
 }  // namespace lr

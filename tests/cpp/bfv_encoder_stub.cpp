@@ -6,24 +6,13 @@
 #include <atomic>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
 std::atomic<unsigned long long> g_encoder_stub_launches{0};
 std::atomic<unsigned long long> g_encoder_stub_fused{0};
 namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-void wr(u64 *p, long long count) {
-    if (count <= 0) return;
-    p[0] = p[0];
-    p[count - 1] = p[count - 1];
-}
 void tables(const EncoderTables &tab) { rd(tab.index, tab.n); }
 void values_r(const void *values, long long n_values, int batch) {
     for (int b = 0; b < batch; ++b) rd((const u64 *)values + (long long)b * n_values, n_values);

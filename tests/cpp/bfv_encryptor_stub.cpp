@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
@@ -23,18 +24,6 @@ struct EncryptorStubEvent {
 thread_local std::vector<EncryptorStubEvent> t_encryptor_stub_events;     // per thread: two handles on two threads record apart
 
 namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-void wr(u64 *p, long long count) {
-    if (count <= 0) return;
-    p[0] = p[0];
-    p[count - 1] = p[count - 1];
-}
 void record(const char *name, int limbs, int batch) {
     g_encryptor_stub_launches.fetch_add(1);
     t_encryptor_stub_events.push_back(EncryptorStubEvent{name, g_stub_launches.load(), limbs, batch});
@@ -50,8 +39,7 @@ int encryptor_stub_limbs(int i) { return t_encryptor_stub_events[(size_t)i].limb
 int encryptor_stub_batch(int i) { return t_encryptor_stub_events[(size_t)i].batch; }
 
 hipError_t launch_bfv_ternary(const TernaryLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 8 || limbs > kMaxLimbs) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     record("ternary", limbs, batch);
     for (int b = 0; b < batch; ++b) {
         rd(L.coeff_bits + (long long)b * (L.n >> 3), L.n >> 3);
@@ -62,8 +50,7 @@ hipError_t launch_bfv_ternary(const TernaryLaunch &L, int limbs, int batch, hipS
 }
 
 hipError_t launch_bfv_noise(const NoiseLaunch &L, int comps, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0 || comps <= 0) return hipSuccess;
-    if (comps > 2 || L.n < 2) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, comps, limbs, batch)) return verdict_error(v);
     record(L.add ? (comps == 2 ? "noise_add2" : "noise_add") : "noise_expand", limbs, batch);
     rd(L.lp, limbs);
     for (int k = 0; k < comps; ++k)
@@ -79,7 +66,7 @@ hipError_t launch_bfv_noise(const NoiseLaunch &L, int comps, int limbs, int batc
 }
 
 hipError_t launch_bfv_negmul(const NegMulLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     record("negmul", limbs, batch);
     rd(L.lp, limbs);
     for (int b = 0; b < batch; ++b)

@@ -6,6 +6,7 @@
 #include <atomic>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
@@ -13,20 +14,6 @@ std::atomic<unsigned long long> g_ckks_stub_launches{0};
 std::atomic<unsigned long long> g_ckks_stub_fused{0};      // fused Encode launches: only the fused route makes them
 std::atomic<unsigned long long> g_ckks_stub_stages{0};     // streaming stages: only the tiled route makes them
 namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-template <class T>
-void wr(T *p, long long count) {
-    if (count <= 0) return;
-    volatile unsigned char *b = (volatile unsigned char *)p, *e = (volatile unsigned char *)(p + count) - 1;
-    *b = *b;
-    *e = *e;
-}
 void tables(const CkksEncTables &tab) {
     rd(tab.roots, 2ll * tab.n + 1);
     rd(tab.rot, tab.n / 2);

@@ -6,31 +6,16 @@
 #include <atomic>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
 extern std::atomic<unsigned long long> g_encryptor_stub_launches;      // bfv_encryptor_stub.cpp
 std::atomic<unsigned long long> g_ckks_expand_launches{0}, g_ckks_fast_launches{0};
 
-namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-void wr(u64 *p, long long count) {
-    if (count <= 0) return;
-    p[0] = p[0];
-    p[count - 1] = p[count - 1];
-}
-}  // namespace
-
 hipError_t launch_ckks_expand(const CkksExpandLaunch &L, int limbs, int batch, hipStream_t) {
     const int parts = L.ternary + L.noises;
-    if (limbs <= 0 || batch <= 0 || parts <= 0) return hipSuccess;
-    if (L.n < 8 || limbs > kMaxLimbs || L.ternary < 0 || L.ternary > 1 || L.noises < 0 || L.noises > 2 || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_encryptor_stub_launches.fetch_add(1);
     g_ckks_expand_launches.fetch_add(1);
     rd(L.lp, limbs);
@@ -47,8 +32,7 @@ hipError_t launch_ckks_expand(const CkksExpandLaunch &L, int limbs, int batch, h
 }
 
 hipError_t launch_ckks_pk_fast(const CkksPkFastLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_encryptor_stub_launches.fetch_add(1);
     g_ckks_fast_launches.fetch_add(1);
     rd(L.lp, limbs);
@@ -68,8 +52,7 @@ hipError_t launch_ckks_pk_fast(const CkksPkFastLaunch &L, int limbs, int batch, 
 }
 
 hipError_t launch_ckks_sk_fast(const CkksSkFastLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_encryptor_stub_launches.fetch_add(1);
     g_ckks_fast_launches.fetch_add(1);
     rd(L.lp, limbs);

@@ -7,29 +7,14 @@
 #include <atomic>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
 std::atomic<unsigned long long> g_cks_share_launches{0}, g_pcks_addend_launches{0}, g_fold_launches{0};
 
-namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-void wr(u64 *p, long long count) {
-    if (count <= 0) return;
-    p[0] = p[0];
-    p[count - 1] = p[count - 1];
-}
-}  // namespace
-
 hipError_t launch_cks_share(const CksShareLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_cks_share_launches.fetch_add(1);
     rd(L.lp, limbs);
     for (int b = 0; b < batch; ++b)
@@ -45,8 +30,7 @@ hipError_t launch_cks_share(const CksShareLaunch &L, int limbs, int batch, hipSt
 }
 
 hipError_t launch_pcks_addend(const PcksAddendLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_pcks_addend_launches.fetch_add(1);
     rd(L.lp, limbs);
     for (int b = 0; b < batch; ++b)
@@ -60,8 +44,7 @@ hipError_t launch_pcks_addend(const PcksAddendLaunch &L, int limbs, int batch, h
 }
 
 hipError_t launch_fold(const FoldLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535 || L.count < 1 || L.count > kFoldSharesPerLaunch) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_fold_launches.fetch_add(1);
     rd(L.lp, limbs);
     for (int b = 0; b < batch; ++b)

@@ -16,6 +16,7 @@
 
 #include "lattigo_ring.h"
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
@@ -26,8 +27,6 @@ std::atomic<unsigned long long> g_stub_launches{0};
 thread_local int g_stub_last_ext[5] = {-1, -1, -1, -1, -1};
 thread_local int g_stub_last_keymac_wide[2] = {-1, -1};
 namespace {
-thread_local volatile u64 t_sink;          // (per thread: the reads are the point, not the sink)
-inline void rd(const u64 *p) { t_sink = *p; }
 inline void rows_r(const u64 *base, long long poly_stride, long long row0, long long row_step, int rows, int batch, long long n) {
     if (!base) return;
     for (int b = 0; b < batch; ++b)
@@ -153,8 +152,7 @@ hipError_t launch_tensor(const TensorLaunch &L, int limbs, int batch, hipStream_
 }
 // refuses what the real launcher refuses: the host code never sends 1 x 1 here (that is launch_tensor)
 hipError_t launch_tensor_deg(const TensorDegLaunch &L, int d0, int d1, bool square, int limbs, int batch, hipStream_t) {
-    if (d0 < 0 || d1 < 0 || d0 + d1 < 1 || d0 + d1 > kTensorMaxDegree || (d0 == 1 && d1 == 1)) return hipErrorInvalidValue;
-    if (square && !(d0 == 2 && d1 == 2)) return hipErrorInvalidValue;
+    if (launch_verdict(L, d0, d1, square, limbs, batch) == kLaunchRefuse) return hipErrorInvalidValue;
     for (int k = 0; k <= d0 + d1; ++k)          // (rows_r / rows_w skip a null base: an unset slot is an error here)
         if ((k <= d0 && !L.a[k]) || (!square && k <= d1 && !L.b[k]) || !L.c[k]) return hipErrorInvalidValue;
     g_stub_launches.fetch_add(1);

@@ -6,29 +6,14 @@
 #include <atomic>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
 std::atomic<unsigned long long> g_keygen_skin_launches{0}, g_keygen_finish_launches{0}, g_keygen_pk_launches{0};
 
-namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-void wr(u64 *p, long long count) {
-    if (count <= 0) return;
-    p[0] = p[0];
-    p[count - 1] = p[count - 1];
-}
-}  // namespace
-
 hipError_t launch_keygen_skin(const KeygenSkInLaunch &L, int limbs, int keys, hipStream_t) {
-    if (limbs <= 0 || keys <= 0) return hipSuccess;
-    if (L.n < 2 || L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || limbs > kMaxLimbs || keys > kKeygenKeysPerLaunch) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, keys)) return verdict_error(v);
     g_keygen_skin_launches.fetch_add(1);
     rd(L.lp, limbs);
     for (int k = 0; k < keys; ++k) {
@@ -42,8 +27,7 @@ hipError_t launch_keygen_skin(const KeygenSkInLaunch &L, int limbs, int keys, hi
 }
 
 hipError_t launch_keygen_powers(const KeygenPowersLaunch &L, int limbs, hipStream_t) {
-    if (limbs <= 0 || L.keys <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || L.first < 0) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs)) return verdict_error(v);
     g_keygen_skin_launches.fetch_add(1);
     rd(L.lp, limbs);
     for (int i = 0; i < limbs; ++i) {
@@ -54,9 +38,7 @@ hipError_t launch_keygen_powers(const KeygenPowersLaunch &L, int limbs, hipStrea
 }
 
 hipError_t launch_keygen_finish(const KeygenFinishLaunch &L, int rows, int keys, hipStream_t) {
-    if (rows <= 0 || keys <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || keys > kKeygenKeysPerLaunch || L.beta < 1 || L.beta > kMaxLimbs || L.alpha < 1 || L.nQ < 1 || L.nQ > rows)
-        return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, rows, keys)) return verdict_error(v);
     g_keygen_finish_launches.fetch_add(1);
     rd(L.lp, rows);
     for (int k = 0; k < keys; ++k)
@@ -73,8 +55,7 @@ hipError_t launch_keygen_finish(const KeygenFinishLaunch &L, int rows, int keys,
 }
 
 hipError_t launch_keygen_pk(const KeygenPkLaunch &L, int rows, int batch, hipStream_t) {
-    if (rows <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, rows, batch)) return verdict_error(v);
     g_keygen_pk_launches.fetch_add(1);
     rd(L.lp, rows);
     for (int b = 0; b < batch; ++b)

@@ -7,30 +7,15 @@
 #include <atomic>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
 std::atomic<unsigned long long> g_refresh_mask_launches{0}, g_refresh_share_launches{0}, g_refresh_recode_launches{0}, g_refresh_product_launches{0},
     g_refresh_lift_launches{0};
 
-namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-void wr(u64 *p, long long count) {
-    if (count <= 0) return;
-    p[0] = p[0];
-    p[count - 1] = p[count - 1];
-}
-}  // namespace
-
 hipError_t launch_refresh_mask(const RefreshMaskLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || L.words < 1 || L.words > kCkksCrtMaxWords || limbs > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_refresh_mask_launches.fetch_add(1);
     rd(L.lp, limbs);
     rd(L.mask, (long long)batch * L.words * L.n);
@@ -40,8 +25,7 @@ hipError_t launch_refresh_mask(const RefreshMaskLaunch &L, int limbs, int batch,
 }
 
 hipError_t launch_refresh_ckks_share(const RefreshCkksShareLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || L.dec_limbs < 1 || L.dec_limbs > limbs || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_refresh_share_launches.fetch_add(1);
     rd(L.lp, limbs);
     for (int b = 0; b < batch; ++b)
@@ -62,8 +46,7 @@ hipError_t launch_refresh_ckks_share(const RefreshCkksShareLaunch &L, int limbs,
 }
 
 hipError_t launch_refresh_recode(const RefreshRecodeLaunch &L, int batch, hipStream_t) {
-    if (batch <= 0 || L.row0 >= L.limbs) return hipSuccess;
-    if (L.n < 2 || L.limbs > kMaxLimbs || L.ls < 0 || L.ls >= L.limbs || L.row0 < 0 || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, batch)) return verdict_error(v);
     g_refresh_recode_launches.fetch_add(1);
     rd(L.lp, L.limbs);
     rd(L.qmod, (long long)L.limbs * L.limbs);
@@ -78,8 +61,7 @@ hipError_t launch_refresh_recode(const RefreshRecodeLaunch &L, int batch, hipStr
 }
 
 hipError_t launch_refresh_bfv_product(const RefreshBfvProductLaunch &L, int rows, int batch, hipStream_t) {
-    if (rows <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || L.nQ < 1 || L.nQ > rows || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, rows, batch)) return verdict_error(v);
     g_refresh_product_launches.fetch_add(1);
     rd(L.lp, rows);
     for (int b = 0; b < batch; ++b)
@@ -93,8 +75,7 @@ hipError_t launch_refresh_bfv_product(const RefreshBfvProductLaunch &L, int rows
 }
 
 hipError_t launch_refresh_bfv_lift(const RefreshBfvLiftLaunch &L, int limbs, int batch, hipStream_t) {
-    if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || limbs > kMaxLimbs || batch > 65535 || !L.dec || (L.plus == nullptr) == (L.rec == nullptr)) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
     g_refresh_lift_launches.fetch_add(1);
     rd(L.lp, limbs);
     rd(L.delta_mont, limbs);

@@ -7,29 +7,14 @@
 #include <atomic>
 
 #include "lr_device.hpp"
+#include "stub_touch.hpp"
 
 namespace lr {
 
 std::atomic<unsigned long long> g_setup_ckg_launches{0}, g_setup_share_launches{0}, g_setup_key_launches{0};
 
-namespace {
-thread_local volatile u64 t_sink;
-template <class T>
-void rd(const T *p, long long count) {
-    if (count <= 0) return;
-    t_sink = (u64)((const volatile unsigned char *)p)[0];
-    t_sink = (u64)((const volatile unsigned char *)(p + count))[-1];
-}
-void wr(u64 *p, long long count) {
-    if (count <= 0) return;
-    p[0] = p[0];
-    p[count - 1] = p[count - 1];
-}
-}  // namespace
-
 hipError_t launch_setup_ckg(const SetupCkgLaunch &L, int rows, int batch, hipStream_t) {
-    if (rows <= 0 || batch <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || batch > 65535) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, rows, batch)) return verdict_error(v);
     g_setup_ckg_launches.fetch_add(1);
     rd(L.lp, rows);
     for (int b = 0; b < batch; ++b)
@@ -43,10 +28,8 @@ hipError_t launch_setup_ckg(const SetupCkgLaunch &L, int rows, int batch, hipStr
 }
 
 hipError_t launch_setup_share(int kind, const SetupShareLaunch &L, int rows, int parties, hipStream_t) {
-    if (rows <= 0 || parties <= 0) return hipSuccess;
-    if (L.n < 2 || L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || rows > kMaxLimbs || parties > kSetupPartiesPerLaunch || L.beta < 1 ||
-        L.beta > kMaxLimbs || L.alpha < 1 || L.nQ < 1 || L.nQ > rows || kind < kSetupRkg1 || kind > kSetupRtg)
-        return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, rows, parties)) return verdict_error(v);
+    if (kind < kSetupRkg1 || kind > kSetupRtg) return hipErrorInvalidValue;
     g_setup_share_launches.fetch_add(1);
     rd(L.lp, rows);
     const bool pairs = kind == kSetupRkg2 || kind == kSetupNaive1 || kind == kSetupNaive2;
@@ -77,8 +60,7 @@ hipError_t launch_setup_share(int kind, const SetupShareLaunch &L, int rows, int
 }
 
 hipError_t launch_setup_key(const SetupKeyLaunch &L, int rows, int beta, hipStream_t) {
-    if (rows <= 0 || beta <= 0) return hipSuccess;
-    if (L.n < 2 || rows > kMaxLimbs || beta > kMaxLimbs || (!L.pairs && (!L.polys || !L.crp))) return hipErrorInvalidValue;
+    if (const LaunchVerdict v = launch_verdict(L, rows, beta)) return verdict_error(v);
     g_setup_key_launches.fetch_add(1);
     rd(L.lp, rows);
     for (int d = 0; d < beta; ++d)

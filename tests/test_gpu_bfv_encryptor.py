@@ -5,6 +5,8 @@ call-by-call shape), batches 1 and 3, keys and plaintext shared by the batch or 
   PN12QP109  N = 2^12, 2 + 1 limbs
   PN13QP218  N = 2^13, 3 + 1 limbs
   PN14QP438  its moduli at N = 2^11, 6 + 2 limbs: the one shape with |P| = 2
+  n65536     N = 2^16, 2 + 1 limbs of CKKS PN16QP1761, batch 2 with shared keys: one pk and one sk encryption, fast, in both shapes -- the
+             one degree at which a lane of the streaming kernels makes a second trip of its loop
 The randomness carries every edge decision at fixed positions: the four ternary (coeff, sign) pairs, a bit plane of all ones, the noise
 bytes (0, sign 0) -- the residue q -- (0, sign 1), (19, +-), (127, +-).  Decrypt: degrees 0, 1, 2, 7, 8 (the reduction cadence) and 9
 (above the one-pass kernel's limit), pt_out aliasing the top component, a key over Q||P, components back to back in memory.  One chain
@@ -137,6 +139,42 @@ def test_encrypt_against_the_restatement(gpu_pkg, oracle, name, batch, shared):
                     assert np.array_equal(got[1][b], want[1]), where
         assert np.array_equal(crp.get().reshape(batch, nQ + nP, N), c["crp"][:batch])      # the uniform poly is never modified
         del keep
+
+
+def test_one_pk_and_one_sk_encryption_at_n65536(gpu_pkg, oracle):
+    """two trips of the streaming loops: the ternary expansion, the two products with the public key, the noise added with the plaintext
+    (one pass) and expanded alone (call by call), and the negated product with the secret key; the keys and the plaintext shared by a batch of 2"""
+    ring = gpu_pkg.ring
+    N, Q, P = gpu_pkg.params.ckks_moduli("PN16QP1761")
+    Q, P, batch = list(Q[:2]), list(P[:1]), 2
+    nQ, rng = len(Q), np.random.default_rng(65536)
+    sk, pk0, pk1 = (k[None] for k in ref.keygen(oracle, N, Q + P, rng)[:3])
+    uni = lambda moduli, n: np.stack([np.array([rng.integers(0, q, N, dtype=np.uint64) for q in moduli], dtype=np.uint64) for _ in range(n)])
+    crp, pt = uni(Q + P, batch), uni(Q, 1)
+    bits = lambda: rng.integers(0, 256, (batch, N >> 3)).astype(np.uint8)
+    noise = lambda: (rng.integers(0, 20, (batch, N)) | (rng.integers(0, 2, (batch, N)) << 7)).astype(np.uint8)
+    uc, us, e0, e1, e = bits(), bits(), noise(), noise(), noise()
+    for a in (e0, e1, e):
+        a[0, :6] = [0, 0x80, 19, 19 | 0x80, 127, 127 | 0x80]
+        a[1, N - 1] = 0                                    # (0, sign 0) on the last coefficient, in the second trip
+    r = ref.Encryptor(oracle, N, Q, P)
+    want_pk = [r.encrypt_pk(True, pk0[0], pk1[0], uc[b], us[b], e0[b], e1[b], pt[0]) for b in range(batch)]
+    want_sk = [r.encrypt_sk(True, sk[0], crp[b], e[b], pt[0]) for b in range(batch)]
+    for no_epilogue in (False, True):
+        opt = ring.Options(no_epilogue=1) if no_epilogue else ring.Options()
+        cQ, cP = ring.NewContextWithParams(N, Q, options=opt), ring.NewContextWithParams(N, P, options=opt)
+        enc = ring.BfvEncryptor(cQ, cP, batch, options=opt)
+        qp = lambda x: ring.Poly(cQ, x.shape[1], x.shape[0]).set(x)
+        dpt = cQ.NewPoly(1).set(pt)
+        for form, want in (("pk", want_pk), ("sk", want_sk)):
+            ct = (cQ.NewPoly(batch), cQ.NewPoly(batch))
+            if form == "pk":
+                enc.EncryptPk((qp(pk0), qp(pk1)), (uc, us), (e0, e1), dpt, ct, fast=True)
+            else:
+                enc.EncryptSk(qp(sk), qp(crp), e, dpt, ct, fast=True)
+            got = [p.get().reshape(batch, nQ, N) for p in ct]
+            for b in range(batch):
+                assert np.array_equal(got[0][b], want[b][0]) and np.array_equal(got[1][b], want[b][1]), (form, no_epilogue, b)
 
 
 def test_fast_forms_without_p(gpu_pkg, oracle):

@@ -5,6 +5,8 @@ batches 1 and 3, keys and plaintext shared by the batch or one per ciphertext, t
   PN12QP109  N = 2^12, 2 + 1 limbs: CKKS moduli, the FP64-butterfly route
   PN13QP218  N = 2^13, 6 + 1 limbs: levels top, 0 and 3
   PN14QP438  its moduli at N = 2^11, 10 + 2 limbs: the one shape with |P| = 2; levels top, 0 and 5
+  n65536     N = 2^16, 2 + 1 limbs of PN16QP1761, batch 2 with shared keys: pk and sk, fast and through P, in both shapes -- the one degree
+             at which a lane of the streaming kernels makes a second trip of its loop
 The randomness carries every edge decision at fixed positions: the four ternary (coeff, sign) pairs, a bit plane of all ones, the noise
 bytes (0, sign 0) -- the residue q -- (0, sign 1), (19, +-), (127, +-); the uniform poly of the sk forms has zero coefficients, so that Neg
 yields q.  The outputs are pre-filled with a pattern: limbs above the level keep it.  pk through P equals lr_ckks_encrypt_pk fed the
@@ -110,6 +112,46 @@ def _rings(ring, c, no_epilogue):
 
 def _pattern(batch, limbs, N):
     return (np.arange(batch * limbs * N, dtype=np.uint64) * np.uint64(2654435761) % np.uint64(1 << 30)).reshape(batch, limbs, N)
+
+
+def test_pk_and_sk_encryption_at_n65536(gpu_pkg, oracle):
+    """two trips of the streaming loops: the expansion and the two fast passes, and through P the products with the keys and the noise of
+    the BFV encryptor's kernels; the keys and the plaintext shared by a batch of 2"""
+    ring = gpu_pkg.ring
+    N, Q, P = gpu_pkg.params.ckks_moduli("PN16QP1761")
+    Q, P, batch = list(Q[:2]), list(P[:1]), 2
+    nQ, level, rng = len(Q), len(Q) - 1, np.random.default_rng(65536)
+    sk, pk0, pk1 = (k[None] for k in ref.keygen(oracle, N, Q + P, rng)[:3])
+    uni = lambda moduli, n: np.stack([np.array([rng.integers(0, q, N, dtype=np.uint64) for q in moduli], dtype=np.uint64) for _ in range(n)])
+    crp, pt = uni(Q + P, batch), uni(Q, 1)
+    crp[1, :, N - 1] = 0                                   # a zero product on the last coefficient, in the second trip: Neg yields q
+    bits = lambda: rng.integers(0, 256, (batch, N >> 3)).astype(np.uint8)
+    noise = lambda: (rng.integers(0, 20, (batch, N)) | (rng.integers(0, 2, (batch, N)) << 7)).astype(np.uint8)
+    uc, us, e0, e1, e = bits(), bits(), noise(), noise(), noise()
+    for a in (e0, e1, e):
+        a[0, :6] = [0, 0x80, 19, 19 | 0x80, 127, 127 | 0x80]
+        a[1, N - 1] = 0                                    # (0, sign 0) on the last coefficient
+    r = ref.Encryptor(oracle, N, Q, P)
+    want = {}
+    for fast in (True, False):
+        want[("pk", fast)] = [r.encrypt_pk(fast, level, pk0[0], pk1[0], uc[b], us[b], e0[b], e1[b], pt[0]) for b in range(batch)]
+        want[("sk", fast)] = [r.encrypt_sk(fast, level, sk[0], crp[b], e[b], pt[0]) for b in range(batch)]
+    for no_epilogue in (False, True):
+        opt = ring.Options(no_epilogue=1) if no_epilogue else ring.Options()
+        cQ, cP = ring.NewContextWithParams(N, Q, options=opt), ring.NewContextWithParams(N, P, options=opt)
+        enc = ring.CkksEncryptor(cQ, cP, batch, options=opt)
+        qp = lambda x: ring.Poly(cQ, x.shape[1], x.shape[0]).set(x)
+        dpt = cQ.NewPoly(1).set(pt)
+        for form, fast in FORMS:
+            ct = (cQ.NewPoly(batch), cQ.NewPoly(batch))
+            if form == "pk":
+                enc.EncryptPk((qp(pk0), qp(pk1)), (uc, us), (e0, e1), dpt, ct, level, fast=fast)
+            else:
+                enc.EncryptSk(qp(sk), qp(crp), e, dpt, ct, level, fast=fast)
+            got = [p.get().reshape(batch, nQ, N) for p in ct]
+            for b in range(batch):
+                w = want[(form, fast)][b]
+                assert np.array_equal(got[0][b], w[0]) and np.array_equal(got[1][b], w[1]), (form, fast, no_epilogue, b)
 
 
 @pytest.mark.parametrize("shared", [True, False], ids=["shared_keys", "own_keys"])

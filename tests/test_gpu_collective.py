@@ -7,7 +7,8 @@ call-by-call shape), batch 1 and 3, keys shared by the batch or one per cipherte
   ckks PN14QP438       its moduli at N = 2^11, 10 + 2 limbs, |P| = 2; levels 0, 9
   bfv PN12QP109, PN13QP218   2 + 1 and 3 + 1 limbs: 39- and 54-bit limbs
   bfv PN14QP438        its moduli at N = 2^11, 6 + 2 limbs, |P| = 2
-  n65536               N = 2^16, 2 + 1 limbs of CKKS PN16QP1761: one CKS share, batch 1, the sub-block transform route
+  n65536               N = 2^16, 2 + 1 limbs of CKKS PN16QP1761: one CKS share, one PCKS share and a fold of 3 shares with a base, batch 1:
+                       the sub-block transform route, and the one degree at which a lane of the streaming kernels makes a second trip
 The noise carries the edge decisions (0, +) (0, -) (19, +-) (127, +-) at fixed positions, with (0, sign 0) also on the last coefficient of
 another batch member; sk_in == sk_out on one NTT coefficient; c1 has coefficients 0 and q_j - 1.  Outputs are pre-filled with a pattern
 (limbs above the level keep it); every input is compared unchanged afterwards.  The fold runs with 1, 2, 3 and 33 shares (a second pass),
@@ -193,6 +194,27 @@ def test_one_cks_share_at_n65536(gpu_pkg, oracle):
         qp = lambda x: ring.Poly(cQ, x.shape[1], x.shape[0]).set(x)
         share = col.CkksCksShare(qp(c["sk_in"]), qp(c["sk_out"]), qp(c["c1"]), c["e"][0], qp(_pattern(1, nQ, N)), level)
         assert np.array_equal(share.get(), want), no_epilogue
+
+
+def test_one_pcks_share_and_a_fold_at_n65536(gpu_pkg, oracle):
+    """two trips of the streaming loops in the PCKS addend and the fold (3 shares and a base, the residue q_j on the last coefficient)"""
+    ring = gpu_pkg.ring
+    c = _case(oracle, gpu_pkg, "ckks", "n65536")
+    N, Q, nQ, level = c["N"], c["Q"], len(c["Q"]), len(c["Q"]) - 1
+    want = c["want"]("pcks", level, 0, 0)
+    rng = np.random.default_rng(65536)
+    shares, base = [keygen_ref.uniform(rng, Q, N, 1) for _ in range(3)], keygen_ref.uniform(rng, Q, N, 1)
+    shares[1][:, :, N - 1] = np.array(Q, dtype=np.uint64)
+    folded = c["ref"].aggregate([s[0] for s in shares], base[0])
+    for no_epilogue in (False, True):
+        opt, cQ, cP = _rings(ring, c, no_epilogue)
+        col = ring.Collective(cQ, cP, 1, options=opt)
+        qp = lambda x: ring.Poly(cQ, x.shape[1], x.shape[0]).set(x)
+        out = (qp(_pattern(1, nQ, N)), qp(_pattern(1, nQ, N)))
+        col.CkksPcksShare(qp(c["sk_in"]), (qp(c["pk0"]), qp(c["pk1"])), qp(c["c1"]), (c["uc"], c["us"]), (c["e"][1], c["e"][2]), out, level)
+        assert np.array_equal(out[0].get(), want[0]) and np.array_equal(out[1].get(), want[1]), no_epilogue
+        got = col.Aggregate([qp(s) for s in shares], qp(_pattern(1, nQ, N)), level, base=qp(base))
+        assert np.array_equal(_get(got)[0], folded), no_epilogue
 
 
 @pytest.mark.parametrize("name,counts,batch", [("n16", [1, 2, 3, 33], 2), ("PN13QP218", [3], 1)])

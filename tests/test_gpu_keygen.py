@@ -6,7 +6,8 @@ reference's call-by-call shape), 1 and 3 keys per call, secret keys shared by th
   PN13QP218  N = 2^13, 6 + 1 limbs, beta 6
   PN14QP438  its moduli at N = 2^11, 10 + 2 limbs, beta 5, alpha 2
   ragged     N = 2^11, the first 5 Q and both P of PN14QP438, beta 3: the last digit owns one row (the reference's break)
-  n65536     N = 2^16, 2 + 1 limbs of PN16QP1761: one rotation key, the sub-block transform route and a 2^16 Galois gather
+  n65536     N = 2^16, 2 + 1 limbs of PN16QP1761: one rotation key, one public key and one relinearisation key: the sub-block transform
+             route, a 2^16 Galois gather, and the one degree at which a lane of the streaming kernels makes a second trip
 The randomness carries every edge decision at fixed positions: the four ternary (coeff, sign) pairs, a bit plane of all ones, the noise
 bytes (0, sign 0), (0, sign 1), (19, +-), (127, +-), with (0, sign 0) also on the last coefficient of another key; the uniform half has
 coefficients 0 (q - MRed = q) and q_j - 1.  Galois elements 5, 5^-1, 2 N - 1, 1 and one element twice in a call; one and two powers of
@@ -212,6 +213,23 @@ def test_one_rotation_key_at_n65536(gpu_pkg, oracle):
         keys = _key_images(kg, c, 1)
         kg.GenRotationKeys(sk, [5], c["e"][:1], keys)
         _check_keys(keys, [want], c, 0, ("n65536", no_epilogue))
+
+
+def test_public_and_relinearisation_key_at_n65536(gpu_pkg, oracle):
+    """two trips of the streaming loops in the public key's pass and the powers of sk, in both shapes"""
+    ring = gpu_pkg.ring
+    c = _case(oracle, gpu_pkg, "n65536")
+    N, rows, want = c["N"], len(c["Q"]) + len(c["P"]), c["want"]
+    for no_epilogue in (False, True):
+        opt, cQ, cP = _rings(ring, c, no_epilogue)
+        kg = ring.KeyGenerator(cQ, cP, 1, options=opt)
+        qp = lambda x: ring.Poly(cQ, rows, x.shape[0]).set(x)
+        sk, pk = qp(c["sk"][:1]), (qp(_pattern(1, rows, N)), qp(c["pk1"][:1]))
+        kg.GenPublicKey(sk, c["pk_e"][:1], pk)
+        assert np.array_equal(pk[0].get().reshape(rows, N), want("pk", 0, 0)), no_epilogue
+        keys = _key_images(kg, c, 1)
+        kg.GenRelinKeys(sk, c["e"][:1], keys)
+        _check_keys(keys, [want("rlk", 0)], c, 0, ("n65536", "rlk", no_epilogue))
 
 
 MANY = 70      # more than the 32 keys of one pass: passes of 32, 32 and 6

@@ -6,7 +6,8 @@ call-by-call shape), batch 1 and 3, keys shared by the batch or one per cipherte
   ckks PN13QP218       N = 2^13, 6 limbs; levelStart 0, 3, 5 = L: 1, 2 and 3 mask words
   ckks PN14QP438       its moduli at N = 2^11, 10 limbs; levelStart 0 and 9 (6 words)
   bfv PN12QP109, PN13QP218, PN14QP438 (N = 2^11, |P| = 2)
-  n65536               N = 2^16, 2 limbs of CKKS PN16QP1761: one shares + finalize, batch 1
+  n65536               N = 2^16, 2 limbs of CKKS PN16QP1761: one shares + finalize, batch 1; with its P limb, one dbfv shares + finalize:
+                       the one degree at which a lane of the streaming kernels makes a second trip of its loop
 and beyond them 20 limbs of Qi60 at N = 2^4 (Recode with more than 16 digits per coefficient) and handles of max_batch 5 at batches 1, 3.
 The noise carries the edge decisions (0, +) (0, -) (19, +-) (127, +-) at fixed positions, with (0, sign 0) also on the last coefficient of
 another batch member; the CKKS masks 0, +-1, +-(2^64 - 1), +-2^64, the largest and smallest W-word values and a multiple of q_i; the
@@ -264,6 +265,23 @@ def test_one_ckks_refresh_at_n65536(gpu_pkg, oracle):
         assert np.array_equal(dec.get(), w[0]) and np.array_equal(rec.get(), w[1]), no_epilogue
         fin = r.CkksFinalize(ls, qp(c["c0_at"][ls]), (qp(c["dec"]), qp(c["rec"])), qp(_pattern(1, nQ, N)))
         assert np.array_equal(fin.get(), wf), no_epilogue
+
+
+def test_one_bfv_refresh_at_n65536(gpu_pkg, oracle):
+    """two trips of the streaming loops in the products in front of the inverse transforms and in both modes of the lift, in both shapes"""
+    ring = gpu_pkg.ring
+    c = _case(oracle, gpu_pkg, "bfv", "n65536")
+    N, nQ = c["N"], len(c["Q"])
+    w, wf = c["want"]("shares", None, 0, 0), c["want"]("finalize", None, 0)
+    for no_epilogue in (False, True):
+        opt, cQ, cP = _rings(ring, c, no_epilogue, True)
+        r = ring.Refresh(cQ, cP, T, 1, options=opt)
+        qp = lambda x: ring.Poly(cQ, x.shape[1], x.shape[0]).set(x)
+        dec, rec = r.BfvGenShares(qp(c["sk"]), qp(c["c1"]), qp(c["crs"]), c["mask"], (c["e"][0], c["e"][1]),
+                                  (qp(_pattern(1, nQ, N)), qp(_pattern(1, nQ, N))))
+        assert np.array_equal(_get(dec)[0], w[0]) and np.array_equal(_get(rec)[0], w[1]), no_epilogue
+        out = r.BfvFinalize(qp(c["c0"]), qp(c["crs"]), (qp(c["dec"]), qp(c["rec"])), (qp(_pattern(1, nQ, N)), qp(_pattern(1, nQ, N))))
+        assert np.array_equal(_get(out[0])[0], wf[0]) and np.array_equal(_get(out[1])[0], wf[1]), no_epilogue
 
 
 def test_recode_beyond_sixteen_digits(gpu_pkg, oracle):

@@ -458,14 +458,24 @@ def test_rescale_round_unfused_agrees(gpu_pkg, oracle, logn, monkeypatch):
 # The kernels put the limb on blockIdx.y and the batch on blockIdx.z with 16 B per lane: a shape-dependent indexing error would not
 # show at N = 2^12 x 3 limbs x batch 2.  Every coefficient of every poly against the oracle.
 REAL_SHAPES = [(14, 8, 3), (15, 16, 3)]
+# beside them, for the streaming kernels: N = 2^16, the one degree at which a lane makes a second trip of its grid-stride loop (64
+# workgroups of 256 lanes cover 2^14 coefficient pairs); 2 limbs of PN16QP1761, batch 1
+EWISE_SHAPES = REAL_SHAPES + [(16, 2, 1)]
 
 
-@pytest.mark.parametrize("logn,limbs,batch", REAL_SHAPES)
+def _ewise_moduli(pkg, logn, limbs):
+    if logn == 16:
+        N, Q, _ = pkg.params.ckks_moduli("PN16QP1761")
+        return N, list(Q[:limbs])
+    N, moduli = pkg.params.DefaultParamsQi(logn)
+    assert len(moduli) == limbs
+    return N, list(moduli)
+
+
+@pytest.mark.parametrize("logn,limbs,batch", EWISE_SHAPES)
 @pytest.mark.parametrize("op", ["MUL_MONT", "MUL_MONT_AND_ADD_NOMOD", "MUL_MONT_AND_ADD", "MUL_COEFFS", "ADD", "SUB"])
 def test_three_operand_ops_at_baseline_shapes(gpu_pkg, oracle, logn, limbs, batch, op):
-    N, moduli = gpu_pkg.params.DefaultParamsQi(logn)
-    moduli = list(moduli)
-    assert len(moduli) == limbs
+    N, moduli = _ewise_moduli(gpu_pkg, logn, limbs)
     ctx, oc = gpu_pkg.ring.NewContextWithParams(N, moduli), oracle.Context(N, moduli)
     mk = lambda s: gpu_pkg.sampling.uniform_poly(moduli, N, batch, seed=900 + s).reshape(batch, limbs, N)
     a, b, c = mk(1), mk(2), mk(3)
@@ -479,10 +489,9 @@ def test_three_operand_ops_at_baseline_shapes(gpu_pkg, oracle, logn, limbs, batc
         assert np.array_equal(got[i, level + 1:], c[i, level + 1:]), (op, i)
 
 
-@pytest.mark.parametrize("logn,limbs,batch", REAL_SHAPES)
+@pytest.mark.parametrize("logn,limbs,batch", EWISE_SHAPES)
 def test_two_operand_ops_at_baseline_shapes(gpu_pkg, oracle, logn, limbs, batch):
-    N, moduli = gpu_pkg.params.DefaultParamsQi(logn)
-    moduli = list(moduli)
+    N, moduli = _ewise_moduli(gpu_pkg, logn, limbs)
     ctx, oc = gpu_pkg.ring.NewContextWithParams(N, moduli), oracle.Context(N, moduli)
     a = gpu_pkg.sampling.uniform_poly(moduli, N, batch, seed=77).reshape(batch, limbs, N)
     pa, pc = ctx.NewPoly(batch).set(a), ctx.NewPoly(batch)

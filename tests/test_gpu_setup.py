@@ -6,7 +6,9 @@ per call, keys shared by the call or one per party, on
   PN12QP109  N = 2^12, 2 + 1 limbs, beta 2: CKKS moduli, the FP64-butterfly route
   ragged     N = 2^11, the first 5 Q and both P of PN14QP438, beta 3: the last digit owns one row (the reference's break)
   PN14QP438  its moduli at N = 2^11, 10 + 2 limbs, beta 5, alpha 2
-  n65536     N = 2^16, 2 + 1 limbs of PN16QP1761: one RTG share, the sub-block transform route and a 2^16 Galois gather
+  n65536     N = 2^16, 2 + 1 limbs of PN16QP1761: one RTG share (the sub-block transform route and a 2^16 Galois gather); one party's CKG
+             share, RKG rounds 1-3 and naive rounds 1-2 with their keys: the one degree at which a lane of the streaming kernels makes a
+             second trip of its loop
 The randomness carries every edge decision at fixed positions (setup_ref.inputs): the four ternary (coeff, sign) pairs, a bit plane of
 all ones, the noise bytes (0, sign 0), (0, sign 1), (19, +-), (127, +-), with (0, sign 0) also on a last coefficient; crs and crp have
 coefficients 0 and q_j - 1.  Outputs are pre-filled with a pattern; every input is compared unchanged afterwards.  33 shares in one fold
@@ -223,6 +225,33 @@ def test_one_rtg_share_at_n65536(gpu_pkg, oracle):
         st = ring.Setup(cQ, cP, 1, options=opt)
         share = st.RtgShare(st.NewPoly().set(sk[None]), [5], st.NewShare().set(crp), e, [st.NewShare().set(_pattern(beta, rows, N))])[0]
         assert np.array_equal(share.get(), want), no_epilogue
+
+
+def test_one_party_through_every_round_at_n65536(gpu_pkg, oracle):
+    """two trips of the streaming loops in the CKG pass, the five share kinds beside RTG and the key pass, in both shapes"""
+    ring = gpu_pkg.ring
+    c = _case(oracle, gpu_pkg, "n65536")
+    N, rows, beta, want = c["N"], c["rows"], c["beta"], c["want"]
+    for no_epilogue in (False, True):
+        opt, cQ, cP = _rings(ring, c, no_epilogue)
+        st = ring.Setup(cQ, cP, 1, options=opt)
+        qp = lambda x: ring.Poly(cQ, rows, x.shape[0]).set(x) if x.ndim == 3 else ring.Poly(cQ, rows, 1).set(x[None])
+        new = lambda members: [ring.Poly(cQ, rows, members).set(_pattern(members, rows, N))]
+        inputs = {k: qp(c[k]) for k in ("crs", "crp", "pk0", "r1_sum", "r2_sum", "r3_sum", "n1_sum", "n2_sum")}
+        sk, u, pk = qp(c["sk"][:1]), qp(c["u"][:1]), (inputs["pk0"], inputs["crs"])
+        share = st.CkgShare(sk, inputs["crs"], c["ckg_e"][:1], ring.Poly(cQ, rows, 1).set(_pattern(1, rows, N)))
+        assert np.array_equal(share.get().reshape(rows, N), want("ckg")), no_epilogue
+        got = {"r1": st.RkgRound1(u, sk, inputs["crp"], c["r1_e"][:1], new(beta)),
+               "r2": st.RkgRound2(inputs["r1_sum"], sk, inputs["crp"], c["r2_e"][:1], new(2 * beta)),
+               "r3": st.RkgRound3(inputs["r2_sum"], u, sk, c["r3_e"][:1], new(beta)),
+               "n1_bfv": st.RkgNaiveRound1(st.BFV, sk, pk, c["n1_e"][:1], (c["n1_bits"][0][:1], c["n1_bits"][1][:1]), new(2 * beta)),
+               "n2": st.RkgNaiveRound2(inputs["n1_sum"], sk, pk, (c["n2_bits"][0][:1], c["n2_bits"][1][:1]), c["n2_e"][:1], new(2 * beta))}
+        for kind, shares in got.items():
+            assert np.array_equal(shares[0].get(), want(kind)), (kind, no_epilogue)
+        evk = st.RkgKey(inputs["r2_sum"], inputs["r3_sum"], st.NewPairShare().set(_pattern(2 * beta, rows, N)))
+        assert np.array_equal(evk.get(), want("rlk")), no_epilogue
+        evk = st.RkgNaiveKey(inputs["n2_sum"], st.NewPairShare().set(_pattern(2 * beta, rows, N)))
+        assert np.array_equal(evk.get(), want("rlk_naive")), no_epilogue
 
 
 def test_thirty_three_shares_in_one_fold(gpu_pkg, oracle):
