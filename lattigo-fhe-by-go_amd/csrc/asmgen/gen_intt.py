@@ -12,12 +12,10 @@ butterflies that add two X-type values need the conditional subtraction of 8q: h
 generation time inside a pass and applied unconditionally on the first stage of a pass.
 15 VALU instructions per butterfly without correction, 19 with.  Inputs must be below 4q.
 
-    python gen_intt.py 15 out.s
+    python catalogue.py build OUTDIR                                (assembly text and code objects of every shipped kernel)
     python ../../../tests/asm_emulate.py 15 --selftest-inverse      (emulator check against the oracle)
 """
-import sys
-
-from gen_ntt import CROSS32, T, Dual, Gen, kernel_text_for
+from gen_ntt import CROSS32, T, Gen
 from isa import EXEC, Neg, s, v
 
 
@@ -630,28 +628,3 @@ class GenInv(Gen):
             self.flush_stamps(3 + 5 * self.HALVES)
         self.e("s_endpgm")
         return self.p
-
-
-if __name__ == "__main__":
-    logn = int(sys.argv[1])
-    mode = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    threads = int(sys.argv[4]) if len(sys.argv) > 4 else 1024
-    # mode 3: FP64 body for the limbs below 2^46, the integer body of mode 1 for the others
-    def make(logn_, threads_, **kw):
-        if mode == 3:
-            return Dual(lambda fp: GenInv(logn_, 1, threads_, fp=fp, dual=True, **kw))
-        return GenInv(logn_, mode, threads_, **kw)
-
-    if logn == 16:      # "s": lazy sub-blocks, ntt_top_kernel follows; "f": the last stage fused (pair flags in NttLaunch::epi_x)
-        fused = len(sys.argv) > 5 and sys.argv[5] == "fused"
-        open(sys.argv[2], "w").write(kernel_text_for(make(15, 1024, sub=True, fuse_last=fused), "lr_ntt_inv16%s_m%d" % ("f" if fused else "s", mode)))
-        sys.exit(0)
-    if len(sys.argv) > 5 and sys.argv[5] == "halves":        # N = 2^15 as two 2^14 sub-blocks with lazy outputs, ntt_top_kernel follows: small launches
-        assert logn == 15
-        open(sys.argv[2], "w").write(kernel_text_for(make(14, 1024, sub=True), "lr_ntt_inv15h_m%d" % mode))
-        sys.exit(0)
-    if len(sys.argv) > 5 and sys.argv[5] == "timeline":      # diagnostics build with per-phase clock stamps (Options::timeline)
-        open(sys.argv[2], "w").write(kernel_text_for(make(logn, threads, profile=True), "lr_ntt_inv%d_m%dt" % (logn, mode)))
-        sys.exit(0)
-    name = "lr_ntt_inv%d%s_m%d" % (logn, "x" if threads < 1024 else "", mode)
-    open(sys.argv[2], "w").write(kernel_text_for(make(logn, threads), name))

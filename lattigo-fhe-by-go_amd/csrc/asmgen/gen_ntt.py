@@ -11,11 +11,10 @@ compiler's version: 21-26).
 Three variants per degree (Gen.mode) cover every modulus in (2^33, 2^61); the host picks the cheapest one
 the context's largest modulus allows and falls back to the C++ kernels for smaller moduli or degrees.
 
-    python gen_ntt.py 15 out.s [mode] # assembly text
-    python gen_ntt.py 15 --selftest   # emulate one workgroup with numpy and compare with a reference NTT
+    python catalogue.py build OUTDIR                        # assembly text and code objects of every shipped kernel
+    python ../../../tests/asm_emulate.py 15 --selftest      # emulate one workgroup with numpy and compare with the oracle
 """
 import os
-import sys
 
 from isa import VCC, Neg, Program, Reg, s, v
 
@@ -1316,11 +1315,6 @@ class Dual:
         return p
 
 
-def kernel_text(logn, name):
-    g = Gen(logn)
-    return kernel_text_for(g, name), g, g.p
-
-
 def kernel_text_for(g, name):
     prog = g.build()
     lds_bytes = g.SPH * 9216
@@ -1381,37 +1375,3 @@ amdhsa.version: [1, 2]
 
 
 FP_LIMIT = 1 << 46
-
-
-if __name__ == "__main__":
-    logn = int(sys.argv[1])
-    mode = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    threads = int(sys.argv[4]) if len(sys.argv) > 4 else 1024
-    # mode 3: FP64 body for the limbs below 2^46, the integer body of mode 2 for the others (every modulus below 2^57)
-    def make(logn_, threads_, **kw):
-        if mode == 5:   # "m5": the integer kernel of mode 1 (q <= 2^60) with the subtract-multiply-add epilogue
-            return Gen(logn_, 1, threads_, epi=True, **kw)
-        if mode == 3:
-            return Dual(lambda fp: Gen(logn_, 2, threads_, fp=fp, dual=True, **kw))
-        if mode == 4:   # mode 3 whose FP64 body ends in the subtract-multiply-add epilogue
-            return Dual(lambda fp: Gen(logn_, 2, threads_, fp=fp, dual=True, epi=True, **kw))
-        return Gen(logn_, mode, threads_, **kw)
-
-    if logn == 16:      # the 2^15 sub-block kernels of N = 2^16: "s" with the fused top stage, "p" plain
-        fused = not (len(sys.argv) > 5 and sys.argv[5] == "plain")
-        open(sys.argv[2], "w").write(kernel_text_for(make(15, 1024, sub=True, fused=fused),
-                                                     "lr_ntt_fwd16%s_m%d" % ("s" if fused else "p", mode)))
-        sys.exit(0)
-    if len(sys.argv) > 5 and sys.argv[5] == "halves":        # N = 2^15 as two 2^14 sub-blocks, plain (the top stage applied before): small launches
-        assert logn == 15
-        open(sys.argv[2], "w").write(kernel_text_for(make(14, 1024, sub=True, fused=False), "lr_ntt_fwd15h_m%d" % mode))
-        sys.exit(0)
-    if len(sys.argv) > 5 and sys.argv[5] == "timeline":      # diagnostics build with per-phase clock stamps (Options::timeline)
-        open(sys.argv[2], "w").write(kernel_text_for(make(logn, threads, profile=True), "lr_ntt_fwd%d_m%dt" % (logn, mode)))
-        sys.exit(0)
-    if len(sys.argv) > 5 and sys.argv[5] in ("persist", "persist-timeline"):    # several polys per workgroup, next poly's loads prefetched
-        tl = sys.argv[5] == "persist-timeline"
-        open(sys.argv[2], "w").write(kernel_text_for(make(logn, threads, persist=True, profile=tl), "lr_ntt_fwd%dp_m%d%s" % (logn, mode, "t" if tl else "")))
-        sys.exit(0)
-    name = "lr_ntt_fwd%d%s_m%d" % (logn, "x" if threads < 1024 else "", mode)     # x: several workgroups per CU
-    open(sys.argv[2], "w").write(kernel_text_for(make(logn, threads), name))

@@ -1,9 +1,12 @@
-// lr_asm.cpp -- loader/launcher of the hand-scheduled gfx950 assembly kernels (asmgen/gen_ntt.py).
+// lr_asm.cpp -- loader/launcher of the hand-scheduled gfx950 assembly kernels (asmgen/gen_ntt.py, gen_intt.py).
 //
 // The code objects are generated and assembled at build time (build.sh) and embedded in this
-// library (lr_asm_blob.cpp).  They implement exactly the forward and inverse NTT of lr_ntt.hip for
-// N = 2^14 and 2^15 and every modulus in (2^33, 2^61), in three lazy-correction variants; everything
-// else stays on the C++ kernels.
+// library (build/lr_asm_blob.cpp); asmgen/catalogue.py states which ones there are, their names and
+// their block sizes.  They implement exactly the forward and inverse NTT of lr_ntt.hip for
+// N = 2^12 ... 2^16 (2^16 as two 2^15 sub-blocks per limb, 2^15 also as two 2^14 ones) and every modulus in
+// (2^33, 2^61): integer kernels in three lazy-correction variants, dual kernels with an FP64 body for
+// the limbs below 2^46, and forward kernels that end in the subtract-multiply-add epilogue.  Smaller
+// degrees and moduli stay on the C++ kernels.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -19,6 +22,7 @@ struct lr_asm_blob {
     const char *name;
     const unsigned char *data;
     unsigned long size;
+    unsigned threads;        // block size of the kernel (catalogue.py: Kernel.threads)
 };
 extern "C" const lr_asm_blob lr_asm_blobs[];
 extern "C" const int lr_asm_blob_count;
@@ -26,8 +30,12 @@ extern "C" const int lr_asm_blob_count;
 namespace lr {
 
 namespace {
+struct AsmKernel {
+    hipFunction_t fn;
+    unsigned threads;
+};
 struct AsmKernels {
-    std::map<std::string, hipFunction_t> fn;
+    std::map<std::string, AsmKernel> fn;
     std::vector<hipModule_t> mods;
     bool ok = false;
 };
@@ -49,7 +57,7 @@ AsmKernels *kernels_for_current_device() {
                hipModuleGetFunction(&fn, mod, lr_asm_blobs[i].name) == hipSuccess;
         if (k.ok) {
             k.mods.push_back(mod);
-            k.fn[lr_asm_blobs[i].name] = fn;
+            k.fn[lr_asm_blobs[i].name] = AsmKernel{fn, lr_asm_blobs[i].threads};
         }
     }
     if (!k.ok) (void)hipGetLastError();
@@ -78,11 +86,11 @@ hipError_t launch_ntt_asm(const NttLaunch &a, int logn, int inverse, int variant
     AsmKernels *k = kernels_for_current_device();
     if (!k || logn < 12 || logn > 15) return hipErrorNotSupported;
     if (persist > 0 && (logn != 15 || inverse || variant > 3)) persist = 0;     // (no persistent form of the epilogue kernels m4 / m5)
-    // N = 2^12 (256 threads, four columns per thread, 36 KiB LDS image) and N = 2^13, 2^14 (512 threads, two columns,
-    // 72 KiB) run several workgroups per CU: one
+    // N = 2^12, 2^13 and 2^14 run several workgroups of fewer than 1024 threads per CU (the "x" kernels: 256 threads = four columns
+    // per thread and a 36 KiB LDS image, 512 = two columns and 72 KiB; the table entry carries the block size): one
     // covers the other's load and store phases.  wide14 (Options::asm14_1024) selects the 1024-thread kernels (testing aid).
     const bool x = logn <= 13 || (logn == 14 && !wide14);
-    char name[32];
+    char name[32];       // the name of catalogue.py: Kernel.name (tests/test_asm_emulator.py enumerates what this line can format)
     std::snprintf(name, sizeof name, "lr_ntt_%s%d%s_m%d%s", inverse ? "inv" : "fwd", logn, x ? "x" : persist > 0 ? "p" : "", variant, timeline ? "t" : "");
     auto it = k->fn.find(name);
     if (it == k->fn.end()) return hipErrorNotSupported;
@@ -104,7 +112,7 @@ hipError_t launch_ntt_asm(const NttLaunch &a, int logn, int inverse, int variant
         gy = (unsigned)a.group;
         gz = (unsigned)(a.batch / a.group);
     }
-    const unsigned threads = !x ? 1024 : (logn == 12 || (logn == 13 && !inverse)) ? 256 : 512;
+    const unsigned threads = it->second.threads;
     if (persist > 0) {
         // chunks of `persist` consecutive polys of a group per workgroup; the kernel reads the group size for plain launches too
         args.group = (int)gy;
@@ -123,7 +131,7 @@ hipError_t launch_ntt_asm(const NttLaunch &a, int logn, int inverse, int variant
     const unsigned gx = swapped ? gy : gx_items, gyy = swapped ? (unsigned)a.n_items : gy;
     args.stagger_gx = (int)gx;
     args.stagger_unit = stagger_unit(stagger, threads == 1024, swapped, (unsigned long long)gx * gyy * gz);
-    return hipModuleLaunchKernel(it->second, gx, gyy, gz, threads, 1, 1, 0, stream, nullptr, extra);
+    return hipModuleLaunchKernel(it->second.fn, gx, gyy, gz, threads, 1, 1, 0, stream, nullptr, extra);
 }
 
 // N = 2^16 runs as two 2^15 sub-blocks per limb (grid x = 2 * n_items).  kind: 's' = forward with the stage over
@@ -134,7 +142,7 @@ hipError_t launch_ntt_asm(const NttLaunch &a, int logn, int inverse, int variant
 hipError_t launch_ntt_asm16(const NttLaunch &a, int inverse, char kind, int variant, hipStream_t stream, char *kernel_name, int stagger, int full_logn) {
     AsmKernels *k = kernels_for_current_device();
     if (!k) return hipErrorNotSupported;
-    char name[32];
+    char name[32];       // catalogue.py: Kernel.name, tags "16s" / "16p" / "16f" / "15h"
     std::snprintf(name, sizeof name, "lr_ntt_%s%d%c_m%d", inverse ? "inv" : "fwd", full_logn, kind, variant);
     auto it = k->fn.find(name);
     if (it == k->fn.end()) return hipErrorNotSupported;
@@ -154,7 +162,7 @@ hipError_t launch_ntt_asm16(const NttLaunch &a, int inverse, char kind, int vari
     if (gz > 65535u) return hipErrorInvalidValue;
     args.stagger_gx = (int)gy;
     args.stagger_unit = stagger_unit(stagger, true, variant >= 3, (unsigned long long)gy * 2u * (unsigned)a.n_items * gz);
-    return hipModuleLaunchKernel(it->second, gy, 2u * (unsigned)a.n_items, gz, 1024, 1, 1, 0, stream, nullptr, extra);
+    return hipModuleLaunchKernel(it->second.fn, gy, 2u * (unsigned)a.n_items, gz, it->second.threads, 1, 1, 0, stream, nullptr, extra);
 }
 
 }  // namespace lr

@@ -6,6 +6,11 @@ asmgen/isa.py and compares it with the CPU oracle: the same checks the device te
     python tests/asm_emulate.py 15 --selftest [threads]          # forward kernels of 2^15
     python tests/asm_emulate.py 15 --selftest-inverse [threads]
     python tests/asm_emulate.py 16 --selftest | --selftest-inverse   # the 2^15 sub-block kernels of N = 2^16
+    python tests/asm_emulate.py 15 --selftest | --selftest-inverse --halves      # the 2^14 sub-block kernels of N = 2^15
+    python tests/asm_emulate.py 15 --selftest-persist                # the persistent forward kernels of the diagnostics build
+
+Every generator comes from asmgen/catalogue.py (make); --list-cases after any of these prints the catalogue keys its cases exercise
+instead of running them.
 """
 import os
 import sys
@@ -14,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "lattigo-fhe-by-go_amd", "csrc", "asmgen"))
 
-from gen_ntt import FP_LIMIT, Dual, Gen  # noqa: E402,F401
+import catalogue  # noqa: E402
+from gen_ntt import FP_LIMIT  # noqa: E402
 from isa import Machine, Program  # noqa: E402,F401
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -263,22 +269,18 @@ def emulate_persist(make_gen, q, polys, per_wg, chunk):
     return ok, info
 
 
-def selftest_persist(threads=1024):
-    ok = True
-    cases = []
-    for mode in (0, 1, 2):
-        cases.append(("mode %d" % mode, (lambda mode=mode: Gen(15, mode, threads, persist=True)), test_moduli(15, mode)[0]))
-    for q in fp_test_moduli(15):
-        cases.append(("dual", (lambda: Dual(lambda fp: Gen(15, 2, threads, fp=fp, dual=True, persist=True))), q))
-    cases.append(("dual timeline", (lambda: Dual(lambda fp: Gen(15, 2, threads, fp=fp, dual=True, persist=True, profile=True))), fp_test_moduli(15)[0]))
-    for name, make, q in cases:
+def persist_cases(threads=1024):
+    cases = [("mode %d" % mode, mode, {}, test_moduli(15, mode)[0]) for mode in (0, 1, 2)]
+    cases += [("dual", 3, {}, q) for q in fp_test_moduli(15)]
+    cases.append(("dual timeline", 3, {"profile": True}, fp_test_moduli(15)[0]))
+    out = []
+    for name, mode, flavour, q in cases:
         # three polys in one loop (prefetch taken twice, skipped once); a trailing chunk of one poly (no prefetch at all)
         for polys, per_wg, chunk in ((3, 3, 0), (3, 2, 1)):
-            good, info = emulate_persist(make, q, polys, per_wg, chunk)
-            ok = ok and good
-            print("forward persistent logN=15 %s q=%d (%d bits), chunk %d of %d x %d: %s; %s" % (
-                name, q, q.bit_length(), chunk, polys, per_wg, "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
-    return ok
+            run = lambda mk, q=q, shape=(polys, per_wg, chunk): emulate_persist(mk, q, *shape)
+            out.append(("forward persistent logN=15 %s %s, chunk %d of %d x %d" % (name, bits(q), chunk, polys, per_wg),
+                        [(("fwd", mode, 15, threads, dict(flavour, persist=True)), run)], VERDICT))
+    return out
 
 
 def fp_tables(np, q, n_inv, tw, twf, put):
@@ -490,156 +492,141 @@ def emulate_sub(make_gen, inverse, q, pretop=False, order=(0, 1), x=None):
     return ok, info
 
 
-def GenInv_(*a, **k):
-    from gen_intt import GenInv
-    return GenInv(*a, **k)
+# A case is (label, [(key, run)], (word when good, word when bad)): key = (direction, mode, logn, threads, flavour), the arguments of
+# catalogue.make and the catalogue key the part exercises; run(make_gen) -> (ok, info).  One line per case: every part must pass.
+VERDICT = ("bit-exact vs oracle", "MISMATCH")
+GROUPS = (2, 1, 1, 2, 3, 6)          # the digit-group addressing (grid z, skipped limbs)
+ORDERS = ((0, 1), (1, 0))            # of a limb's two sub-block workgroups
 
 
-def selftest(logn, inverse=False, threads=1024):
-    """every case on the seeded random input and on the stress polys of tests/limit_moduli.py (stress_inputs)"""
+def bits(q):
+    return "q=%d (%d bits)" % (q, q.bit_length())
+
+
+def run_cases(cases, list_only=False):
+    """runs the cases and prints a line for each; list_only: prints the catalogue keys they exercise instead"""
     ok = True
-    fams = lambda mk, q, geom, second=False: over_families(logn, q, inverse, lambda x: emulate(mk(), inverse, q, geom, x=x), harshest_only=second)
+    for label, parts, words in cases:
+        good, info = True, None
+        for (direction, mode, logn, threads, flavour), run in parts:
+            if list_only:
+                print(catalogue.key(direction, mode, logn, threads, **flavour))
+                continue
+            g, i = run(lambda: catalogue.make(direction, mode, logn, threads, **flavour))
+            if info is None or not g:           # the first part's summary, or that of a part that failed
+                info = i
+            good = good and g
+        ok = ok and good
+        if not list_only:
+            print("%s: %s; %s" % (label, words[not good], info), flush=True)
+    return ok
+
+
+def selftest_cases(logn, inverse=False, threads=1024):
+    """every case on the seeded random input and on the stress polys of tests/limit_moduli.py (stress_inputs)"""
+    d, head = ("inv", "inverse") if inverse else ("fwd", "forward")
+    head += " logN=%d T=%d" % (logn, threads)
+    key = lambda mode: (d, mode, logn, threads, {})
+
+    def fams(q, geom=None, second=False):
+        return lambda mk: over_families(logn, q, inverse, lambda x: emulate(mk(), inverse, q, geom, x=x), harshest_only=second)
+
+    cases = []
     for mode in ((0, 1) if inverse else (0, 1, 2)):
         for q in test_moduli(logn, mode):
-            mk = (lambda: GenInv_(logn, mode, threads)) if inverse else (lambda: Gen(logn, mode, threads))
-            # the last modulus of each mode also exercises the digit-group addressing (grid z, skipped limbs)
-            geom = (2, 1, 1, 2, 3, 6) if q == test_moduli(logn, mode)[-1] else None
-            good, info = fams(mk, q, geom)
-            ok = ok and good
-            print("%s logN=%d T=%d mode %d q=%d (%d bits): %s; %s" % ("inverse" if inverse else "forward", logn, threads, mode, q, q.bit_length(),
-                                                             "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
+            # the last modulus of each mode also exercises the digit-group addressing
+            geom = GROUPS if q == test_moduli(logn, mode)[-1] else None
+            cases.append(("%s mode %d %s" % (head, mode, bits(q)), [(key(mode), fams(q, geom))], VERDICT))
     # grid x padded to a multiple of eight (lr_asm.cpp): the workgroups beyond n_items store nothing (integer kernels: x = limb)
-    for mk in ([lambda: GenInv_(logn, 1, threads)] if inverse else [lambda: Gen(logn, 1, threads), lambda: Gen(logn, 1, threads, epi=True)]):
-        good, info = emulate(mk(), inverse, test_moduli(logn, 1)[0], (3, 1, 0, 0, 0, 4, 3))
-        ok = ok and good
-        print("%s logN=%d T=%d padding workgroup: %s; %s" % ("inverse" if inverse else "forward", logn, threads, "stores nothing" if good else "WROTE", info), flush=True)
+    for mode in ((1,) if inverse else (1, 5)):
+        pad = lambda mk: emulate(mk(), inverse, test_moduli(logn, 1)[0], (3, 1, 0, 0, 0, 4, 3))
+        cases.append((head + " padding workgroup", [(key(mode), pad)], ("stores nothing", "WROTE")))
     for q in fp_test_moduli(logn):
-        if inverse:
-            mk = lambda: Dual(lambda fp: GenInv_(logn, 1, threads, fp=fp, dual=True))
-        else:
-            mk = lambda: Dual(lambda fp: Gen(logn, 2, threads, fp=fp, dual=True))
-        geom = (2, 1, 1, 2, 3, 6) if q == fp_test_moduli(logn)[0] else None
-        good, info = fams(mk, q, geom)
-        ok = ok and good
-        print("%s logN=%d T=%d dual q=%d (%d bits): %s; %s" % ("inverse" if inverse else "forward", logn, threads, q, q.bit_length(),
-                                                        "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
+        geom = GROUPS if q == fp_test_moduli(logn)[0] else None
+        cases.append(("%s dual %s" % (head, bits(q)), [(key(3), fams(q, geom))], VERDICT))
     if not inverse:
         # the integer epilogue: the pure integer kernel of mode 1 ("m5") on the headline modulus and at both ends of its modulus range,
-        # and the dual kernels' integer body on a modulus just above 2^46
+        # and the dual kernels' integer body on a modulus just above 2^46; then out = (x - NTT(in)) * c + plus on the FP64 body.
+        # Each plain and with the digit-group addressing
         m1 = test_moduli(logn, 1)
-        for q, mk in [(qq, (lambda: Gen(logn, 1, threads, epi=True))) for qq in (m1[0], m1[1], m1[-1])] + \
-                     [(fp_test_moduli(logn)[2], (lambda: Dual(lambda fp: Gen(logn, 2, threads, fp=fp, dual=True, epi=True))))]:
-            for geom in (None, (2, 1, 1, 2, 3, 6)):
-                good, info = fams(mk, q, geom, geom is not None)
-                ok = ok and good
-                print("forward logN=%d T=%d integer epilogue q=%d (%d bits): %s; %s" % (logn, threads, q, q.bit_length(),
-                                                                                  "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
-        # the epilogue kernels: out = (x - NTT(in)) * c + plus on the FP64 body, plain and with the digit-group addressing
-        for q in fp_test_moduli(logn)[:2]:
-            for geom in (None, (2, 1, 1, 2, 3, 6)):
-                good, info = fams(lambda: Dual(lambda fp: Gen(logn, 2, threads, fp=fp, dual=True, epi=True)), q, geom, geom is not None)
-                ok = ok and good
-                print("forward logN=%d T=%d epilogue q=%d (%d bits): %s; %s" % (logn, threads, q, q.bit_length(),
-                                                                          "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
-    return ok
+        epilogues = [("integer epilogue", 5, q) for q in (m1[0], m1[1], m1[-1])] + [("integer epilogue", 4, fp_test_moduli(logn)[2])]
+        epilogues += [("epilogue", 4, q) for q in fp_test_moduli(logn)[:2]]
+        for name, mode, q in epilogues:
+            for geom in (None, GROUPS):
+                cases.append(("%s %s %s" % (head, name, bits(q)), [(key(mode), fams(q, geom, geom is not None))], VERDICT))
+    return cases
 
 
-def selftest_sub(inverse=False):
+def sub_cases(inverse=False):
     """the sub-block kernels of N = 2^16, on the seeded random input and the harshest stress polys"""
-    ok = True
+    d, head = ("inv", "inverse N=2^16 sub-blocks") if inverse else ("fwd", "forward N=2^16 sub-blocks")
+    key = lambda mode, **flavour: (d, mode, 15, 1024, dict(flavour, sub=True))
 
-    def fams(q, mk, **kw):
-        return over_families(16, q, inverse, lambda x: emulate_sub(mk, inverse, q, x=x, **kw))
+    def fams(q, **kw):
+        return lambda mk: over_families(16, q, inverse, lambda x: emulate_sub(mk, inverse, q, x=x, **kw))
 
+    def variants(mode, q):
+        if inverse:     # lazy outputs; the pair-flag kernels (last stage by whichever sub-block finishes second), both orders
+            return [(key(mode), fams(q))] + [(key(mode, fuse_last=True), fams(q, order=order)) for order in ORDERS]
+        # the top stage fused into the loads; the plain variant continues from the output of the separate top-stage pass
+        return [(key(mode), fams(q)), (key(mode, fused=False), fams(q, pretop=True))]
+
+    cases = []
     for mode in ((0, 1) if inverse else (0, 1, 2)):
         q = test_moduli(16, mode)[0]
-        if inverse:
-            make = lambda: GenInv_(15, mode, 1024, sub=True)
-        else:
-            make = lambda: Gen(15, mode, 1024, sub=True)
-        good, info = fams(q, make)
-        if inverse:
-            # the pair-flag kernels (last stage by whichever sub-block finishes second), both orders
-            for order in ((0, 1), (1, 0)):
-                g2, i2 = fams(q, lambda: GenInv_(15, mode, 1024, sub=True, fuse_last=True), order=order)
-                good, info = good and g2, info if g2 else i2
-        if not inverse:
-            # the plain variant continues from the output of the separate top-stage pass
-            good2, i2 = fams(q, lambda: Gen(15, mode, 1024, sub=True, fused=False), pretop=True)
-            good, info = good and good2, info if good2 else i2
-        ok = ok and good
-        print("%s N=2^16 sub-blocks mode %d q=%d (%d bits): %s; %s" % ("inverse" if inverse else "forward", mode, q, q.bit_length(),
-                                                                    "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
+        cases.append(("%s mode %d %s" % (head, mode, bits(q)), variants(mode, q), VERDICT))
     if not inverse:
         # the integer epilogue on the sub-block kernels: pure integer ("m5", fused top stage and plain), and the dual kernels' integer body
-        for q1 in test_moduli(16, 1)[:2]:
-            for label, mk, pre in (("m5 fused-top", (lambda: Gen(15, 1, 1024, sub=True, epi=True)), False),
-                                   ("m5 plain", (lambda: Gen(15, 1, 1024, sub=True, fused=False, epi=True)), True)):
-                good, info = fams(q1, mk, pretop=pre)
-                ok = ok and good
-                print("forward N=2^16 sub-blocks %s q=%d (%d bits): %s; %s" % (label, q1, q1.bit_length(), "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
-        q2 = fp_test_moduli(16)[2]
-        good, info = fams(q2, lambda: Dual(lambda fp: Gen(15, 2, 1024, sub=True, fused=False, fp=fp, dual=True, epi=True)), pretop=True)
-        ok = ok and good
-        print("forward N=2^16 sub-blocks dual integer-body epilogue q=%d (%d bits): %s; %s" % (q2, q2.bit_length(), "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
+        for q in test_moduli(16, 1)[:2]:
+            cases.append(("%s m5 fused-top %s" % (head, bits(q)), [(key(5), fams(q, pretop=False))], VERDICT))
+            cases.append(("%s m5 plain %s" % (head, bits(q)), [(key(5, fused=False), fams(q, pretop=True))], VERDICT))
+        q = fp_test_moduli(16)[2]
+        cases.append(("%s dual integer-body epilogue %s" % (head, bits(q)), [(key(4, fused=False), fams(q, pretop=True))], VERDICT))
     for q in fp_test_moduli(16)[:2]:
-        if inverse:
-            good, info = fams(q, lambda: Dual(lambda fp: GenInv_(15, 1, 1024, sub=True, fp=fp, dual=True)))
-            for order in ((0, 1), (1, 0)):
-                g2, i2 = fams(q, lambda: Dual(lambda fp: GenInv_(15, 1, 1024, sub=True, fp=fp, dual=True, fuse_last=True)), order=order)
-                good, info = good and g2, info if g2 else i2
-        else:
-            good, info = fams(q, lambda: Dual(lambda fp: Gen(15, 2, 1024, sub=True, fp=fp, dual=True)))
-            for mk in ((lambda: Dual(lambda fp: Gen(15, 2, 1024, sub=True, fused=False, fp=fp, dual=True))),
-                       (lambda: Dual(lambda fp: Gen(15, 2, 1024, sub=True, fused=False, fp=fp, dual=True, epi=True)))):
-                g2, i2 = fams(q, mk, pretop=True)
-                good, info = good and g2, info if g2 else i2
-        ok = ok and good
-        print("%s N=2^16 sub-blocks dual q=%d (%d bits): %s; %s" % ("inverse" if inverse else "forward", q, q.bit_length(),
-                                                             "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
-    return ok
+        parts = variants(3, q) + ([] if inverse else [(key(4, fused=False), fams(q, pretop=True))])
+        cases.append(("%s dual %s" % (head, bits(q)), parts, VERDICT))
+    if not inverse:
+        # the epilogue behind the fused top stage (lr_ntt_fwd16s_m4, route Fwd16Fused with an epilogue): FP64 body and integer body
+        for q in (fp_test_moduli(16)[0], fp_test_moduli(16)[2]):
+            cases.append(("%s dual fused-top epilogue %s" % (head, bits(q)), [(key(4), fams(q, pretop=False))], VERDICT))
+    return cases
 
 
-def selftest_halves(inverse=False):
+def halves_cases(inverse=False):
     """N = 2^15 as two 2^14 sub-blocks (small launches: twice the workgroups, half the latency): the plain forward sub-block kernels
     ("h": the stage over bit 14 applied before, by the basis extension or ntt_top_kernel) in every mode incl. the epilogues, the lazy inverse
-    ones; on the seeded random input and the harshest stress polys, the integer modes at the top of their modulus range"""
-    ok = True
-    sub_q = lambda mode: test_moduli(15, mode)[0]
-    cases = []
-    if inverse:
-        for mode in (0, 1):
-            cases.append(("mode %d" % mode, (lambda mode=mode: GenInv_(14, mode, 1024, sub=True)), sub_q(mode)))
-        cases.append(("mode 1", (lambda: GenInv_(14, 1, 1024, sub=True)), test_moduli(15, 1)[1]))
-        for q in fp_test_moduli(15):
-            cases.append(("dual", (lambda: Dual(lambda fp: GenInv_(14, 1, 1024, sub=True, fp=fp, dual=True))), q))
+    ones; on the seeded random input and the harshest stress polys, the integer modes at the top of their modulus range; both orders"""
+    d, head = ("inv", "inverse N=2^15 halves") if inverse else ("fwd", "forward N=2^15 halves")
+    cases = [("mode %d" % mode, mode, test_moduli(15, mode)[0]) for mode in ((0, 1) if inverse else (0, 1, 2))]
+    cases.append(("mode 1", 1, test_moduli(15, 1)[1]))
+    if not inverse:
+        cases.append(("m5", 5, test_moduli(15, 1)[0]))
+    for q in fp_test_moduli(15):
+        cases += [("dual", 3, q)] + ([] if inverse else [("dual epilogue", 4, q)])
+    out = []
+    for name, mode, q in cases:
+        runs = [lambda mk, q=q, order=order: over_families(15, q, inverse, lambda x: emulate_sub(mk, inverse, q, pretop=not inverse, order=order, x=x))
+                for order in ORDERS]
+        key = (d, mode, 14, 1024, {"sub": True} if inverse else {"sub": True, "fused": False})
+        out.append(("%s %s %s" % (head, name, bits(q)), [(key, run) for run in runs], VERDICT))
+    return out
+
+
+def main(argv):
+    list_only = "--list-cases" in argv
+    argv = [a for a in argv if a != "--list-cases"]
+    logn = int(argv[0])
+    inverse = argv[1:2] == ["--selftest-inverse"]
+    if argv[-1] == "--halves":
+        cases = halves_cases(inverse)
+    elif logn == 16:
+        cases = sub_cases(inverse)
+    elif argv[1:2] == ["--selftest-persist"]:
+        cases = persist_cases()
     else:
-        for mode in (0, 1, 2):
-            cases.append(("mode %d" % mode, (lambda mode=mode: Gen(14, mode, 1024, sub=True, fused=False)), sub_q(mode)))
-        cases.append(("mode 1", (lambda: Gen(14, 1, 1024, sub=True, fused=False)), test_moduli(15, 1)[1]))
-        cases.append(("m5", (lambda: Gen(14, 1, 1024, sub=True, fused=False, epi=True)), sub_q(1)))
-        for q in fp_test_moduli(15):
-            cases.append(("dual", (lambda: Dual(lambda fp: Gen(14, 2, 1024, sub=True, fused=False, fp=fp, dual=True))), q))
-            cases.append(("dual epilogue", (lambda: Dual(lambda fp: Gen(14, 2, 1024, sub=True, fused=False, fp=fp, dual=True, epi=True))), q))
-    for label, mk, q in cases:
-        good = True
-        for order in ((0, 1), (1, 0)):
-            g, i2 = over_families(15, q, inverse, lambda x: emulate_sub(mk, inverse, q, pretop=not inverse, order=order, x=x))
-            good, info = good and g, i2 if (not g or order == (1, 0)) else i2
-        ok = ok and good
-        print("%s N=2^15 halves %s q=%d (%d bits): %s; %s" % ("inverse" if inverse else "forward", label, q, q.bit_length(),
-                                                          "bit-exact vs oracle" if good else "MISMATCH", info), flush=True)
-    return ok
+        cases = selftest_cases(logn, inverse, int(argv[2]) if len(argv) > 2 else 1024)
+    return run_cases(cases, list_only)
 
 
 if __name__ == "__main__":
-    logn = int(sys.argv[1])
-    inverse = len(sys.argv) > 2 and sys.argv[2] == "--selftest-inverse"
-    if len(sys.argv) > 2 and sys.argv[-1] == "--halves":
-        sys.exit(0 if selftest_halves(inverse=inverse) else 1)
-    if logn == 16:
-        sys.exit(0 if selftest_sub(inverse=inverse) else 1)
-    threads = int(sys.argv[3]) if len(sys.argv) > 3 else 1024
-    if len(sys.argv) > 2 and sys.argv[2] == "--selftest-persist":
-        sys.exit(0 if selftest_persist() else 1)
-    sys.exit(0 if selftest(logn, inverse=inverse, threads=threads) else 1)
+    sys.exit(0 if main(sys.argv[1:]) else 1)
