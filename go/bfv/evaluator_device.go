@@ -15,9 +15,13 @@
 //	delete  relinearize  :480-501   -> below: degree 2 is ONE call, CkksPlan.BfvRelinearize (key switch + the two Adds); higher degrees
 //	                                   keep upstream's loop over switchKeys
 //	delete  switchKeys   :736-812   -> below: CkksPlan.BfvSwitchKeys (the per-modulus loops over Coeffs at :776-792 live inside the pipeline)
-//	delete  permute      :711-735   -> below: ONE call, CkksPlan.BfvPermute (Context.Permute x2, the key switch, Add, Copy); RotateRows,
-//	                                   RotateColumns and rotateColumnsPow2 (:579-681, kept) reach the device through it
-//	keep    Relinearize :512, SwitchKeys :539, the rotation front ends :560-709, InnerSum :683, Add / Sub / Neg / MulScalar (Context
+//	delete  permute      :711-735   -> below: ONE call, CkksPlan.BfvPermute (Context.Permute x2, the key switch, Add, Copy); RotateRows
+//	                                   and RotateColumns with the key of the rotation (:579-681, kept) reach the device through it
+//	delete  rotateColumnsPow2 :637-666 -> below: ONE call, CkksPlan.BfvRotateChain over the set bits of k (each step one key switch and
+//	                                   one fused pass instead of a permute call of two permutations, the key switch and an Add)
+//	delete  InnerSum     :691-708   -> below: ONE call, CkksPlan.BfvInnerSum (log2(N) - 1 column rotations and the row rotation, each
+//	                                   added to the running sum) instead of about 3 calls per step
+//	keep    Relinearize :512, SwitchKeys :539, the rotation front ends :560-634 and :669-687, Add / Sub / Neg / MulScalar (Context
 //	        methods)
 package bfv
 
@@ -182,5 +186,43 @@ func (evaluator *evaluator) relinearize(ct0 *Ciphertext, evakey *EvaluationKey, 
 func (evaluator *evaluator) permute(ct0 *Ciphertext, generator uint64, switchKey *SwitchingKey, ctOut *Ciphertext) {
 	evaluator.resident(ct0.value[0], ct0.value[1], ctOut.value[0], ctOut.value[1])
 	evaluator.dev().ks.BfvPermute([2]*ring.Poly{ct0.value[0], ct0.value[1]}, generator, evaluator.keyImage(switchKey),
+		[2]*ring.Poly{ctOut.value[0], ctOut.value[1]})
+}
+
+// rotateColumnsPow2 (:637): the power-of-two rotations at the set bits of k as one chain on the device.
+func (evaluator *evaluator) rotateColumnsPow2(ct0 *Ciphertext, generator, k uint64, evakeyRotCol map[uint64]*SwitchingKey, ctOut *Ciphertext) {
+	mask := (evaluator.bfvContext.n << 1) - 1
+	var generators []uint64
+	var keys []*ring.Poly
+	for evakeyIndex := uint64(1); k > 0; evakeyIndex, k = evakeyIndex<<1, k>>1 {
+		if k&1 == 1 {
+			generators = append(generators, generator)
+			keys = append(keys, evaluator.keyImage(evakeyRotCol[evakeyIndex])) // (a missing key: upstream's nil dereference in switchKeys, :762)
+		}
+		generator *= generator
+		generator &= mask
+	}
+	evaluator.resident(ct0.value[0], ct0.value[1], ctOut.value[0], ctOut.value[1])
+	evaluator.dev().ks.BfvRotateChain([2]*ring.Poly{ct0.value[0], ct0.value[1]}, generators, keys, false,
+		[2]*ring.Poly{ctOut.value[0], ctOut.value[1]})
+}
+
+// InnerSum (:691): the column rotations by 2^i added up, then the row rotation, as one call.
+func (evaluator *evaluator) InnerSum(ct0 *Ciphertext, evakey *RotationKeys, ctOut *Ciphertext) {
+	if ct0.Degree() != 1 || ctOut.Degree() != 1 {
+		panic("cannot InnerSum: input and output must be of degree 1")
+	}
+	var colKeys []*ring.Poly
+	for i := uint64(1); i < evaluator.bfvContext.n>>1; i <<= 1 {
+		if evakey.evakeyRotColLeft[i] == nil { // RotateColumns (:593-619) without the key of the rotation: the pow2 set lacks it as well
+			panic("cannot RotateColumns: specific rotation and pow2 rotations have not been generated")
+		}
+		colKeys = append(colKeys, evaluator.keyImage(evakey.evakeyRotColLeft[i]))
+	}
+	if evakey.evakeyRotRow == nil { // RotateRows (:675-677)
+		panic("cannot RotateRows: rotation key not generated")
+	}
+	evaluator.resident(ct0.value[0], ct0.value[1], ctOut.value[0], ctOut.value[1])
+	evaluator.dev().ks.BfvInnerSum([2]*ring.Poly{ct0.value[0], ct0.value[1]}, colKeys, evaluator.keyImage(evakey.evakeyRotRow),
 		[2]*ring.Poly{ctOut.value[0], ctOut.value[1]})
 }

@@ -194,6 +194,60 @@ func (p *CkksPlan) BfvPermute(ct0 [2]*Poly, generator uint64, switchKey *Poly, c
 	done(ctOut[0], ctOut[1])
 }
 
+// polyTable fills C memory with the handles of ps for the duration of one call (a go 1.13 cgo caller may not keep Go pointers in a C
+// array: these are C handles); the caller frees it.  nil for no polys.
+func polyTable(ps []*Poly) **C.lr_poly {
+	if len(ps) == 0 {
+		return nil
+	}
+	raw := C.malloc(C.size_t(len(ps)) * C.size_t(unsafe.Sizeof(uintptr(0))))
+	arr := polyArray(raw, len(ps))
+	for i, q := range ps {
+		if q != nil {
+			arr[i] = q.d
+		} else {
+			arr[i] = nil
+		}
+	}
+	return (**C.lr_poly)(raw)
+}
+
+// BfvRotateChain = a chain of bfv evaluator.permute steps (bfv/evaluator.go:711-735) as ONE call: step i rotates the running ciphertext by
+// the Galois element generators[i] under switchKeys[i] and replaces it (accumulate false: the loop of rotateColumnsPow2, :653-665) or is
+// added to it (accumulate true: the loop of InnerSum, :701-707); ctOut may be ct0; no step copies.
+func (p *CkksPlan) BfvRotateChain(ct0 [2]*Poly, generators []uint64, switchKeys []*Poly, accumulate bool, ctOut [2]*Poly) {
+	p.contextQ.use(ct0[0], ct0[1])
+	p.contextQ.want(ctOut[0], ctOut[1])
+	n := len(generators)
+	keys := polyTable(switchKeys)
+	defer C.free(unsafe.Pointer(keys))
+	var gens *C.uint64_t
+	if n > 0 {
+		gens = (*C.uint64_t)(unsafe.Pointer(&generators[0]))
+	}
+	acc := C.int(0)
+	if accumulate {
+		acc = 1
+	}
+	call(func() C.int {
+		return C.lr_bfv_rotate_chain(p.h, ct0[0].d, ct0[1].d, C.int(n), gens, keys, acc, ctOut[0].d, ctOut[1].d)
+	})
+	done(ctOut[0], ctOut[1])
+}
+
+// BfvInnerSum = bfv evaluator.InnerSum (bfv/evaluator.go:691-708) as ONE call: colKeys[i] = the image of evakeyRotColLeft[2^i] for
+// i = 0 .. log2(N) - 2, rowKey = the image of evakeyRotRow; the Galois elements are computed by the library; ctOut may be ct0.
+func (p *CkksPlan) BfvInnerSum(ct0 [2]*Poly, colKeys []*Poly, rowKey *Poly, ctOut [2]*Poly) {
+	p.contextQ.use(ct0[0], ct0[1])
+	p.contextQ.want(ctOut[0], ctOut[1])
+	keys := polyTable(colKeys)
+	defer C.free(unsafe.Pointer(keys))
+	call(func() C.int {
+		return C.lr_bfv_inner_sum(p.h, ct0[0].d, ct0[1].d, C.int(len(colKeys)), keys, rowKey.d, ctOut[0].d, ctOut[1].d)
+	})
+	done(ctOut[0], ctOut[1])
+}
+
 // CkksBatcher merges the MulRelin calls of the evaluators of many goroutines -- upstream's concurrency model is one evaluator per
 // goroutine, one ciphertext per call (examples/dbfv/psi/psi.go:215-233) -- into batched device launches (lr_ckks_batcher_* in
 // lattigo_ring.h).  One batcher per parameter set, shared by the evaluators; each lane is a plan over its own pair of contexts.

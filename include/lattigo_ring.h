@@ -395,6 +395,30 @@ int lr_bfv_relinearize(lr_ckks_plan *plan, const lr_poly *c0, const lr_poly *c1,
  * domain; (out_c0, out_c1) may be (c0, c1); out_c0 != out_c1. */
 int lr_bfv_rotate(lr_ckks_plan *plan, const lr_poly *c0, const lr_poly *c1, uint64_t gen, const lr_poly *rotkey,
                   lr_poly *out_c0, lr_poly *out_c1);
+/* A chain of bfv.evaluator.permute steps as ONE call (rotateColumnsPow2, bfv/evaluator.go:637-666, and the loop of InnerSum, :701-707).
+ * The state (a0, a1) starts as (c0, c1); step i = 0 .. n_steps - 1, with Galois element gens[i] and key image keys[i], is permute
+ * (:711-733): (e0, e1) = Permute of both components by gens[i]; (p0, p1) = switchKeys(e1, keys[i]); (r0, r1) = (CRed(e0 + p0), p1); then
+ *   accumulate == 0:  (a0, a1) <- (r0, r1)                               rotateColumnsPow2 :653-665 (gens: the generator's squarings at the
+ *                                                                        set bits of k, keys: evakeyRotCol[2^i] of those bits)
+ *   accumulate != 0:  (a0, a1) <- (CRed(r0 + a0), CRed(r1 + a1))         InnerSum :702-703, :706-707
+ * and (out_c0, out_c1) <- the last state; bit for bit the reference's call sequence.  Every poly over all of Q, coefficient domain,
+ * inputs in [0, q); any batch up to the plan's max_batch; (out_c0, out_c1) may be (c0, c1), an input that is not an output is left
+ * unchanged; one key handle may serve several steps; n_steps == 0 copies (gens and keys may then be NULL).
+ * Checks, in this order: LR_ERR_ARG for a null argument or a null entry of keys, n_steps < 0, an even Galois element, out_c0 and out_c1
+ * the same poly; then LR_ERR_SHAPE for a batch beyond max_batch, a poly with fewer limbs than Q, of another degree or another batch.
+ * Nothing is written by a refused call.  Each step is the key switch plus one fused pass where a coefficient row fits
+ * the LDS (2^11 <= N <= 2^14); other degrees, plans or contexts with lr_options::no_epilogue, and the replacing chain of a single
+ * ciphertext at N = 2^14 (measured) run the step from the separate Permute / Add launches.  Same bits on every route.
+ * The plan keeps four more polys over Q per batch member for its chains. */
+int lr_bfv_rotate_chain(lr_ckks_plan *plan, const lr_poly *c0, const lr_poly *c1, int n_steps, const uint64_t *gens,
+                        const lr_poly *const *keys, int accumulate, lr_poly *out_c0, lr_poly *out_c1);
+/* bfv.evaluator.InnerSum (bfv/evaluator.go:691-708): the accumulating chain over galElRotColLeft[2^i] = 5^(2^i) mod 2N with
+ * col_keys[i] = the image of evakeyRotColLeft[2^i], i = 0 .. log2(N) - 2, and then galElRotRow = 2N - 1 with row_key; the Galois
+ * elements are computed here.  N = 2 has no column step (n_col_keys == 0, col_keys may be NULL).  Polys, batch, aliasing and routes as
+ * for lr_bfv_rotate_chain.  Checks, in this order: LR_ERR_ARG for a null argument or a null entry of col_keys, out_c0 and out_c1 the
+ * same poly, n_col_keys != log2(N) - 1; then the LR_ERR_SHAPE checks of lr_bfv_rotate_chain. */
+int lr_bfv_inner_sum(lr_ckks_plan *plan, const lr_poly *c0, const lr_poly *c1, int n_col_keys, const lr_poly *const *col_keys,
+                     const lr_poly *row_key, lr_poly *out_c0, lr_poly *out_c1);
 /* MulRelin (ckks/evaluator.go:1016), ciphertext x ciphertext, with evaluation key.
  * ct0_c0/ct0_c1 etc. are the degree-0/1 components (Ciphertext.Value()[0], [1]). */
 int lr_ckks_mulrelin(lr_ckks_plan *plan, int level, const lr_poly *ct0_c0, const lr_poly *ct0_c1,

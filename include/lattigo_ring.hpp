@@ -188,6 +188,58 @@ class SimpleScaler {
     lr_simple_scaler *h_ = nullptr;
 };
 
+// The BFV rotations of the key-switch plan over (contextQ, contextP) -- what bfv.NewEvaluator builds for them (decomposer,
+// baseconverterQ1P, keyswitchpool: bfv/evaluator.go:100-112) is an lr_ckks_plan.  Ciphertexts are pairs of Polys over Q in the
+// coefficient domain, keys the images of SwitchingKey.evakey; an output pair may be the input pair.
+class BfvRotator {
+  public:
+    BfvRotator(const Context *contextQ, const Context *contextP, int max_batch = 1, const lr_options *options = nullptr) : N_(contextQ->N) {
+        check(lr_ckks_plan_create_ex(contextQ->handle(), contextP->handle(), max_batch, options, &h_));
+    }
+    ~BfvRotator() { lr_ckks_plan_destroy(h_); }
+    BfvRotator(const BfvRotator &) = delete;
+    BfvRotator &operator=(const BfvRotator &) = delete;
+    // evaluator.permute (:711): RotateRows, RotateColumns with the key of the rotation
+    void Permute(const Poly *c0, const Poly *c1, uint64_t generator, const Poly *switchKey, Poly *out0, Poly *out1) {
+        check(lr_bfv_rotate(h_, c0->handle(), c1->handle(), generator, switchKey->handle(), out0->handle(), out1->handle()));
+    }
+    // a chain of permute steps as one call: replaced by each rotation (rotateColumnsPow2 :637) or added to it (InnerSum's loop :701)
+    void RotateChain(const Poly *c0, const Poly *c1, const std::vector<uint64_t> &generators, const std::vector<const Poly *> &switchKeys,
+                     bool accumulate, Poly *out0, Poly *out1) {
+        if (generators.size() != switchKeys.size()) throw Error(LR_ERR_ARG, "RotateChain: one key per Galois element");
+        const std::vector<const lr_poly *> keys = handles(switchKeys);
+        check(lr_bfv_rotate_chain(h_, c0->handle(), c1->handle(), (int)generators.size(), generators.data(), keys.data(), accumulate ? 1 : 0,
+                                  out0->handle(), out1->handle()));
+    }
+    // rotateColumnsPow2(ct0, generator, k, evakeyRotCol, ctOut) with pow2Keys[i] = the image of evakeyRotCol[2^i]
+    void RotateColumnsPow2(const Poly *c0, const Poly *c1, uint64_t generator, uint64_t k, const std::vector<const Poly *> &pow2Keys, Poly *out0,
+                           Poly *out1) {
+        std::vector<uint64_t> generators;
+        std::vector<const Poly *> keys;
+        for (size_t i = 0; k > 0; ++i, k >>= 1, generator = (generator * generator) & (2 * N_ - 1))
+            if (k & 1) {
+                generators.push_back(generator);
+                keys.push_back(i < pow2Keys.size() ? pow2Keys[i] : nullptr);
+            }
+        RotateChain(c0, c1, generators, keys, false, out0, out1);
+    }
+    // evaluator.InnerSum (:691): colKeys[i] = the image of evakeyRotColLeft[2^i], i = 0 .. log2(N) - 2; rowKey = the image of evakeyRotRow
+    void InnerSum(const Poly *c0, const Poly *c1, const std::vector<const Poly *> &colKeys, const Poly *rowKey, Poly *out0, Poly *out1) {
+        const std::vector<const lr_poly *> keys = handles(colKeys);
+        check(lr_bfv_inner_sum(h_, c0->handle(), c1->handle(), (int)colKeys.size(), keys.data(), rowKey ? rowKey->handle() : nullptr,
+                               out0->handle(), out1->handle()));
+    }
+
+  private:
+    static std::vector<const lr_poly *> handles(const std::vector<const Poly *> &ps) {
+        std::vector<const lr_poly *> raw;
+        for (const Poly *p : ps) raw.push_back(p ? p->handle() : nullptr);
+        return raw;
+    }
+    uint64_t N_;
+    lr_ckks_plan *h_ = nullptr;
+};
+
 // bfv.Encoder (bfv/encoder.go:10-182) for batches of plaintexts; slots are [batch][n] host arrays, plaintexts Polys over contextQ
 class BfvEncoder {
   public:

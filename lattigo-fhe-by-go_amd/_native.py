@@ -115,6 +115,8 @@ SYMBOLS = {
     "lr_bfv_switch_keys": [vp, vp, vp, vp, vp],
     "lr_bfv_relinearize": [vp, vp, vp, vp, vp, vp, vp],
     "lr_bfv_rotate": [vp, vp, vp, u64, vp, vp, vp],
+    "lr_bfv_rotate_chain": [vp, vp, vp, i32, u64p, C.POINTER(vp), i32, vp, vp],
+    "lr_bfv_inner_sum": [vp, vp, vp, i32, C.POINTER(vp), vp, vp, vp],
     "lr_ckks_mulrelin": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
     "lr_ckks_batcher_create": [vp, i32, vp],
     "lr_ckks_batcher_destroy": [vp],

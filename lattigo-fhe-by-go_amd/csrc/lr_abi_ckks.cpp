@@ -538,7 +538,7 @@ extern "C" int lr_ckks_switch_keys(lr_ckks_plan *pl, int level, const lr_poly *c
 // bfv.evaluator.switchKeys (bfv/evaluator.go:736-812): cx in the coefficient domain over all of Q, evk over Q||P in the NTT +
 // Montgomery domain like the reference's SwitchingKey; p0 / p1 <- the two key-switched polys over Q, coefficient domain.  Same
 // machinery as the CKKS key switch (one plan over contextQ / contextP serves both), with the transforms the other way round.
-static int bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc) {
+int lr_host::bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc) {
     const int level = pl->cQ->h.L() - 1;
     LR_TRY(ks_decompose(pl, level, batch, cx, cx_stride, KsInput::Coeff));
     const long long sQ = (long long)pl->cQ->h.L() * (long long)pl->cQ->h.N;

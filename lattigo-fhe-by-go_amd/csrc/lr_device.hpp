@@ -336,6 +336,38 @@ struct GaloisLaunch {
     const u64 *const *in_table = nullptr;   // batcher form: batch poly b is read from in_table[b] (in / in_stride unused)
 };
 hipError_t launch_permute(const GaloisLaunch &L, int limbs, int batch, hipStream_t stream);
+// the degrees whose coefficient-domain rows one workgroup holds in LDS (permute_coeff_lds_kernel, bfv_chain_step_kernel): 128 KiB of the
+// CU's 160 at N = 2^14; below 2^11 a row is too short to pay for a workgroup of its own
+inline bool lds_row_degree(int logn) { return logn >= 11 && logn <= 14; }
+// g^-1 modulo 2N for an odd g (Newton's iteration doubles the correct low bits): output j of Context.Permute is input (j * g^-1 mod 2N) mod N
+inline u32 galois_inverse(u64 gen, int n) {
+    const u32 mask2 = 2u * (u32)n - 1u, g = (u32)gen & mask2;
+    u32 inv = g;
+    for (int it = 0; it < 5; ++it) inv *= 2u - g * inv;
+    return inv & mask2;
+}
+
+// One step of a BFV rotation chain after its key switch (lr_bfv_rotate_chain, lr_bfv_inner_sum; bfv/evaluator.go:711-733 followed by
+// InnerSum's Add :703 / :707, or nothing for rotateColumnsPow2 :657): see bfv_chain_step_kernel.  Coefficient domain, all of Q.
+struct BfvChainStepLaunch {
+    const u64 *a0, *a1;      // the chain's state before the step
+    long long a0_stride, a1_stride;
+    const u64 *p0, *p1;      // switchKeys(Permute(a1, g)): the key switch's two results
+    long long p_stride;
+    u64 *out0, *out1;        // the state after the step; out_k may be p_k or a_k (the pass is row-local), never the other component's operand
+    long long out0_stride, out1_stride;
+    u64 *cx_next;            // Permute(out1, g'), the next step's key-switch input; nullptr: the last step
+    long long cx_stride;
+    int n, logn;
+    u32 ginv, ginv_next;     // g^-1, g'^-1 modulo 2N (galois_inverse)
+    int accumulate;          // 1: InnerSum (the state is added to the rotation), 0: rotateColumnsPow2 (replaced by it)
+    const LimbParams *lp;
+};
+inline LaunchVerdict launch_verdict(const BfvChainStepLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, !lds_row_degree(L.logn) || (1 << L.logn) != L.n || limbs > kMaxLimbs || batch > 65535 || !(L.ginv & 1u) ||
+                                                        (L.cx_next && !(L.ginv_next & 1u)) || L.out0 == L.out1);
+}
+hipError_t launch_bfv_chain_step(const BfvChainStepLaunch &L, int limbs, int batch, hipStream_t stream);
 // Context.MultByMonomial (ring/ring.go:663): out = in * X^shift in Z_q[X]/(X^N+1), shift already reduced modulo 2N;
 // like the reference, negated coefficients are q - x without reduction (0 becomes q).  Not in place.
 hipError_t launch_monomial(const GaloisLaunch &L, int limbs, int batch, hipStream_t stream);

@@ -867,29 +867,89 @@ __global__ __launch_bounds__(1024) void permute_coeff_lds_kernel(GaloisLaunch L,
     }
 }
 
+// more than 64 KiB of dynamic LDS is an attribute of the function ON THE CURRENT DEVICE: asked for once per device of the process
+// (state: 0 = not asked yet, 1 = granted, 2 = refused)
+static bool lds_row_granted(const void *kernel, std::atomic<int> (&lds_ok)[64]) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::atomic<int> &state = lds_ok[dev >= 0 && dev < 64 ? dev : 0];
+    if (state.load(std::memory_order_acquire) == 0)
+        state.store(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess ? 1 : 2, std::memory_order_release);
+    return state.load(std::memory_order_acquire) == 1;
+}
+
 hipError_t launch_permute(const GaloisLaunch &L, int limbs, int batch, hipStream_t stream) {
     if (limbs <= 0 || batch <= 0) return hipSuccess;
-    if (!L.ntt_domain && !L.in_table && (L.gen & 1) && L.logn >= 11 && L.logn <= 14 && batch <= 65535) {
-        // gen^-1 modulo 2N (gen odd): Newton's iteration doubles the correct low bits
-        const u32 mask2 = 2u * (u32)L.n - 1u, g = (u32)L.gen & mask2;
-        u32 inv = g;
-        for (int it = 0; it < 5; ++it) inv *= 2u - g * inv;
-        inv &= mask2;
-        const size_t lds = (size_t)L.n * sizeof(u64);
-        // more than 64 KiB of dynamic LDS is an attribute of the function ON THE CURRENT DEVICE: asked for once per device of the process
-        static std::atomic<int> lds_ok[64];      // 0 = not asked yet, 1 = granted, 2 = refused
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::atomic<int> &state = lds_ok[dev >= 0 && dev < 64 ? dev : 0];
-        if (state.load(std::memory_order_acquire) == 0)
-            state.store(hipFuncSetAttribute(reinterpret_cast<const void *>(permute_coeff_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess ? 1 : 2,
-                        std::memory_order_release);
-        if (state.load(std::memory_order_acquire) == 1) {
-            return launch_kernel(permute_coeff_lds_kernel, dim3((unsigned)limbs, (unsigned)batch), dim3(1024), lds, stream, L, inv);
+    if (!L.ntt_domain && !L.in_table && (L.gen & 1) && lds_row_degree(L.logn) && batch <= 65535) {
+        static std::atomic<int> lds_ok[64];
+        if (lds_row_granted(reinterpret_cast<const void *>(permute_coeff_lds_kernel), lds_ok)) {
+            return launch_kernel(permute_coeff_lds_kernel, dim3((unsigned)limbs, (unsigned)batch), dim3(1024), (size_t)L.n * sizeof(u64), stream, L,
+                                 galois_inverse(L.gen, L.n));
         }
         (void)hipGetLastError();     // (the attribute was refused: the scatter form below)
     }
     return launch_kernel(permute_kernel, coeff_grid(L.n, (unsigned)limbs, (unsigned)batch), dim3(256), 0, stream, L);
+}
+
+// One step of a BFV rotation chain after its key switch, as ONE pass (BfvChainStepLaunch): what bfv.evaluator.permute does after
+// switchKeys (Add :731, Copy :732), InnerSum's Add of the rotation to the running sum (:703 / :707), and the two Context.Permute calls
+// (:723-724) -- the one of THIS step's first component and the one of the NEXT step's second.  One workgroup per (limb, batch member,
+// component) row, the row in LDS as in permute_coeff_lds_kernel; g = this step's Galois element, g' the next one's:
+//   component 0:  a0 row -> LDS;  out0[j] = CRed(CRed(+-a0[j g^-1] + p0[j]) + a0[j])          (replace: without "+ a0[j]")
+//   component 1:  out1[j] = CRed(p1[j] + a1[j]) -> memory and LDS;  cx_next[j] = +-out1[j g'^-1]   (replace: out1 = p1; last step: no cx_next)
+// +-x is x where (j g^-1 mod 2N) < N and q - x otherwise, a zero becoming q (ring_galois.go:119-124, neg2's convention); the inner CRed
+// is Context.Add's at :731 and stays where the reference has it.  out0[j] reads p0[j], a0[j] and the LDS copy only, out1[j] reads p1[j]
+// and a1[j]: out_k may be p_k (the key switch's accumulators) or a_k.  7 row passes per step (3 + 4; replace 3 + 3, or 3 + 2 with out1 = p1
+// in place) against 13 in five launches for Permute x2, Add, Add x2.
+__global__ __launch_bounds__(1024) void bfv_chain_step_kernel(BfvChainStepLaunch L) {
+    extern __shared__ u64 lr_chain_row[];
+    const int limb = blockIdx.x;
+    const long long b = blockIdx.y, row = (long long)limb * L.n;
+    const u32 n = (u32)L.n, mask2 = 2 * n - 1;
+    const u64 q = L.lp[limb].q;
+    if (blockIdx.z == 0) {
+        const ulonglong2 *pa = row_in(L.a0, b, L.a0_stride, row), *pp = row_in(L.p0, b, L.p_stride, row);
+        ulonglong2 *po = row_out(L.out0, b, L.out0_stride, row);
+        for (u32 e = threadIdx.x; e < n / 2; e += 1024) {
+            const ulonglong2 v = ld_stream(pa + e);
+            lr_chain_row[2 * e] = v.x;
+            lr_chain_row[2 * e + 1] = v.y;
+        }
+        __syncthreads();
+        for (u32 e = threadIdx.x; e < n / 2; e += 1024) {
+            const u32 t0 = ((2 * e) * L.ginv) & mask2, t1 = ((2 * e + 1) * L.ginv) & mask2;
+            const u64 x0 = lr_chain_row[t0 & (n - 1)], x1 = lr_chain_row[t1 & (n - 1)];
+            ulonglong2 r = add2(make_ulonglong2(t0 >= n ? q - x0 : x0, t1 >= n ? q - x1 : x1), ld_stream(pp + e), q);       // :723, :731
+            if (L.accumulate) r = add2(r, make_ulonglong2(lr_chain_row[2 * e], lr_chain_row[2 * e + 1]), q);                // InnerSum :703 / :707
+            st_stream(po + e, r);
+        }
+        return;
+    }
+    const ulonglong2 *pa = row_in(L.a1, b, L.a1_stride, row), *pp = row_in(L.p1, b, L.p_stride, row);
+    ulonglong2 *po = row_out(L.out1, b, L.out1_stride, row);
+    const bool store = L.accumulate || L.out1 != L.p1;      // (replace, in place over the accumulator: out1 is p1 already, :732)
+    for (u32 e = threadIdx.x; e < n / 2; e += 1024) {
+        ulonglong2 r = ld_stream(pp + e);
+        if (L.accumulate) r = add2(r, ld_stream(pa + e), q);                                                                // InnerSum :703 / :707
+        if (store) st_stream(po + e, r);
+        lr_chain_row[2 * e] = r.x;
+        lr_chain_row[2 * e + 1] = r.y;
+    }
+    if (!L.cx_next) return;
+    __syncthreads();
+    ulonglong2 *pc = row_out(L.cx_next, b, L.cx_stride, row);
+    for (u32 e = threadIdx.x; e < n / 2; e += 1024) {
+        const u32 t0 = ((2 * e) * L.ginv_next) & mask2, t1 = ((2 * e + 1) * L.ginv_next) & mask2;
+        const u64 x0 = lr_chain_row[t0 & (n - 1)], x1 = lr_chain_row[t1 & (n - 1)];
+        st_stream(pc + e, make_ulonglong2(t0 >= n ? q - x0 : x0, t1 >= n ? q - x1 : x1));                                   // the next step's :724
+    }
+}
+
+hipError_t launch_bfv_chain_step(const BfvChainStepLaunch &L, int limbs, int batch, hipStream_t stream) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    static std::atomic<int> lds_ok[64];
+    if (!lds_row_granted(reinterpret_cast<const void *>(bfv_chain_step_kernel), lds_ok)) return hipErrorNotSupported;
+    return launch_kernel(bfv_chain_step_kernel, dim3((unsigned)limbs, (unsigned)batch, 2), dim3(1024), (size_t)L.n * sizeof(u64), stream, L);
 }
 
 }  // namespace lr

@@ -378,6 +378,7 @@ struct lr_ckks_plan {
     Pool c2QiQ, c2QiP, poolPP, c2, c0, c1, c2x, q1, q2, permQ, permP;
     Pool encQ, encP;       // pk-encryption temporaries over Q||P (lr_ckks_encrypt_pk)
     Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q)
+    Pool chainP;           // bfv rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_bfv_chain.cpp)
     Pool zerosQ;           // one poly of zeros over Q: the `plus` operand of the NTT epilogue where a caller has none
     Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_plan_decomposition)
     // small batches: independent launches of one pipeline side by side (PlanFork); stream and events are created at the first fork
@@ -613,6 +614,7 @@ int decompose_core(lr_decomposer *d, int level, int crt, Rows in, int batch, Row
 std::atomic<int> &standalone_plans(int device);
 int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride, u64 gen, const u64 *const *in_table = nullptr);
 int switch_keys_core(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc, const KeySwitchEpilogue *fin = nullptr);
+int bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc);
 int check_ct(const lr_ckks_plan *pl, int level, const lr_poly *p, int batch);
 int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride);
 

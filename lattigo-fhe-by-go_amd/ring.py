@@ -623,6 +623,37 @@ class CkksPlan:
             idx <<= 1
             k >>= 1
 
+    def BfvRotateChain(self, ct0, generators, switchKeys, accumulate, ctOut):
+        """a chain of bfv.evaluator.permute steps as one call (lr_bfv_rotate_chain): step i rotates the running ciphertext by the Galois
+        element generators[i] under switchKeys[i] and replaces it (accumulate False: rotateColumnsPow2, bfv/evaluator.go:637-666) or is
+        added to it (True: InnerSum's loop, :701-707); ctOut may be ct0; no step copies"""
+        n = len(generators)
+        if len(switchKeys) != n:
+            raise ValueError("one key per Galois element")
+        g = (C.c_uint64 * max(n, 1))(*[int(x) for x in generators])
+        keys = (C.c_void_p * max(n, 1))(*[k.h.value if k is not None else None for k in switchKeys])
+        check(lib().lr_bfv_rotate_chain(self.h, ct0[0].h, ct0[1].h, n, g, keys, 1 if accumulate else 0, ctOut[0].h, ctOut[1].h))
+
+    def BfvRotateColumnsPow2Chain(self, ct0, generator, k, pow2_keys, ctOut):
+        """BfvRotateColumnsPow2 as ONE call: the set bits of k become the steps of a replace chain"""
+        mask = (self.contextQ.N << 1) - 1
+        gens, keys, idx = [], [], 1
+        while k > 0:
+            if k & 1:
+                gens.append(generator)
+                keys.append(pow2_keys[idx])
+            generator = (generator * generator) & mask
+            idx <<= 1
+            k >>= 1
+        self.BfvRotateChain(ct0, gens, keys, False, ctOut)
+
+    def BfvInnerSum(self, ct0, col_keys, row_key, ctOut):
+        """bfv.evaluator.InnerSum (bfv/evaluator.go:691-708) as one call (lr_bfv_inner_sum): col_keys[i] = the image of
+        evakeyRotColLeft[2^i], i = 0 .. log2(N) - 2; row_key = the image of evakeyRotRow; ctOut may be ct0"""
+        n = len(col_keys)
+        keys = (C.c_void_p * max(n, 1))(*[k.h.value if k is not None else None for k in col_keys])
+        check(lib().lr_bfv_inner_sum(self.h, ct0[0].h, ct0[1].h, n, keys, row_key.h if row_key is not None else None, ctOut[0].h, ctOut[1].h))
+
     def MulRelin(self, level, ct0, ct1, evakey, ctOut):
         """evaluator.MulRelin (ckks/evaluator.go:1016).  ct0, ct1: tuples of Poly -- (value[0], value[1]) for a ciphertext,
         (value[0],) for a plaintext; ctOut: pair, or triple when evakey is None and both operands are ciphertexts
