@@ -13,7 +13,7 @@
 //	                                   through upstream's tensorAndRescale (:278-464, kept) on host views -- its copy loop into
 //	                                   polyBig (:430-436) indexes Coeffs
 //	delete  relinearize  :480-501   -> below: degree 2 is ONE call, CkksPlan.BfvRelinearize (key switch + the two Adds); higher degrees
-//	                                   keep upstream's loop over switchKeys
+//	                                   are ONE call as well, CkksPlan.BfvRelinearizeDeg (the key switches of all degrees merged)
 //	delete  switchKeys   :736-812   -> below: CkksPlan.BfvSwitchKeys (the per-modulus loops over Coeffs at :776-792 live inside the pipeline)
 //	delete  permute      :711-735   -> below: ONE call, CkksPlan.BfvPermute (Context.Permute x2, the key switch, Add, Copy); RotateRows
 //	                                   and RotateColumns with the key of the rotation (:579-681, kept) reach the device through it
@@ -169,16 +169,16 @@ func (evaluator *evaluator) relinearize(ct0 *Ciphertext, evakey *EvaluationKey, 
 		ctOut.SetValue(ctOut.value[:2])
 		return
 	}
-	if ctOut != ct0 {
-		context.Copy(ct0.value[0], ctOut.value[0])
-		context.Copy(ct0.value[1], ctOut.value[1])
+	// degree > 2 (:494-498): every degree's key switch and its two Adds as ONE call, the highest degree first; the key switches' results
+	// stay in the plan's pool on the device (upstream's keyswitchpool[2], [3] of :489-490 are not touched)
+	degree := int(ct0.Degree())
+	keys := make([]*ring.Poly, 0, degree-1)
+	for deg := 2; deg <= degree; deg++ {
+		keys = append(keys, evaluator.keyImage(evakey.evakey[deg-2])) // (a missing key: upstream's nil dereference in switchKeys, :762)
 	}
-	p0, p1 := evaluator.keyswitchpool[2], evaluator.keyswitchpool[3]
-	for deg := uint64(ct0.Degree()); deg > 1; deg-- {
-		evaluator.switchKeys(ct0.value[deg], evakey.evakey[deg-2], p0, p1)
-		context.Add(ctOut.value[0], p0, ctOut.value[0])
-		context.Add(ctOut.value[1], p1, ctOut.value[1])
-	}
+	evaluator.resident(ct0.value...)
+	evaluator.resident(ctOut.value[0], ctOut.value[1])
+	evaluator.dev().ks.BfvRelinearizeDeg(ct0.value[:degree+1], keys, [2]*ring.Poly{ctOut.value[0], ctOut.value[1]})
 	ctOut.SetValue(ctOut.value[:2])
 }
 

@@ -235,6 +235,22 @@ func (p *CkksPlan) BfvRotateChain(ct0 [2]*Poly, generators []uint64, switchKeys 
 	done(ctOut[0], ctOut[1])
 }
 
+// BfvRelinearizeDeg = bfv evaluator.relinearize for a ciphertext of any degree len(ct) - 1 <= 5 (bfv/evaluator.go:480-499) as ONE call:
+// evakeys[k] = the image of evakey.evakey[k], the key that switches from s^(k+2); the additions keep upstream's order, the highest degree
+// first; ctOut may be (ct[0], ct[1]).
+func (p *CkksPlan) BfvRelinearizeDeg(ct []*Poly, evakeys []*Poly, ctOut [2]*Poly) {
+	p.contextQ.use(ct...)
+	p.contextQ.want(ctOut[0], ctOut[1])
+	cts := polyTable(ct)
+	defer C.free(unsafe.Pointer(cts))
+	keys := polyTable(evakeys)
+	defer C.free(unsafe.Pointer(keys))
+	call(func() C.int {
+		return C.lr_bfv_relinearize_deg(p.h, cts, C.int(len(ct)-1), keys, ctOut[0].d, ctOut[1].d)
+	})
+	done(ctOut[0], ctOut[1])
+}
+
 // BfvInnerSum = bfv evaluator.InnerSum (bfv/evaluator.go:691-708) as ONE call: colKeys[i] = the image of evakeyRotColLeft[2^i] for
 // i = 0 .. log2(N) - 2, rowKey = the image of evakeyRotRow; the Galois elements are computed by the library; ctOut may be ct0.
 func (p *CkksPlan) BfvInnerSum(ct0 [2]*Poly, colKeys []*Poly, rowKey *Poly, ctOut [2]*Poly) {

@@ -389,6 +389,26 @@ int lr_bfv_switch_keys(lr_ckks_plan *plan, const lr_poly *cx, const lr_poly *evk
  * (p0, p1) = switchKeys(c2, evakey.evakey[0]); every poly over Q, coefficient domain; out0 / out1 may be c0 / c1. */
 int lr_bfv_relinearize(lr_ckks_plan *plan, const lr_poly *c0, const lr_poly *c1, const lr_poly *c2, const lr_poly *evk,
                        lr_poly *out0, lr_poly *out1);
+/* bfv.evaluator.Relinearize for every degree (bfv/evaluator.go:480-499, 509-522) as ONE call:
+ *   (a0, a1) = (ct[0], ct[1]);  for deg = degree .. 2:  (p0, p1) = switchKeys(ct[deg], evks[deg - 2]);
+ *   a0 = CRed(a0 + p0); a1 = CRed(a1 + p1);   (out0, out1) <- (a0, a1)
+ * bit for bit the reference's loop.  ct[0 .. degree] over all of Q, coefficient domain, one batch up to the plan's max_batch; evks[k] =
+ * the image of evakey.evakey[k], the key that switches from s^(k + 2), in the layout lr_ckks_switch_keys reads (what
+ * lr_keygen_relin_keys with n_powers = maxDegree, lr_setup_rkg_key and NewSwitchingKey().set produce).  1 <= degree <= 5, the reach of
+ * lr_bfv_mul_deg; degree 1 copies (evks may then be NULL); degree 2 gives the bits of lr_bfv_relinearize.  The additions keep the
+ * reference's order, the highest degree first, each with one conditional subtraction: the result is the composed sequence's for any
+ * input lr_ewise ADD accepts, not only canonical ones.  out0 may be ct[0] and out1 may be ct[1]; an input that is not an output is left
+ * unchanged.
+ * Checks, in this order: LR_ERR_ARG for a null argument, a null entry of ct or, for degree >= 2, a null evks or a null entry of evks, a
+ * degree outside 1 .. 5, out0 and out1 the same poly, an output that is ct[k] for k >= 2, out0 being ct[1] or out1 being ct[0] ("the
+ * same poly": the same device rows); then LR_ERR_SHAPE for a batch beyond max_batch, a poly with fewer limbs than Q, of another ring
+ * degree or another batch, a key image with a batch below 2 beta or fewer than |Q| + |P| limbs.  Nothing is written by a refused call.
+ * Routes: the degree - 1 key switches share no data, so G = min(degree - 1, max(1, max_batch / batch)) of them, the
+ * highest degrees first, run as ONE key switch over G * batch members with one key per group, and one pass adds their G results to the
+ * running pair (the plan's scratch stays what a call at max_batch needs); plans or contexts with lr_options::no_epilogue run the
+ * reference's sequence call by call: per degree the key switch and the two Adds of lr_bfv_relinearize.  Same bits on every route. */
+int lr_bfv_relinearize_deg(lr_ckks_plan *plan, const lr_poly *const *ct, int degree, const lr_poly *const *evks, lr_poly *out0,
+                           lr_poly *out1);
 /* bfv.evaluator.permute (bfv/evaluator.go:711-735) = RotateRows (:670) with gen = galElRotRow, RotateColumns (:579) with the key of
  * that rotation and gen = galElRotColLeft[k], and one step of rotateColumnsPow2 (:636): Context.Permute of both components by the
  * Galois element `gen` (coefficient domain), switchKeys of the second with `rotkey`, Add + Copy.  Every poly over Q, coefficient

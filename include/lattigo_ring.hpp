@@ -223,6 +223,13 @@ class BfvRotator {
             }
         RotateChain(c0, c1, generators, keys, false, out0, out1);
     }
+    // evaluator.Relinearize (:509) of a ciphertext of degree ct.size() - 1 <= 5 as one call: evakeys[k] = the image of evakey.evakey[k]
+    // (the key from s^(k + 2)); out0 / out1 may be ct[0] / ct[1]
+    void RelinearizeDeg(const std::vector<const Poly *> &ct, const std::vector<const Poly *> &evakeys, Poly *out0, Poly *out1) {
+        if (ct.size() < 2 || evakeys.size() + 2 < ct.size()) throw Error(LR_ERR_ARG, "RelinearizeDeg: one key per degree above 1");
+        const std::vector<const lr_poly *> cts = handles(ct), keys = handles(evakeys);
+        check(lr_bfv_relinearize_deg(h_, cts.data(), (int)ct.size() - 1, keys.empty() ? nullptr : keys.data(), out0->handle(), out1->handle()));
+    }
     // evaluator.InnerSum (:691): colKeys[i] = the image of evakeyRotColLeft[2^i], i = 0 .. log2(N) - 2; rowKey = the image of evakeyRotRow
     void InnerSum(const Poly *c0, const Poly *c1, const std::vector<const Poly *> &colKeys, const Poly *rowKey, Poly *out0, Poly *out1) {
         const std::vector<const lr_poly *> keys = handles(colKeys);

@@ -114,6 +114,7 @@ SYMBOLS = {
     "lr_ckks_switch_keys": [vp, i32, vp, vp, vp, vp],
     "lr_bfv_switch_keys": [vp, vp, vp, vp, vp],
     "lr_bfv_relinearize": [vp, vp, vp, vp, vp, vp, vp],
+    "lr_bfv_relinearize_deg": [vp, C.POINTER(vp), i32, C.POINTER(vp), vp, vp],
     "lr_bfv_rotate": [vp, vp, vp, u64, vp, vp, vp],
     "lr_bfv_rotate_chain": [vp, vp, vp, i32, u64p, C.POINTER(vp), i32, vp, vp],
     "lr_bfv_inner_sum": [vp, vp, vp, i32, C.POINTER(vp), vp, vp, vp],

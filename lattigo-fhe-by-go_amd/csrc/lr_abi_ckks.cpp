@@ -321,12 +321,21 @@ KeyMacLaunch keymac_p_part(const lr_ckks_plan *pl, KeyMacLaunch K, const KsSizes
     return K;
 }
 
+// The members of a pass that one inner product works on: polys [first, first + count) of its `batch`, under a key of their own (the
+// grouped BFV key switch, bfv_switch_keys_grouped).  The range is base offsets into the digits, `own`, the accumulators and poolPP; the
+// strides stay those of the whole pass.  The default is every member: the launch of a pass under one key.
+struct KsMembers {
+    int first = 0, count = -1;      // count < 0: all `batch` members
+};
+
 // Inner product of the digits with a switching key (:1511-1535 / :1339-1365): acc <- the Q parts, pl->poolPP = [2][batch][|P|][N] <- the
-// P parts of sum over the digits of evakey[i][0/1] (*) c2_i, canonical
-int ks_inner_product(lr_ckks_plan *pl, int level, int batch, const KsDigits &dig, const lr_poly *evk, const KeySwitchAcc &acc) {
+// P parts of sum over the digits of evakey[i][0/1] (*) c2_i, canonical; for the members `mem` of the pass
+int ks_inner_product(lr_ckks_plan *pl, int level, int batch, const KsDigits &dig, const lr_poly *evk, const KeySwitchAcc &acc, KsMembers mem = KsMembers()) {
     lr_context *cQ = pl->cQ;
     const int nQ = cQ->h.L(), nP = pl->cP->h.L();
     const KsSizes z = ks_sizes(pl, level, batch);
+    const long long m0 = mem.first;
+    const int members = mem.count < 0 ? batch : mem.count;
     if (evk->batch < 2 * z.beta || evk->limbs < nQ + nP) return fail(LR_ERR_SHAPE, "evaluation key: need batch >= 2*beta and |Q|+|P| limbs");
     LR_TRY(pl->poolPP.ensure(cQ, (size_t)2 * batch * z.sP));
     KeyMacLaunch KQ;
@@ -334,18 +343,18 @@ int ks_inner_product(lr_ckks_plan *pl, int level, int batch, const KsDigits &dig
     KQ.perm_gen = (unsigned)(dig.perm_gen & ((cQ->h.N << 1) - 1));
     KQ.n = (int)cQ->h.N; KQ.logn = (int)cQ->h.logN; KQ.beta = z.beta;
     KQ.key = evk->d; KQ.key_poly_stride = evk->stride(); KQ.key_limb0 = 0;
-    KQ.c2 = dig.Q; KQ.c2_digit_stride = z.dQ; KQ.c2_poly_stride = z.sQ;
-    KQ.out0 = acc.p[0]; KQ.out1 = acc.p[1]; KQ.out_stride = acc.stride[0]; KQ.out1_stride = acc.stride[1];
+    KQ.c2 = dig.Q + m0 * z.sQ; KQ.c2_digit_stride = z.dQ; KQ.c2_poly_stride = z.sQ;
+    KQ.out0 = acc.p[0] + m0 * acc.stride[0]; KQ.out1 = acc.p[1] + m0 * acc.stride[1]; KQ.out_stride = acc.stride[0]; KQ.out1_stride = acc.stride[1];
     KQ.lp = cQ->d_lp;
     KQ.wide = keymac_wide_ok(pl, cQ, z.beta) ? 1 : 0;
-    KQ.own = dig.own; KQ.own_stride = dig.own_stride; KQ.alpha = dig.own ? pl->dec->alpha : 0;
-    const KeyMacLaunch KP = keymac_p_part(pl, KQ, z, dig.P, pl->poolPP.d, pl->poolPP.d + (long long)batch * z.sP);
+    KQ.own = dig.own ? dig.own + m0 * dig.own_stride : nullptr; KQ.own_stride = dig.own_stride; KQ.alpha = dig.own ? pl->dec->alpha : 0;
+    const KeyMacLaunch KP = keymac_p_part(pl, KQ, z, dig.P + m0 * z.sP, pl->poolPP.d + m0 * z.sP, pl->poolPP.d + ((long long)batch + m0) * z.sP);
     // a small batch: the Q part and the P part as one launch (they share nothing and each is a few hundred workgroups)
     hipError_t pe = hipErrorNotSupported;
-    if (!pl->opt.no_pair && (long long)batch * (level + 1) <= pl->opt.pair_max_workgroups) pe = launch_keymac_pair(KQ, level + 1, KP, nP, batch, cQ->stream);
+    if (!pl->opt.no_pair && (long long)members * (level + 1) <= pl->opt.pair_max_workgroups) pe = launch_keymac_pair(KQ, level + 1, KP, nP, members, cQ->stream);
     if (pe == hipErrorNotSupported) {
-        LR_HIP(launch_keymac(KQ, level + 1, batch, cQ->stream));
-        LR_HIP(launch_keymac(KP, nP, batch, cQ->stream));
+        LR_HIP(launch_keymac(KQ, level + 1, members, cQ->stream));
+        LR_HIP(launch_keymac(KP, nP, members, cQ->stream));
     } else if (pe != hipSuccess) {
         return fail(LR_ERR_HIP, std::string("launch_keymac_pair: ") + hipGetErrorString(pe));
     }
@@ -539,11 +548,21 @@ extern "C" int lr_ckks_switch_keys(lr_ckks_plan *pl, int level, const lr_poly *c
 // Montgomery domain like the reference's SwitchingKey; p0 / p1 <- the two key-switched polys over Q, coefficient domain.  Same
 // machinery as the CKKS key switch (one plan over contextQ / contextP serves both), with the transforms the other way round.
 int lr_host::bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc) {
-    const int level = pl->cQ->h.L() - 1;
-    LR_TRY(ks_decompose(pl, level, batch, cx, cx_stride, KsInput::Coeff));
+    return bfv_switch_keys_grouped(pl, batch, 1, cx, cx_stride, &evk, acc);
+}
+
+// `groups` independent bfv.switchKeys of `batch` polys each as ONE pass over groups * batch members (lr_bfv_relinearize_deg: the key
+// switches of ct[degree], ct[degree - 1], ... share no data): member g * batch + b of cx and of the accumulators is poly b of group g,
+// switched under evks[g].  Decomposition and tail run once over all members; only the inner product is per key, on its group's member
+// range.  Every member gets the bits of a key switch of its own.
+int lr_host::bfv_switch_keys_grouped(lr_ckks_plan *pl, int batch, int groups, const u64 *cx, long long cx_stride, const lr_poly *const *evks,
+                                     const KeySwitchAcc &acc) {
+    const int level = pl->cQ->h.L() - 1, members = groups * batch;
+    LR_TRY(ks_decompose(pl, level, members, cx, cx_stride, KsInput::Coeff));
     const long long sQ = (long long)pl->cQ->h.L() * (long long)pl->cQ->h.N;
-    LR_TRY(ks_inner_product(pl, level, batch, KsDigits::in_place(pl, pl->c2.d, sQ), evk, acc));
-    return ks_coeff_tail(pl, level, batch, acc);
+    for (int g = 0; g < groups; ++g)
+        LR_TRY(ks_inner_product(pl, level, members, KsDigits::in_place(pl, pl->c2.d, sQ), evks[g], acc, groups == 1 ? KsMembers() : KsMembers{g * batch, batch}));
+    return ks_coeff_tail(pl, level, members, acc);
 }
 
 extern "C" int lr_bfv_switch_keys(lr_ckks_plan *pl, const lr_poly *cx, const lr_poly *evk, lr_poly *p0, lr_poly *p1) {

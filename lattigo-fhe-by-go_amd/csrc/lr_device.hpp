@@ -368,6 +368,28 @@ inline LaunchVerdict launch_verdict(const BfvChainStepLaunch &L, int limbs, int 
                                                         (L.cx_next && !(L.ginv_next & 1u)) || L.out0 == L.out1);
 }
 hipError_t launch_bfv_chain_step(const BfvChainStepLaunch &L, int limbs, int batch, hipStream_t stream);
+
+// The additions of bfv.evaluator.Relinearize after a pass of key switches (lr_bfv_relinearize_deg; bfv/evaluator.go:494-495 once per degree
+// of the pass): out[k] = CRed(... CRed(CRed(base[k] + p[k][0]) + p[k][1]) ... + p[k][terms - 1]) for both components k in one launch, see
+// bfv_relin_fold_kernel.  Term t of batch member b is the row block p[k] + t * group_stride + b * p_stride: the pass's accumulator, whose
+// groups lie group_stride words apart, the highest degree first.  Coefficient domain, all of Q.
+constexpr int kBfvRelinFoldTerms = 4;       // degree 5: the key switches of ct[5] .. ct[2]
+struct BfvRelinFoldLaunch {
+    const u64 *base[2];      // the running pair: ct[0] / ct[1] for the first pass, the outputs afterwards
+    long long base_stride[2];
+    const u64 *p[2];         // the key switches' results of the pass
+    long long p_stride, group_stride;
+    int terms;               // 1 .. kBfvRelinFoldTerms
+    u64 *out[2];             // out[k] may be base[k] (a lane reads everything before it stores), never the other component's operand
+    long long out_stride[2];
+    int n;
+    const LimbParams *lp;
+};
+inline LaunchVerdict launch_verdict(const BfvRelinFoldLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 2 || limbs > kMaxLimbs || batch > 32767 || L.terms < 1 || L.terms > kBfvRelinFoldTerms ||
+                                                        L.out[0] == L.out[1] || L.out[0] == L.base[1] || L.out[1] == L.base[0]);
+}
+hipError_t launch_bfv_relin_fold(const BfvRelinFoldLaunch &L, int limbs, int batch, hipStream_t stream);
 // Context.MultByMonomial (ring/ring.go:663): out = in * X^shift in Z_q[X]/(X^N+1), shift already reduced modulo 2N;
 // like the reference, negated coefficients are q - x without reduction (0 becomes q).  Not in place.
 hipError_t launch_monomial(const GaloisLaunch &L, int limbs, int batch, hipStream_t stream);

@@ -952,4 +952,40 @@ hipError_t launch_bfv_chain_step(const BfvChainStepLaunch &L, int limbs, int bat
     return launch_kernel(bfv_chain_step_kernel, dim3((unsigned)limbs, (unsigned)batch, 2), dim3(1024), (size_t)L.n * sizeof(u64), stream, L);
 }
 
+// The additions that follow a pass of key switches in bfv.evaluator.Relinearize (BfvRelinFoldLaunch), as ONE streaming pass over both
+// components (grid z = 2 * member + component): TERMS + 1 rows read, one written, where Context.Add twice per degree moves 6 TERMS rows
+// in 2 TERMS launches.  The additions keep the reference's order -- the base first, then the highest degree -- each with its own CRed, so
+// the bits are those of the composed sequence for any operands LR_ADD takes, a base holding q or 2q - 1 included.  The terms' loads do not
+// depend on the running sum: a lane issues all TERMS + 1 before the add chain, and reads them all before it stores (out[k] may be base[k]).
+template <int TERMS>
+__global__ __launch_bounds__(256) void bfv_relin_fold_kernel(BfvRelinFoldLaunch L) {
+    const int limb = blockIdx.y, k = blockIdx.z & 1;
+    const long long b = blockIdx.z >> 1;
+    const u64 q = L.lp[limb].q;
+    const long long row = (long long)limb * L.n;
+    const ulonglong2 *pb = row_in(L.base[k], b, L.base_stride[k], row), *pp = row_in(L.p[k], b, L.p_stride, row);
+    ulonglong2 *po = row_out(L.out[k], b, L.out_stride[k], row);
+    const long long gs = L.group_stride >> 1;       // in pairs
+    const int pairs = L.n >> 1;
+    LR_FOR_PAIRS(e, pairs) {
+        ulonglong2 acc = ld_stream(pb + e), t[TERMS];
+#pragma unroll
+        for (int i = 0; i < TERMS; ++i) t[i] = ld_stream(pp + i * gs + e);
+#pragma unroll
+        for (int i = 0; i < TERMS; ++i) acc = add2(acc, t[i], q);      // :494-495, degree by degree
+        st_stream(po + e, acc);
+    }
+}
+
+hipError_t launch_bfv_relin_fold(const BfvRelinFoldLaunch &L, int limbs, int batch, hipStream_t stream) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    const dim3 grid = pair_grid(L.n, (unsigned)limbs, 2u * (unsigned)batch);
+    switch (L.terms) {
+    case 1: return launch_kernel(bfv_relin_fold_kernel<1>, grid, dim3(256), 0, stream, L);
+    case 2: return launch_kernel(bfv_relin_fold_kernel<2>, grid, dim3(256), 0, stream, L);
+    case 3: return launch_kernel(bfv_relin_fold_kernel<3>, grid, dim3(256), 0, stream, L);
+    default: return launch_kernel(bfv_relin_fold_kernel<4>, grid, dim3(256), 0, stream, L);
+    }
+}
+
 }  // namespace lr

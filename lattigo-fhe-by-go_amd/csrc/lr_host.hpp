@@ -377,7 +377,7 @@ struct lr_ckks_plan {
     Options opt;           // environment switches, read once at plan creation
     Pool c2QiQ, c2QiP, poolPP, c2, c0, c1, c2x, q1, q2, permQ, permP;
     Pool encQ, encP;       // pk-encryption temporaries over Q||P (lr_ckks_encrypt_pk)
-    Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q)
+    Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q; lr_bfv_relinearize_deg: two of them per group of a pass)
     Pool chainP;           // bfv rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_bfv_chain.cpp)
     Pool zerosQ;           // one poly of zeros over Q: the `plus` operand of the NTT epilogue where a caller has none
     Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_plan_decomposition)
@@ -540,6 +540,7 @@ struct DigitExtension {
 //   ks_coeff_tail                   nothing
 //   ks_ntt_tail                     batch == 1; asked about the OUTPUTS (the addends may coincide: both the row of zeros, distance 0)
 //   lr_bfv_relinearize              batch == 1; inputs and outputs both; no output over the other component's operand
+//   lr_bfv_relinearize_deg          its composed route, as lr_bfv_relinearize (an output over the other component's operand is refused there)
 //   lr_bfv_rotate, lr_ckks_rotate   batch == 1; (the outputs are two pools)
 //   lr_ckks_rescale                 !rescale_unpaired; the lower address first; one poly each only at a distance >= limbs * N (no overlap);
 //                                   same shapes; 2 * batch * limbs <= pair_max_workgroups
@@ -615,6 +616,7 @@ std::atomic<int> &standalone_plans(int device);
 int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride, u64 gen, const u64 *const *in_table = nullptr);
 int switch_keys_core(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc, const KeySwitchEpilogue *fin = nullptr);
 int bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc);
+int bfv_switch_keys_grouped(lr_ckks_plan *pl, int batch, int groups, const u64 *cx, long long cx_stride, const lr_poly *const *evks, const KeySwitchAcc &acc);
 int check_ct(const lr_ckks_plan *pl, int level, const lr_poly *p, int batch);
 int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride);
 

@@ -623,6 +623,16 @@ class CkksPlan:
             idx <<= 1
             k >>= 1
 
+    def BfvRelinearizeDeg(self, ct, evakeys, ctOut):
+        """bfv.evaluator.Relinearize of a ciphertext of any degree len(ct) - 1 <= 5 as one call (lr_bfv_relinearize_deg,
+        bfv/evaluator.go:480-499): evakeys[k] = the image of evakey.evakey[k], the key from s^(k + 2); ctOut may be (ct[0], ct[1])"""
+        degree = len(ct) - 1
+        if len(evakeys) < degree - 1:
+            raise ValueError("one key per degree above 1")
+        cts = (C.c_void_p * max(degree + 1, 1))(*[p.h.value if p is not None else None for p in ct])
+        keys = (C.c_void_p * max(len(evakeys), 1))(*[k.h.value if k is not None else None for k in evakeys])
+        check(lib().lr_bfv_relinearize_deg(self.h, cts, degree, keys if len(evakeys) else None, ctOut[0].h, ctOut[1].h))
+
     def BfvRotateChain(self, ct0, generators, switchKeys, accumulate, ctOut):
         """a chain of bfv.evaluator.permute steps as one call (lr_bfv_rotate_chain): step i rotates the running ciphertext by the Galois
         element generators[i] under switchKeys[i] and replaces it (accumulate False: rotateColumnsPow2, bfv/evaluator.go:637-666) or is
