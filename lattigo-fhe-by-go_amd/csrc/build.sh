@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 [ -n "$LR_BUILD_DIAG" ] && FLAGS="$FLAGS -DLR_BUILD_DIAG=1"
 mkdir -p build
 # the C ABI, one translation unit per handle family (lr_host.hpp is what they share)
-ABI_UNITS="lr_abi_core lr_abi_ring lr_abi_bext lr_abi_ckks lr_abi_batcher lr_abi_bfv lr_bfv_chain lr_bfv_relin lr_abi_bfv_batcher lr_abi_peer lr_bfv_encoder lr_ckks_encoder lr_bfv_encryptor lr_ckks_encryptor lr_keygen lr_collective lr_refresh lr_setup"
+ABI_UNITS="lr_abi_core lr_abi_ring lr_abi_bext lr_abi_ckks lr_abi_batcher lr_abi_bfv lr_abi_bfv_eval lr_abi_bfv_batcher lr_abi_peer lr_bfv_encoder lr_ckks_encoder lr_bfv_encryptor lr_ckks_encryptor lr_keygen lr_collective lr_refresh lr_setup"
 link() {
   $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../liblattigo_ring_hip.so build/lr_ntt.o build/lr_ewise.o build/lr_bext.o build/lr_bfv_encode.o build/lr_ckks_encode.o build/lr_bfv_encrypt.o build/lr_ckks_encrypt.o build/lr_keygen_kernels.o build/lr_collective_kernels.o build/lr_refresh_kernels.o build/lr_setup_kernels.o $(for u in $ABI_UNITS; do echo build/$u.o; done) build/lr_precompute.o build/lr_asm.o build/lr_asm_blob.o
   echo "built $(cd .. && pwd)/liblattigo_ring_hip.so"

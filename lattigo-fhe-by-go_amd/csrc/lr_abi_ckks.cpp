@@ -1,5 +1,6 @@
-// lr_abi_ckks.cpp -- C ABI: lr_ckks_plan and the ckks.Evaluator / bfv key-switch call sequences (switchKeysInPlace, MulRelin, rotations,
-// hoisted rotations, Relinearize, pk-encrypt, decrypt, Rescale).
+// lr_abi_ckks.cpp -- C ABI: lr_ckks_plan, the key switch itself (ks_*, switch_keys_core, bfv_switch_keys_core / _grouped) and the
+// ckks.Evaluator call sequences over it (switchKeysInPlace, MulRelin, rotations, hoisted rotations, pk-encrypt, decrypt, Rescale).  The
+// BFV evaluator's pipelines over the same key switch are lr_abi_bfv_eval.cpp.
 #include "lr_host.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -133,8 +134,9 @@ struct PlanFork {
 };
 
 
-int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride,
-                    u64 gen, const u64 *const *in_table) {
+// Context.Permute (coefficient domain) or PermuteNTT of `batch` polys: THE GaloisLaunch fill of the rotations, CKKS and BFV
+int run_permute(lr_context *c, bool ntt_domain, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride,
+                u64 gen, const u64 *const *in_table) {
     GaloisLaunch L;
     L.in_table = in_table;
     L.in = in;
@@ -143,11 +145,15 @@ int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long lon
     L.out_stride = out_stride;
     L.n = (int)c->h.N;
     L.logn = (int)c->h.logN;
-    L.ntt_domain = 1;
+    L.ntt_domain = ntt_domain ? 1 : 0;
     L.gen = gen & ((c->h.N << 1) - 1);
     L.lp = c->d_lp;
     LR_HIP(launch_permute(L, limbs, batch, c->stream));
     return LR_OK;
+}
+int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride,
+                    u64 gen, const u64 *const *in_table) {
+    return run_permute(c, true, limbs, batch, in, in_stride, out, out_stride, gen, in_table);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -508,9 +514,9 @@ int check_ct(const lr_ckks_plan *pl, int level, const lr_poly *p, int batch) {
     return LR_OK;
 }
 
-namespace {
-// The checks the pipelines' entry points share, after their null checks.  The first that fails decides the code a doubly wrong call gets,
-// so each entry point keeps the order it always had: most are check_call; lr_bfv_switch_keys and lr_bfv_relinearize ask in another.
+// The checks the pipelines' entry points share (here and in lr_abi_bfv_eval.cpp), after their null checks.  The first that fails decides
+// the code a doubly wrong call gets, so each entry point keeps the order it always had: most are check_call; lr_bfv_switch_keys and
+// lr_bfv_relinearize ask in another.
 int check_batch(const lr_ckks_plan *pl, int batch) {
     if (batch > pl->max_batch) return fail(LR_ERR_SHAPE, "batch exceeds the plan's max_batch");
     return LR_OK;
@@ -530,7 +536,6 @@ int begin_pipeline(const lr_ckks_plan *pl) {
     LR_HIP(hipSetDevice(pl->device));
     return LR_OK;
 }
-}  // namespace
 
 }  // namespace lr_host
 
@@ -563,84 +568,6 @@ int lr_host::bfv_switch_keys_grouped(lr_ckks_plan *pl, int batch, int groups, co
     for (int g = 0; g < groups; ++g)
         LR_TRY(ks_inner_product(pl, level, members, KsDigits::in_place(pl, pl->c2.d, sQ), evks[g], acc, groups == 1 ? KsMembers() : KsMembers{g * batch, batch}));
     return ks_coeff_tail(pl, level, members, acc);
-}
-
-extern "C" int lr_bfv_switch_keys(lr_ckks_plan *pl, const lr_poly *cx, const lr_poly *evk, lr_poly *p0, lr_poly *p1) {
-    return guarded([&]() -> int {
-    if (!pl || !cx || !evk || !p0 || !p1) return fail(LR_ERR_ARG, "null argument");
-    const int level = pl->cQ->h.L() - 1;
-    if (cx == p0 || cx == p1 || p0 == p1) return fail(LR_ERR_ARG, "bfv switch keys: cx, p0 and p1 must be distinct polys");
-    LR_TRY(check_cts(pl, level, cx->batch, {cx, p0, p1}));
-    LR_TRY(check_batch(pl, cx->batch));
-    LR_TRY(begin_pipeline(pl));
-    return bfv_switch_keys_core(pl, cx->batch, cx->d, cx->stride(), evk, {{p0->d, p1->d}, {p0->stride(), p1->stride()}});
-    });
-}
-
-// bfv.evaluator.Relinearize on a degree-2 ciphertext (bfv/evaluator.go:480-501, 512-524): out = (c0 + p0, c1 + p1) with
-// (p0, p1) = switchKeys(c2, evakey[0]); all polys over Q in the coefficient domain.  out0 / out1 may be c0 / c1.
-extern "C" int lr_bfv_relinearize(lr_ckks_plan *pl, const lr_poly *c0, const lr_poly *c1, const lr_poly *c2, const lr_poly *evk,
-                                  lr_poly *out0, lr_poly *out1) {
-    return guarded([&]() -> int {
-    if (!pl || !c0 || !c1 || !c2 || !evk || !out0 || !out1) return fail(LR_ERR_ARG, "null argument");
-    lr_context *cQ = pl->cQ;
-    const int level = cQ->h.L() - 1, batch = c2->batch;
-    LR_TRY(check_cts(pl, level, batch, {c0, c1, c2, out0, out1}));
-    if (out0 == out1 || c2 == out0 || c2 == out1) return fail(LR_ERR_ARG, "bfv relinearize: out0, out1 and c2 must be distinct polys");
-    LR_TRY(check_batch(pl, batch));
-    LR_TRY(begin_pipeline(pl));
-    const long long sQ = (long long)cQ->h.L() * (long long)cQ->h.N;
-    LR_TRY(pl->bfvP.ensure(cQ, (size_t)2 * batch * sQ));        // keyswitchpool[2], [3] (:489-490)
-    u64 *p0 = pl->bfvP.d, *p1 = pl->bfvP.d + (long long)batch * sQ;
-    LR_TRY(bfv_switch_keys_core(pl, batch, c2->d, c2->stride(), evk, {{p0, p1}, {sQ, sQ}}));
-    const ComponentPair ins = component_pair(c0->d, c0->stride(), c1->d, c1->stride(), batch);
-    const ComponentPair outs = component_pair(out0->d, out0->stride(), out1->d, out1->stride(), batch);
-    if (batch == 1 && !pl->opt.no_pair && ins && outs && out0->d != c1->d && out1->d != c0->d) {
-        // one ciphertext: the two additions as one launch over two "polys" at the distances between the components
-        return run_ewise(cQ, LR_ADD, level + 1, 2, c0->d, ins.stride, p0, sQ, out0->d, outs.stride, nullptr);   // :494-495
-    }
-    LR_TRY(run_ewise(cQ, LR_ADD, level + 1, batch, c0->d, c0->stride(), p0, sQ, out0->d, out0->stride(), nullptr));   // :494
-    return run_ewise(cQ, LR_ADD, level + 1, batch, c1->d, c1->stride(), p1, sQ, out1->d, out1->stride(), nullptr);    // :495
-    });
-}
-
-// bfv.evaluator.permute (bfv/evaluator.go:711-735), the body of RotateRows (:670-681) and of RotateColumns with the key of that
-// rotation (:590-592, and each step of rotateColumnsPow2 :636-662): Context.Permute of both components (coefficient domain, :723-724),
-// switchKeys of the second (:729), Add and Copy (:731-732).  The key switch accumulates straight into the outputs (the reference's
-// keyswitchpool[2], [3] and its Copy are the same values); out may be the input (the reference's polypool branch, :717-721).
-extern "C" int lr_bfv_rotate(lr_ckks_plan *pl, const lr_poly *c0, const lr_poly *c1, uint64_t gen, const lr_poly *rotkey, lr_poly *o0,
-                             lr_poly *o1) {
-    return guarded([&]() -> int {
-    if (!pl || !c0 || !c1 || !rotkey || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
-    lr_context *cQ = pl->cQ;
-    const int level = cQ->h.L() - 1, batch = c0->batch;
-    LR_TRY(check_call(pl, level, batch, {c0, c1, o0, o1}));
-    if (o0->d == o1->d) return fail(LR_ERR_ARG, "bfv rotate: the two output polys must be distinct");
-    if (cQ->h.N < 2 || cQ->h.logN > 31) return fail(LR_ERR_UNSUPPORTED, "ring degree");
-    LR_TRY(begin_pipeline(pl));
-    const int n = (int)cQ->h.N, L1 = level + 1;
-    const long long s = (long long)L1 * n;
-    for (Pool *p : {&pl->c0, &pl->c2x}) LR_TRY(p->ensure(cQ, (size_t)batch * s));
-    GaloisLaunch G;
-    G.n = n;
-    G.logn = (int)cQ->h.logN;
-    G.ntt_domain = 0;
-    G.gen = gen & ((cQ->h.N << 1) - 1);
-    G.lp = cQ->d_lp;
-    const ComponentPair ins = component_pair(c0->d, c0->stride(), c1->d, c1->stride(), batch);
-    if (batch == 1 && !pl->opt.no_pair && ins) {
-        // one ciphertext: both components in one launch, the strides are the distances between them (see lr_ckks_rotate)
-        G.in = c0->d; G.in_stride = ins.stride; G.out = pl->c0.d; G.out_stride = component_distance(pl->c0.d, pl->c2x.d);
-        LR_HIP(launch_permute(G, L1, 2, cQ->stream));                                          // :723-724
-    } else {
-        G.in = c0->d; G.in_stride = c0->stride(); G.out = pl->c0.d; G.out_stride = s;
-        LR_HIP(launch_permute(G, L1, batch, cQ->stream));                                      // :723
-        G.in = c1->d; G.in_stride = c1->stride(); G.out = pl->c2x.d;
-        LR_HIP(launch_permute(G, L1, batch, cQ->stream));                                      // :724
-    }
-    LR_TRY(bfv_switch_keys_core(pl, batch, pl->c2x.d, s, rotkey, {{o0->d, o1->d}, {o0->stride(), o1->stride()}}));   // :729 (p1 lands in out1: :732)
-    return run_ewise(cQ, LR_ADD, L1, batch, pl->c0.d, s, o0->d, o0->stride(), o0->d, o0->stride(), nullptr);   // :731
-    });
 }
 
 // permuteNTT (ckks/evaluator.go:1448-1468): RotateColumns with a specific rotation key / Conjugate.

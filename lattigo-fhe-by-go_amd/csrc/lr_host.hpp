@@ -377,8 +377,8 @@ struct lr_ckks_plan {
     Options opt;           // environment switches, read once at plan creation
     Pool c2QiQ, c2QiP, poolPP, c2, c0, c1, c2x, q1, q2, permQ, permP;
     Pool encQ, encP;       // pk-encryption temporaries over Q||P (lr_ckks_encrypt_pk)
-    Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q; lr_bfv_relinearize_deg: two of them per group of a pass)
-    Pool chainP;           // bfv rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_bfv_chain.cpp)
+    Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q; lr_bfv_relinearize_deg: two of them per group of a pass; lr_abi_bfv_eval.cpp)
+    Pool chainP;           // bfv rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_abi_bfv_eval.cpp)
     Pool zerosQ;           // one poly of zeros over Q: the `plus` operand of the NTT epilogue where a caller has none
     Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_plan_decomposition)
     // small batches: independent launches of one pipeline side by side (PlanFork); stream and events are created at the first fork
@@ -539,9 +539,10 @@ struct DigitExtension {
 // carries both components of a small batch asks here, and adds (all but the rescale: !no_pair):
 //   ks_coeff_tail                   nothing
 //   ks_ntt_tail                     batch == 1; asked about the OUTPUTS (the addends may coincide: both the row of zeros, distance 0)
-//   lr_bfv_relinearize              batch == 1; inputs and outputs both; no output over the other component's operand
-//   lr_bfv_relinearize_deg          its composed route, as lr_bfv_relinearize (an output over the other component's operand is refused there)
-//   lr_bfv_rotate, lr_ckks_rotate   batch == 1; (the outputs are two pools)
+//   bfv_add_pair                    (lr_abi_bfv_eval.cpp: lr_bfv_relinearize and the composed route of lr_bfv_relinearize_deg) batch == 1; inputs
+//                                   and outputs both; no output over the other component's operand; the two addends back to back
+//   bfv_permute_pair                (lr_abi_bfv_eval.cpp: lr_bfv_rotate and the composed rotation chains) batch == 1; (the outputs are two pools)
+//   lr_ckks_rotate                  batch == 1; (the outputs are two pools)
 //   lr_ckks_rescale                 !rescale_unpaired; the lower address first; one poly each only at a distance >= limbs * N (no overlap);
 //                                   same shapes; 2 * batch * limbs <= pair_max_workgroups
 // Only the rescale asks for a positive distance.  With the outputs of ks_ntt_tail at a negative one, N = 2^16 and Options::no_exttop, the
@@ -611,13 +612,18 @@ int moddown_pq_core(lr_bext *b, int level, const u64 *p1Q, long long p1Q_stride,
 bool moddown_epilogue_available(const lr_bext *b);
 DigitShape digit_shape(const lr_decomposer *d, int level, int crt);
 int decompose_core(lr_decomposer *d, int level, int crt, Rows in, int batch, Rows outQ, const Rows *outP, DigitExtension how = DigitExtension());
-// lr_abi_ckks.cpp: the key switch and the pipelines over it
+// lr_abi_ckks.cpp: the key switch and the pipelines over it (the BFV evaluator's: lr_abi_bfv_eval.cpp)
 std::atomic<int> &standalone_plans(int device);
+int run_permute(lr_context *c, bool ntt_domain, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride, u64 gen, const u64 *const *in_table = nullptr);
 int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride, u64 gen, const u64 *const *in_table = nullptr);
 int switch_keys_core(lr_ckks_plan *pl, int level, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc, const KeySwitchEpilogue *fin = nullptr);
 int bfv_switch_keys_core(lr_ckks_plan *pl, int batch, const u64 *cx, long long cx_stride, const lr_poly *evk, const KeySwitchAcc &acc);
 int bfv_switch_keys_grouped(lr_ckks_plan *pl, int batch, int groups, const u64 *cx, long long cx_stride, const lr_poly *const *evks, const KeySwitchAcc &acc);
 int check_ct(const lr_ckks_plan *pl, int level, const lr_poly *p, int batch);
+int check_batch(const lr_ckks_plan *pl, int batch);
+int check_cts(const lr_ckks_plan *pl, int level, int batch, std::initializer_list<const lr_poly *> cts);
+int check_call(const lr_ckks_plan *pl, int level, int batch, std::initializer_list<const lr_poly *> cts);
+int begin_pipeline(const lr_ckks_plan *pl);
 int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride);
 
 }  // namespace lr_host

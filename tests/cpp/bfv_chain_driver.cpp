@@ -1,6 +1,6 @@
 // The BFV rotation chains' host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_bfv_chain_sanitizers.py): the
-// REAL host code -- lr_bfv_chain.cpp over lr_abi_*.cpp, lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP
-// stand-in, the recording launch stubs of tests/cpp/hipstub/ and bfv_chain_stub.cpp.  lr_bfv_inner_sum and lr_bfv_rotate_chain over
+// REAL host code -- lr_abi_*.cpp (the chains are in lr_abi_bfv_eval.cpp), lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the
+// host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/.  lr_bfv_inner_sum and lr_bfv_rotate_chain over
 //   * N = 2^12 and 2^14 (the fused route), 2^15, 2^10 and 2 (the composed route; N = 2: the row step alone), |Q| = 5 with |P| = 3 or 2;
 //   * the default plan, lr_options::no_epilogue (composed at every degree) and no_pair;
 //   * batches 1, 2 and 5; out of place, in place, into the other component's poly, polys with another stride than the pools';
@@ -10,46 +10,15 @@
 //   * every refusal of the header: the code, and that nothing was launched;
 //   * two plans on two threads.
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#include "driver_check.hpp"
 
 namespace lr {
-extern std::atomic<unsigned long long> g_stub_launches, g_bfv_chain_step_launches, g_bfv_chain_step_last, g_bfv_chain_step_crossed;
+extern std::atomic<unsigned long long> g_bfv_chain_step_launches, g_bfv_chain_step_last, g_bfv_chain_step_crossed;
 }
 
-static std::atomic<int> g_fail{0}, g_calls{0}, g_refusals{0};
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-#define RUN(x)       \
-    do {             \
-        OK(x);       \
-        ++g_calls;   \
-    } while (0)
-// a refusal: the code, and no launch (single-threaded part only)
-#define REFUSED(x, code)                                                   \
-    do {                                                                   \
-        const unsigned long long before_ = lr::g_stub_launches.load();     \
-        CHECK((x) == (code));                                              \
-        CHECK(lr::g_stub_launches.load() == before_);                      \
-        ++g_refusals;                                                      \
-    } while (0)
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
-static const uint64_t Q5[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 36028797019488257ull};
-static const uint64_t P3[3] = {1125899908612097ull, 1125899909398529ull, 36028797023420417ull};
 static const int MAXB = 5;
 
 struct Ring {
@@ -59,16 +28,10 @@ struct Ring {
 };
 static const Ring kRings[5] = {{12, 3, true}, {14, 2, true}, {15, 2, false}, {10, 3, false}, {1, 2, false}};
 
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
-
 struct Plan {
     Ring r;
     bool fused = false, pairs = true;
-    // the route of a chain (chain_route, lr_bfv_chain.cpp): a replace chain of one ciphertext at N = 2^14 takes the separate launches
+    // the route of a chain (chain_route, lr_abi_bfv_eval.cpp): a replace chain of one ciphertext at N = 2^14 takes the separate launches
     bool step_pass(int batch, int accumulate) const { return fused && !(accumulate == 0 && batch == 1 && r.logn == 14 && pairs); }
     lr_context *q = nullptr, *p = nullptr;
     lr_ckks_plan *pl = nullptr;

@@ -1,6 +1,6 @@
 // lr_bfv_relinearize_deg's host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_bfv_relin_deg_sanitizers.py):
-// the REAL host code -- lr_bfv_relin.cpp over lr_abi_*.cpp, lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP
-// stand-in, the recording launch stubs of tests/cpp/hipstub/ and bfv_relin_stub.cpp.  Over
+// the REAL host code -- lr_abi_*.cpp (the call is in lr_abi_bfv_eval.cpp), lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the
+// host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/.  Over
 //   * N = 2^12, 2^15 and 8, |Q| = 5 with |P| = 3 or 2;
 //   * the default plan (merged route), lr_options::no_epilogue (composed route) and no_pair;
 //   * degrees 1 .. 5 at batches 1, 2 and max_batch, with max_batch 4 and 3: G = min(degree - 1, max(1, max_batch / batch)) takes 1, the
@@ -14,58 +14,21 @@
 //   * two plans on two threads.
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <algorithm>
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#include "driver_check.hpp"
 
 namespace lr {
-extern std::atomic<unsigned long long> g_stub_launches, g_bfv_relin_fold_launches, g_bfv_relin_fold_terms, g_bfv_relin_fold_crossed;
+extern std::atomic<unsigned long long> g_bfv_relin_fold_launches, g_bfv_relin_fold_terms, g_bfv_relin_fold_crossed;
 }
 
-static std::atomic<int> g_fail{0}, g_calls{0}, g_refusals{0};
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-#define RUN(x)       \
-    do {             \
-        OK(x);       \
-        ++g_calls;   \
-    } while (0)
-// a refusal: the code, and no launch (single-threaded part only)
-#define REFUSED(x, code)                                                   \
-    do {                                                                   \
-        const unsigned long long before_ = lr::g_stub_launches.load();     \
-        CHECK((x) == (code));                                              \
-        CHECK(lr::g_stub_launches.load() == before_);                      \
-        ++g_refusals;                                                      \
-    } while (0)
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
-static const uint64_t Q5[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 36028797019488257ull};
-static const uint64_t P3[3] = {1125899908612097ull, 1125899909398529ull, 36028797023420417ull};
 
 struct Ring {
     int logn;
     int nP;
 };
 static const Ring kRings[3] = {{12, 3}, {15, 2}, {3, 3}};
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
 
 struct Plan {
     Ring r;

@@ -21,6 +21,10 @@
 namespace lr {
 
 std::atomic<unsigned long long> g_stub_launches{0};
+// the BFV chain step passes (all, those that write no next input, those with a crossed operand) and the relinearisation folds (all, their
+// terms, those with a crossed operand): tests/cpp/bfv_chain_driver.cpp and bfv_relin_deg_driver.cpp read them
+std::atomic<unsigned long long> g_bfv_chain_step_launches{0}, g_bfv_chain_step_last{0}, g_bfv_chain_step_crossed{0};
+std::atomic<unsigned long long> g_bfv_relin_fold_launches{0}, g_bfv_relin_fold_terms{0}, g_bfv_relin_fold_crossed{0};
 // what the host admitted the last basis extension and the last key inner product with (tests/cpp/admission_driver.cpp prints them):
 // {lazy_terms, exact_terms, word_barrett, wide_ok, input limbs} of the extension's tables; KeyMacLaunch::wide of the Q part and the P part
 // (per thread: the concurrency drivers launch from many threads at once)
@@ -208,6 +212,50 @@ hipError_t launch_multicopy(const MultiCopyLaunch &L, int limbs, hipStream_t) {
         rows_w(L.dst[k], L.dst_stride[k], 0, 1, limbs, L.batch, L.n);
         for (int b = 0; b < L.batch; ++b) L.dst[k][b * L.dst_stride[k]] = L.src[k][b * L.src_stride[k]];
     }
+    return hipSuccess;
+}
+// asks the product's launch_verdict and checks what the pass relies on: an output is never the OTHER component's operand, and the next
+// key-switch input is none of the operands
+hipError_t launch_bfv_chain_step(const BfvChainStepLaunch &L, int limbs, int batch, hipStream_t) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    g_stub_launches.fetch_add(1);
+    g_bfv_chain_step_launches.fetch_add(1);
+    if (!L.cx_next) g_bfv_chain_step_last.fetch_add(1);
+    if (L.out0 == L.a1 || L.out0 == L.p1 || L.out1 == L.a0 || L.out1 == L.p0 || L.p0 == L.a0 || L.p1 == L.a1 ||
+        (L.cx_next && (L.cx_next == L.a0 || L.cx_next == L.a1 || L.cx_next == L.p0 || L.cx_next == L.p1 || L.cx_next == L.out0 || L.cx_next == L.out1)))
+        g_bfv_chain_step_crossed.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.a0 + b * L.a0_stride + row, L.n);
+            rd(L.p0 + b * L.p_stride + row, L.n);
+            rd(L.p1 + b * L.p_stride + row, L.n);
+            if (L.accumulate) rd(L.a1 + b * L.a1_stride + row, L.n);
+            wr(L.out0 + b * L.out0_stride + row, L.n);
+            wr(L.out1 + b * L.out1_stride + row, L.n);
+            if (L.cx_next) wr(L.cx_next + b * L.cx_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+// asks the product's launch_verdict, counts its terms and checks what the pass relies on: an output is neither the other component's
+// operand nor any term
+hipError_t launch_bfv_relin_fold(const BfvRelinFoldLaunch &L, int limbs, int batch, hipStream_t) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    g_stub_launches.fetch_add(1);
+    g_bfv_relin_fold_launches.fetch_add(1);
+    g_bfv_relin_fold_terms.fetch_add((unsigned long long)L.terms);
+    if (L.out[0] == L.p[0] || L.out[0] == L.p[1] || L.out[1] == L.p[0] || L.out[1] == L.p[1] || L.base[0] == L.p[0] || L.base[1] == L.p[1])
+        g_bfv_relin_fold_crossed.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int k = 0; k < 2; ++k)
+        for (int b = 0; b < batch; ++b)
+            for (int i = 0; i < limbs; ++i) {
+                const long long row = (long long)i * L.n;
+                rd(L.base[k] + b * L.base_stride[k] + row, L.n);
+                for (int t = 0; t < L.terms; ++t) rd(L.p[k] + t * L.group_stride + b * L.p_stride + row, L.n);
+                wr(L.out[k] + b * L.out_stride[k] + row, L.n);
+            }
     return hipSuccess;
 }
 static void keymac_touch(const KeyMacLaunch &L, int limbs, int batch) {

@@ -2,7 +2,7 @@
 // decomposition, the key inner product and the two ModDown tails of lr_abi_ckks.cpp, the digit shapes of lr_abi_bext.cpp), lr_host.hpp,
 // lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/, which touch
 // the first and the last word of every row a kernel would read or write.  lr_ckks_switch_keys, lr_ckks_mulrelin, lr_ckks_rotate,
-// lr_ckks_rotate_hoisted (two rotations), lr_ckks_rescale, lr_bfv_switch_keys, lr_bfv_relinearize and lr_bfv_rotate over
+// lr_ckks_rotate_hoisted (two rotations), lr_ckks_rescale, lr_bfv_switch_keys, lr_bfv_relinearize and lr_bfv_rotate (lr_abi_bfv_eval.cpp) over
 //   * N = 2^12 (|Q| = 5, |P| = 3: digits of 3 + 2 limbs), 2^15 (|Q| = 5, |P| = 2: 2 + 2 + 1) and 2^16 (|Q| = 4, |P| = 2, the six primes there are:
 //     the top-stage extensions, the staging buffers and the forks of a lone plan), every level from 0 to |Q| - 1 -- full digits, partial last
 //     digits, single-limb digits, the trivial-copy branch;
@@ -15,39 +15,11 @@
 //     bounds -- Q and P just under 2^61 with one special prime, either side of 2^57, either side of 2^33).
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <algorithm>
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <deque>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
-
-namespace lr {
-extern std::atomic<unsigned long long> g_stub_launches;
-}
-
-static int g_fail = 0;
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-// a refusal: the code, and no launch
-#define REFUSED(x, code)                                                   \
-    do {                                                                   \
-        const unsigned long long before_ = lr::g_stub_launches.load();     \
-        CHECK((x) == (code));                                              \
-        CHECK(lr::g_stub_launches.load() == before_);                      \
-        ++g_refusals;                                                      \
-    } while (0)
-static int g_calls = 0, g_refusals = 0;
+// a successful call here also launches something
 #define RUN(x)                                                             \
     do {                                                                   \
         const unsigned long long before_ = lr::g_stub_launches.load();     \
@@ -55,10 +27,9 @@ static int g_calls = 0, g_refusals = 0;
         CHECK(lr::g_stub_launches.load() > before_);                       \
         ++g_calls;                                                         \
     } while (0)
+#include "driver_check.hpp"
 
-// DefaultParams[PN15QP880]'s and DefaultParams[PN16QP1761]'s first primes (the latter congruent to 1 modulo 2^17, the former modulo 2^16)
-static const uint64_t Q5[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 36028797019488257ull};
-static const uint64_t P3[3] = {1125899908612097ull, 1125899909398529ull, 36028797023420417ull};
+// Q5 / P3 of driver_check.hpp with DefaultParams[PN16QP1761]'s first primes (congruent to 1 modulo 2^17)
 static const uint64_t P2[2] = {1125899908612097ull, 1125899909398529ull};
 static const uint64_t Q16[4] = {36028797019488257ull, 35184372744193ull, 35184373006337ull, 35184376545281ull};
 static const uint64_t P16[2] = {36028797023420417ull, 36028797024206849ull};
@@ -87,12 +58,6 @@ static const char *set_variant(lr_options *o, int v) {
     case 8: o->keymac_narrow = 1; return "keymac_narrow";
     default: o->pair_max_workgroups = 4; o->fork_below_workgroups = 4; return "low thresholds";
     }
-}
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
 }
 
 static uintptr_t address(const lr_poly *p) {
@@ -362,6 +327,6 @@ int main(int argc, char **argv) {
     }
     CHECK(forks16 > 0 && forks_other == 0 && grouped > 0);                // the lone plan forks at N = 2^16 only; the digits' extensions are grouped
     CHECK(hipstub_live_allocations() == 0);                                // every pool and table went with its handle
-    std::printf("key_switch: calls %d, refusals %d, forks %llu, grouped extensions %llu, failures %d\n", g_calls, g_refusals, forks16, grouped, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("key_switch: calls %d, refusals %d, forks %llu, grouped extensions %llu, failures %d\n", g_calls.load(), g_refusals.load(), forks16, grouped, g_fail.load());
+    return g_fail.load() ? 1 : 0;
 }

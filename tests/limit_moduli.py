@@ -132,7 +132,7 @@ def word_barrett(P):
 
 
 def keymac_wide_ok(moduli, beta, keymac_narrow=False):
-    """lr_abi_ckks.cpp:293-298"""
+    """keymac_wide_ok, lr_abi_ckks.cpp"""
     return (not keymac_narrow) and max(moduli) * beta < (1 << 64)
 
 
@@ -225,7 +225,7 @@ def admission_sets(logn):
     add("ext_word_in", "ext", Qs, "word_barrett: every p > 2^32", True, P=above(32, logn, 2), terms=2)
     add("ext_word_out", "ext", Qs, "word_barrett: every p > 2^32", False, P=[above(32, logn), below(32, logn)], terms=2)
 
-    # ---- key inner product (lr_abi_ckks.cpp:292-298): beta * qmax < 2^64 with one special prime, so beta = |Q|
+    # ---- key inner product (keymac_wide_ok, lr_abi_ckks.cpp): beta * qmax < 2^64 with one special prime, so beta = |Q|
     q61 = below(61, logn, 10)
     add("keymac_beta8_in", "keymac", q61[1:9], "beta * q < 2^64", True, P=q61[:1], terms=8)
     add("keymac_beta9_out", "keymac", q61[1:10], "beta * q < 2^64", False, P=q61[:1], terms=9)

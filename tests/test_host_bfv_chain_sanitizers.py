@@ -1,4 +1,4 @@
-"""The BFV rotation chains' host side (lattigo-fhe-by-go_amd/csrc/lr_bfv_chain.cpp: the argument and shape checks in the header's order, the
+"""The BFV rotation chains' host side (lattigo-fhe-by-go_amd/csrc/lr_abi_bfv_eval.cpp: the argument and shape checks in the header's order, the
 route decision, the two pool pairs that state and accumulators alternate on, the copy for crossed outputs, the Galois elements of InnerSum)
 under AddressSanitizer + UBSan and under ThreadSanitizer (CPU build only, each run as its own executable), driven by
 tests/cpp/bfv_chain_driver.cpp: lr_bfv_inner_sum and lr_bfv_rotate_chain on both routes, N = 2 among the degrees, three option sets,
@@ -18,7 +18,7 @@ from host_stub_build import build_host_driver
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_bfv_chain_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "bfv_chain_driver", flags, tag, units=["lr_bfv_chain"], stubs=["bfv_chain_stub"])
+    exe = build_host_driver(str(tmp_path), "bfv_chain_driver", flags, tag)
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the routes, not the caller's env
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])

@@ -1,4 +1,4 @@
-"""lr_bfv_relinearize_deg's host side (lattigo-fhe-by-go_amd/csrc/lr_bfv_relin.cpp: the argument and shape checks in the header's order, the
+"""lr_bfv_relinearize_deg's host side (lattigo-fhe-by-go_amd/csrc/lr_abi_bfv_eval.cpp: the argument and shape checks in the header's order, the
 route decision, the passes of G groups, the gather, the grouped key switch's member ranges in lr_abi_ckks.cpp, the fold's operands) under
 AddressSanitizer + UBSan and under ThreadSanitizer (CPU build only, each run as its own executable), driven by
 tests/cpp/bfv_relin_deg_driver.cpp: both routes, degrees 1 to 5, batches 1, 2 and max_batch with max_batch 4 and 3 (G = 1, partial and
@@ -18,7 +18,7 @@ from host_stub_build import build_host_driver
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_bfv_relin_deg_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "bfv_relin_deg_driver", flags, tag, units=["lr_bfv_relin"], stubs=["bfv_relin_stub"])
+    exe = build_host_driver(str(tmp_path), "bfv_relin_deg_driver", flags, tag)
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the routes, not the caller's env
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
