@@ -31,12 +31,27 @@
 //	        (MRed(x, s)).  Polynomial evaluation (EvaluatePoly*, EvaluateCheby*) calls these between its MulRelin / Rescale steps: with
 //	        the patch a whole evaluation stays on the device.  (Unpatched, the first statement `defer eval.hostLoop(ct0, ctOut)()` keeps
 //	        the upstream loops correct on resident ciphertexts at the price of one PCIe round trip per call.)
+//
+// The patch to upstream ckks/polynomial_evaluation.go:
+//
+//	delete  evaluatePolyFromPowerBasis :142-159 -> below: res = c0 + sum c_k C[k] as ONE ring.CkksLinCombConstants call (the scalar
+//	        lines of AddConst and of every MultByConstAndAdd, with the MultByConst calls on the receiver that equalise scales) and ONE
+//	        Context.CkksLinComb call (their element loops on both components: T + 1 row passes where T halfScalar calls move 3 T to
+//	        5 T), then eval.Rescale as upstream.  DEVIATION, stated here once: upstream walks `for key := range coeffs` over a Go map,
+//	        and every MultByConstAndAdd may rescale the receiver depending on the scales it meets, so upstream's output bits depend on
+//	        Go's randomised map order -- every order is one of its outputs.  The replacement sorts the keys ASCENDING: one of
+//	        upstream's outputs, the same on every run.  The 1e-15 filter on the coefficients is upstream's.  AddConst and
+//	        MultByConstAndAdd keep their patch above for their other callers (recurse, recurseCheby, evaluateInPlace call Add / Sub /
+//	        MulRelin / Rescale around this leaf and stay as they are).
+//
 //	keep    DropLevel :901 (it re-slices Coeffs: metadata; the device image is sized by cap(Coeffs) and keeps its stride), RescaleMany
 //	        :971 (Context.DivRoundByLastModulusManyNTT is a device call), Add / Sub / Neg / MulByPow2 / Reduce / ScaleUp (Context methods)
 package ckks
 
 import (
 	"errors"
+	"math"
+	"sort"
 	"sync"
 
 	"github.com/ldsec/lattigo/ring"
@@ -155,6 +170,46 @@ func (eval *evaluator) halfScalar(op int, level uint64, ct0, ctOut *Ciphertext, 
 		eval.resident(ct0.value[u], ctOut.value[u])
 		context.HalfScalarOp(op, level, ct0.value[u], lo, hi, ctOut.value[u])
 	}
+}
+
+// evaluatePolyFromPowerBasis (polynomial_evaluation.go:142): res = coeffs[0] + sum coeffs[k] C[k] over the keys in ascending order
+// (patch list above), the scalar side on the host and the element side as one device call, then upstream's Rescale.
+func evaluatePolyFromPowerBasis(coeffs map[uint64]complex128, C map[uint64]*Ciphertext, evaluator *evaluator, evakey *EvaluationKey) (res *Ciphertext) {
+	res = NewCiphertext(evaluator.params, 1, C[1].Level(), C[1].Scale())
+	kept := func(c complex128) bool { return math.Abs(real(c)) > 1e-15 || math.Abs(imag(c)) > 1e-15 }
+	var keys []uint64
+	for key := range coeffs {
+		if key != 0 && kept(coeffs[key]) {
+			keys = append(keys, key)
+		}
+	}
+	sort.Slice(keys, func(i, j int) bool { return keys[i] < keys[j] })
+	var c0 *complex128
+	if c, ok := coeffs[0]; ok && kept(c) {
+		c0 = &c
+	}
+	context := evaluator.ckksContext.contextQ
+	psi1 := make([]uint64, len(context.Modulus))
+	for i := range psi1 {
+		psi1[i] = context.GetNttPsi()[i][1]
+	}
+	terms := make([]ring.CkksLinCombTerm, len(keys))
+	polys := make([][2]*ring.Poly, len(keys))
+	for k, key := range keys {
+		ct := C[key]
+		terms[k] = ring.CkksLinCombTerm{Constant: coeffs[key], Scale: ct.Scale(), Level: ct.Level()}
+		evaluator.resident(ct.value[0], ct.value[1])
+		polys[k] = [2]*ring.Poly{ct.value[0], ct.value[1]}
+	}
+	consts := ring.CkksLinCombConstants(context.Modulus, psi1, evaluator.ckksContext.scale, res.Level(), res.Scale(), c0, terms)
+	if res.Level() > consts.LevelAfter {
+		evaluator.DropLevel(res, res.Level()-consts.LevelAfter)
+	}
+	res.SetScale(consts.ScaleAfter)
+	evaluator.resident(res.value[0], res.value[1])
+	context.CkksLinComb(polys, consts, false, [2]*ring.Poly{res.value[0], res.value[1]})
+	evaluator.Rescale(res, evaluator.ckksContext.scale, res)
+	return
 }
 
 // galoisElement recovers the Galois element from the NTT permutation table upstream passes around (ring.PermuteNTTIndex,

@@ -279,6 +279,69 @@ int lr_ewise(lr_context *ctx, int op, int level, const lr_poly *a, const lr_poly
  * op 0: CRed(x + s)   op 1: MRed(x, s)   op 2: CRed(out + MRed(x, s)).  lo / hi: level+1 host words each (the scalars as the
  * reference computes them: scaleUpExact + MForm, or nttPsi[i][1] and its negation).  in may be out. */
 int lr_half_scalar_op(lr_context *ctx, int op, int level, const lr_poly *in, const uint64_t *lo, const uint64_t *hi, lr_poly *out);
+
+/* ------------------------------------------------------------------ CKKS linear combination by constants */
+/* res = c0 + sum_k c_k ct_k over ciphertexts of degree 1: evaluatePolyFromPowerBasis (ckks/polynomial_evaluation.go:142-159), the leaf
+ * of recurse / recurseCheby and of anything that sums ciphertexts weighted by constants.  The reference runs
+ *     if has_const:  AddConst(res, c0, res)                 ckks/evaluator.go:373-444
+ *     for k = 0 .. n_terms-1, IN THE CALLER'S ORDER:
+ *                    MultByConstAndAdd(ct_k, c_k, res)      :451-608, with MultByConst :622-734 where it calls it (:530, :553)
+ * (it iterates a Go map there, so its own order -- and with it its output bits, because every step may rescale the receiver -- is
+ * random; the caller of these two entry points fixes one).  The chain is split into its scalar lines and its element loops.
+ *
+ * lr_ckks_lincomb_constants: the scalar lines (everything outside the `for j` / `for u` loops), literally.  HOST ONLY: no context, no
+ * device, thread-safe.  Constants are complex128 (re, im); the reference's float64 / uint64 / int64 / int cases are im = 0 with the
+ * same arithmetic.
+ *   in : moduli[n_moduli] and ntt_psi1[n_moduli] = the word GetNttPsi()[i][1] of each (lr_context_get_table NTT_PSI, entry 1);
+ *        default_scale = ckksContext.scale; the receiver's res_level / res_scale before the chain; has_const and c0; per term
+ *        term_re / term_im / term_scale / term_level [n_terms].
+ *   out: *level_after = min(res_level, every term_level) (DropLevel :457-460), *scale_after; with has_const add_lo / add_hi
+ *        [level_after+1]; has_pre[n_terms]; pre / lo / hi [n_terms][level_after+1], rows level_after+1 words apart.  pre[k] is the
+ *        Montgomery-form multiplier of the RECEIVER where the reference calls MultByConst(ctOut, ...) at :530 or :553 (has_pre[k] = 1;
+ *        real-valued, one word per limb; otherwise the row is zero); lo[k] / hi[k] are scaledConst after MForm for the coefficients
+ *        below / above N/2 (:585, :597); add_lo / add_hi are AddConst's scaledConst (:426, :437; no MForm).
+ *   DropLevel only lowers the receiver's level and the limbs above the final level are dropped, so words are produced for the limbs
+ *   0..level_after only, whatever level a step ran at: equivalent for the limbs that remain.
+ *   scaleUpExact (ckks/utils.go:22-49) is restated exactly: 53-bit products and a + 0.5 that rounds to even, truncation, and q itself
+ *   for a negative multiple of q.
+ *   QUIRK kept: :553 passes a float64 ratio to MultByConst; with a fractional part that call scales the ratio by the default scale
+ *   (:656-667) and the scale it sets (:733) is overwritten at :556 -- the receiver is then off by the default scale, as in the
+ *   reference.  The lines as they stand (as lr_ckks_encrypt_pk does below the top level).
+ *   Domain (Go's float-to-integer conversions are machine-specific out of range): finite constants with |re|, |im| < 2^63, finite
+ *   positive scales, every ratio the reference converts with uint64(...) below 2^63, every product constant * scale finite; moduli
+ *   odd, in [3, 2^61), each root word below its modulus; levels inside the moduli.  Outside it: LR_ERR_ARG and NOTHING is written.
+ *   Checked in this order, messages "CKKS linear combination constants: " + "null argument" | "a count or a level is out of range" |
+ *   "a modulus is even, below 3 or not below 2^61" | "a root word is not below its modulus" | "a scale is not finite and positive" |
+ *   "a constant is not finite and below 2^63 in magnitude" | then, in chain order, "a scale ratio is not below 2^63" |
+ *   "a constant times its scale is not finite". */
+int lr_ckks_lincomb_constants(const uint64_t *moduli, const uint64_t *ntt_psi1, int n_moduli, double default_scale, int res_level,
+                              double res_scale, int has_const, double c0_re, double c0_im, int n_terms, const double *term_re,
+                              const double *term_im, const double *term_scale, const int *term_level, int *level_after,
+                              double *scale_after, uint64_t *add_lo, uint64_t *add_hi, uint8_t *has_pre, uint64_t *pre, uint64_t *lo,
+                              uint64_t *hi);
+/* lr_ckks_lincomb: the element loops of the same chain as one device call.  Per limb i <= level, coefficient j and component u, with
+ * s(j) = j < N/2 ? lo : hi:
+ *     acc_u = accumulate ? out_u[i][j] : 0
+ *     if add_lo:      acc_0 = CRed(acc_0 + add(j)[i])                         (component 0 only; AddConst :433, :441)
+ *     for k in order: if has_pre[k]: acc_u = MRed(acc_u, pre[k][i])           (MultByConst :715, :728)
+ *                     acc_u = CRed(acc_u + MRed(x_{k,u}[i][j], s_k(j)[i]))    (:591, :604)
+ *     out_u[i][j] = acc_u
+ * -- the same bits as lr_half_scalar_op with op 0, then per term op 1 and op 2, on a receiver zeroed when accumulate == 0, for every
+ * input that sequence accepts (values need not be canonical).  One streaming pass per sixteen terms (T + 1 row passes per component
+ * where the sequence moves 3 T to 5 T); more terms are chained through the receiver.  n_terms >= 0, no upper limit; n_terms == 0
+ * with a constant is a valid call.  has_pre / pre / lo / hi: host arrays [n_terms] and [n_terms][level+1] (rows level+1 words apart:
+ * lr_ckks_lincomb_constants' layout at level = level_after); add_lo / add_hi [level+1], or both NULL.  Every term and the receiver
+ * carry the same batch (at most 32767); a term may appear twice; no term may share memory with a receiver poly; out_c0 != out_c1.
+ * The constants travel in the launches' arguments: asynchronous on the context's stream, no host synchronisation, capturable.
+ * Checks, in this order; a refused call writes nothing.  Messages "CKKS linear combination: " +
+ *   LR_ERR_ARG          "null argument" | "n_terms is negative" | "a term is null" | "add_lo and add_hi come together or not at all" |
+ *                       "the two components of the receiver share memory" | "a term shares memory with the receiver"
+ *   LR_ERR_SHAPE        "level out of range" | "ring degree mismatch" | "a poly has fewer limbs than level + 1" |
+ *                       "every term and the receiver carry the same batch" | "batch above 32767"
+ *   LR_ERR_UNSUPPORTED  "ring degree below 4" */
+int lr_ckks_lincomb(lr_context *ctxQ, int level, int n_terms, const lr_poly *const *terms_c0, const lr_poly *const *terms_c1,
+                    const uint8_t *has_pre, const uint64_t *pre, const uint64_t *lo, const uint64_t *hi, const uint64_t *add_lo,
+                    const uint64_t *add_hi, int accumulate, lr_poly *out_c0, lr_poly *out_c1);
 /* ring.PermuteNTT (ring/ring_galois.go:55) on limbs 0..level: out[i][j] = in[i][index(j)], index(j) =
  * bitrev(((gen * (2*bitrev(j)+1) mod 2N) - 1) / 2), computed on the fly.  PermuteNTTWithIndex (:89) with the
  * table of PermuteNTTIndex(gen, power, N) (:29) is the same call with gen^power mod 2N.  Not in place

@@ -26,6 +26,55 @@ inline void check(int rc) {
 
 class Context;
 
+// What the scalar lines of res = c0 + sum c_k ct_k yield (lr_ckks_lincomb_constants: evaluatePolyFromPowerBasis' chain of AddConst and
+// MultByConstAndAdd, ckks/polynomial_evaluation.go:142-159, in the caller's order): Context::CkksLinComb takes it as it is.
+struct CkksLinCombConsts {
+    int level_after = 0;
+    double scale_after = 0;
+    bool has_const = false;
+    std::vector<uint64_t> add_lo, add_hi;      // [level_after + 1] with has_const
+    std::vector<uint8_t> has_pre;              // [terms]
+    std::vector<uint64_t> pre, lo, hi;         // [terms][level_after + 1]
+};
+struct CkksLinCombTerm {
+    std::complex<double> constant;
+    double scale;
+    int level;
+};
+// host only: no context, no device.  nttPsi1[i] = GetNttPsi()[i][1]
+inline CkksLinCombConsts CkksLinCombConstants(const std::vector<uint64_t> &moduli, const std::vector<uint64_t> &nttPsi1, double defaultScale,
+                                              int resLevel, double resScale, const std::complex<double> *c0,
+                                              const std::vector<CkksLinCombTerm> &terms) {
+    const size_t T = terms.size(), L = moduli.size();
+    if (nttPsi1.size() != L) throw Error(LR_ERR_ARG, "CkksLinCombConstants: one root word per modulus");
+    std::vector<double> re(T), im(T), sc(T);
+    std::vector<int> lv(T);
+    for (size_t k = 0; k < T; ++k) {
+        re[k] = terms[k].constant.real();
+        im[k] = terms[k].constant.imag();
+        sc[k] = terms[k].scale;
+        lv[k] = terms[k].level;
+    }
+    CkksLinCombConsts r;
+    r.has_const = c0 != nullptr;
+    r.add_lo.resize(L);
+    r.add_hi.resize(L);
+    r.has_pre.resize(T);
+    r.pre.resize(T * L);
+    r.lo.resize(T * L);
+    r.hi.resize(T * L);
+    check(lr_ckks_lincomb_constants(moduli.data(), nttPsi1.data(), (int)L, defaultScale, resLevel, resScale, c0 ? 1 : 0, c0 ? c0->real() : 0,
+                                    c0 ? c0->imag() : 0, (int)T, re.data(), im.data(), sc.data(), lv.data(), &r.level_after, &r.scale_after,
+                                    r.add_lo.data(), r.add_hi.data(), r.has_pre.data(), r.pre.data(), r.lo.data(), r.hi.data()));
+    const size_t L1 = (size_t)r.level_after + 1;
+    r.add_lo.resize(r.has_const ? L1 : 0);
+    r.add_hi.resize(r.has_const ? L1 : 0);
+    r.pre.resize(T * L1);
+    r.lo.resize(T * L1);
+    r.hi.resize(T * L1);
+    return r;
+}
+
 // ring.Poly (ring/ring_object.go:11-13) as a device-resident batch; Coeffs mirrors [][]uint64 on demand
 class Poly {
   public:
@@ -125,6 +174,20 @@ class Context {
     // ring/ring_galois.go
     void PermuteNTT(const Poly *polIn, uint64_t gen, Poly *polOut) const { check(lr_permute_ntt(h_, full(), polIn->handle(), gen, polOut->handle())); }   // :55
     void Permute(const Poly *polIn, uint64_t gen, Poly *polOut) const { check(lr_permute(h_, polIn->handle(), gen, polOut->handle())); }                  // :106
+
+    // res = c0 + sum c_k ct_k at level consts.level_after, both components in one device call (lr_ckks_lincomb); terms[k] = {c0, c1} of ct_k
+    void CkksLinComb(const std::vector<std::pair<const Poly *, const Poly *>> &terms, const CkksLinCombConsts &consts, Poly *out0, Poly *out1,
+                     bool accumulate = false) const {
+        std::vector<const lr_poly *> t0, t1;
+        for (const auto &t : terms) {
+            t0.push_back(t.first->handle());
+            t1.push_back(t.second->handle());
+        }
+        if (consts.has_pre.size() != terms.size()) throw Error(LR_ERR_ARG, "CkksLinComb: the constants are those of another term count");
+        check(lr_ckks_lincomb(h_, consts.level_after, (int)terms.size(), t0.data(), t1.data(), consts.has_pre.data(), consts.pre.data(),
+                              consts.lo.data(), consts.hi.data(), consts.has_const ? consts.add_lo.data() : nullptr,
+                              consts.has_const ? consts.add_hi.data() : nullptr, accumulate ? 1 : 0, out0->handle(), out1->handle()));
+    }
 
     void Sync() const { check(lr_context_sync(h_)); }
 

@@ -287,6 +287,42 @@ struct HalfScalarLaunch {
     LimbScalars lo, hi;
 };
 
+// res = c0 + sum c_k ct_k (lr_ckks_lincomb.hip): evaluatePolyFromPowerBasis' chain AddConst, MultByConstAndAdd ... (ckks/
+// polynomial_evaluation.go:142-159) on both components of a degree-1 ciphertext in one pass.  Per limb, coefficient j and component u:
+//   acc = accumulate ? out_u : 0;  component 0 with has_add: acc = CRed(acc + (j < n/2 ? add_lo : add_hi))
+//   for k < count: bit k of pre_mask: acc = MRed(acc, pre_k);  acc = CRed(acc + MRed(x_k,u, j < n/2 ? lo_k : hi_k))
+// -- HalfScalarLaunch's op 0, then per term op 1 and op 2, with the accumulator in registers.  The constants travel in the kernel
+// arguments (no table on the device, no copy, nothing to synchronise; a captured launch carries them): per limb of the launch
+// lincomb_limb_words words in `k` -- add_lo, add_hi when has_add, then (pre, lo, hi) per term -- so a launch covers
+// lincomb_limbs_per_launch limbs from limb0 on and a workgroup reads its own limb's words at wave-uniform addresses.
+constexpr int kLinCombTerms = 16;        // terms whose addresses travel in one launch
+constexpr int kLinCombWords = 384;       // words of constants in one launch: eight limbs of sixteen terms
+struct LinCombTermRef {
+    const u64 *c[2];
+    long long stride[2];                 // between batch polys
+};
+struct LinCombLaunch {
+    LinCombTermRef term[kLinCombTerms];
+    u64 *out[2];
+    long long out_stride[2];
+    int n, count, limb0, accumulate, has_add;
+    unsigned pre_mask;
+    const LimbParams *lp;
+    u64 k[kLinCombWords];
+};
+static_assert(sizeof(LinCombLaunch) <= 4096, "LinCombLaunch travels by value in the kernel arguments");
+LR_HD int lincomb_limb_words(int count, int has_add) { return 3 * count + (has_add ? 2 : 0); }
+inline int lincomb_limbs_per_launch(int count, int has_add) {
+    const int w = lincomb_limb_words(count, has_add);
+    return w == 0 || kLinCombWords / w > kMaxLimbs ? kMaxLimbs : kLinCombWords / w;
+}
+hipError_t launch_ckks_lincomb(const LinCombLaunch &L, int limbs, int batch, hipStream_t stream);
+// (component on grid z next to the batch member: 2 * batch <= 65535)
+inline LaunchVerdict launch_verdict(const LinCombLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 4 || L.count < 0 || L.count > kLinCombTerms || L.limb0 < 0 || L.limb0 + limbs > kMaxLimbs ||
+                                                        limbs > lincomb_limbs_per_launch(L.count, L.has_add) || batch > 32767);
+}
+
 // key-switch inner product over all digits (lr_ewise.hip)
 struct KeyMacLaunch {
     const u64 *c2;                 // [beta][batch][limbs][N], NTT domain

@@ -368,6 +368,30 @@ class Context:
         check(lib().lr_half_scalar_op(self.h, {"ADD": 0, "MRED": 1, "MRED_ADD": 2}[op], level, p1.h, lo.ctypes.data_as(C.c_void_p),
                                       hi.ctypes.data_as(C.c_void_p), p2.h))
 
+    def CkksLinComb(self, level, terms, consts, add=None, accumulate=False, out=None):
+        """res = c0 + sum c_k ct_k on both components of degree-1 ciphertexts in one device call (lr_ckks_lincomb): the element loops of
+        evaluatePolyFromPowerBasis' chain (ckks/polynomial_evaluation.go:142-159), AddConst once and per term MultByConst on the receiver
+        where the reference equalises scales and MultByConstAndAdd, in the terms' order.  terms: [(c0, c1), ...] Polys; consts: a
+        CkksLinCombConsts (ckks_lincomb_constants) or anything with has_pre [T], pre / lo / hi [T][level+1]; add: (add_lo, add_hi) of
+        level+1 words each, or None; accumulate: on top of the receiver instead of zero; out: (out0, out1).  The same bits as HalfScalarOp
+        "ADD", then per term "MRED" and "MRED_ADD"."""
+        T, L1 = len(terms), level + 1
+
+        def words(a, n, what, dtype=np.uint64):
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            if a.size != n:
+                raise LatticeRingError(3, "CkksLinComb: need %d words in %s" % (n, what))
+            return a
+        has_pre = words(consts.has_pre, T, "has_pre", np.uint8)
+        pre, lo, hi = (words(getattr(consts, n), T * L1, n) for n in ("pre", "lo", "hi"))
+        a_lo, a_hi = (None, None) if add is None else (words(add[0], L1, "add_lo"), words(add[1], L1, "add_hi"))
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)
+        t0 = (C.c_void_p * max(T, 1))(*[t[0].h.value for t in terms])
+        t1 = (C.c_void_p * max(T, 1))(*[t[1].h.value for t in terms])
+        check(lib().lr_ckks_lincomb(self.h, level, T, t0, t1, ptr(has_pre), ptr(pre), ptr(lo), ptr(hi), ptr(a_lo), ptr(a_hi),
+                                    1 if accumulate else 0, out[0].h, out[1].h))
+        return out
+
     def MultByMonomial(self, p1, monomialDeg, p2):  # ring/ring.go:663
         check(lib().lr_mult_by_monomial(self.h, p1.h, int(monomialDeg), p2.h))
 
@@ -436,6 +460,42 @@ def PermuteNTTIndex(gen, power, N):
 def PermuteNTT(context, polIn, gen, polOut):
     """ring.PermuteNTT (ring/ring_galois.go:55): all limbs of polIn"""
     context.PermuteNTTLvl(polIn.limbs - 1, polIn, gen, polOut)
+
+
+class CkksLinCombConsts:
+    """what ckks_lincomb_constants yields: level_after, scale_after, add = (add_lo, add_hi) or None, has_pre [T], pre / lo / hi
+    [T][level_after + 1]"""
+
+    def __init__(self, level_after, scale_after, add, has_pre, pre, lo, hi):
+        self.level_after, self.scale_after, self.add = level_after, scale_after, add
+        self.has_pre, self.pre, self.lo, self.hi = has_pre, pre, lo, hi
+
+
+def ckks_lincomb_constants(moduli, ntt_psi1, default_scale, res_level, res_scale, terms, c0=None):
+    """The scalar lines of res = c0 + sum c_k ct_k as the reference runs it (lr_ckks_lincomb_constants; evaluatePolyFromPowerBasis,
+    ckks/polynomial_evaluation.go:142-159: AddConst(res, c0, res) if c0 is given, then MultByConstAndAdd(ct_k, c_k, res) in the terms'
+    order, with the MultByConst calls on the receiver that equalise scales).  Host only: needs no context and no device.
+    moduli, ntt_psi1: the moduli and per limb the word GetNttPsi()[i][1]; default_scale: ckksContext.scale; res_level, res_scale: the
+    receiver before the chain; terms: [(constant, scale, level), ...] with complex (or real) constants.  Returns a CkksLinCombConsts."""
+    moduli = [int(q) for q in moduli]
+    L, T = len(moduli), len(terms)
+    cs = [complex(t[0]) for t in terms]
+    dbl = lambda vals: (C.c_double * max(len(vals), 1))(*[float(v) for v in vals])
+    lv = (C.c_int * max(T, 1))(*[int(t[2]) for t in terms])
+    level_after, scale_after = C.c_int(0), C.c_double(0.0)
+    add_lo, add_hi = np.zeros(L, dtype=np.uint64), np.zeros(L, dtype=np.uint64)
+    has_pre = np.zeros(max(T, 1), dtype=np.uint8)
+    pre, lo, hi = (np.zeros(max(T * L, 1), dtype=np.uint64) for _ in range(3))
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    z = complex(c0) if c0 is not None else 0j
+    check(lib().lr_ckks_lincomb_constants(_u64(moduli), _u64(ntt_psi1), L, float(default_scale), int(res_level), float(res_scale),
+                                          0 if c0 is None else 1, z.real, z.imag, T, dbl([c.real for c in cs]), dbl([c.imag for c in cs]),
+                                          dbl([t[1] for t in terms]), lv, C.byref(level_after), C.byref(scale_after), ptr(add_lo), ptr(add_hi),
+                                          ptr(has_pre), ptr(pre), ptr(lo), ptr(hi)))
+    L1 = level_after.value + 1
+    rows = lambda a: a[:T * L1].reshape(T, L1).copy()
+    return CkksLinCombConsts(level_after.value, scale_after.value, None if c0 is None else (add_lo[:L1].copy(), add_hi[:L1].copy()),
+                             has_pre[:T].copy(), rows(pre), rows(lo), rows(hi))
 
 
 def NewContextWithParams(N, Moduli, device=0, options=None):
