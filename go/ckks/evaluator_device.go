@@ -41,11 +41,12 @@
 //	        and every MultByConstAndAdd may rescale the receiver depending on the scales it meets, so upstream's output bits depend on
 //	        Go's randomised map order -- every order is one of its outputs.  The replacement sorts the keys ASCENDING: one of
 //	        upstream's outputs, the same on every run.  The 1e-15 filter on the coefficients is upstream's.  AddConst and
-//	        MultByConstAndAdd keep their patch above for their other callers (recurse, recurseCheby, evaluateInPlace call Add / Sub /
-//	        MulRelin / Rescale around this leaf and stay as they are).
+//	        MultByConstAndAdd keep their patch above for their other callers (recurse and recurseCheby call Add / MulRelin / Rescale
+//	        around this leaf and stay as they are; Add / AddNoMod / Sub / SubNoMod with evaluateInPlace, computePowerBasisCheby and the
+//	        head of EvaluateChebyFast / Eco have their replacement bodies and their patch list in combine_device.go).
 //
 //	keep    DropLevel :901 (it re-slices Coeffs: metadata; the device image is sized by cap(Coeffs) and keeps its stride), RescaleMany
-//	        :971 (Context.DivRoundByLastModulusManyNTT is a device call), Add / Sub / Neg / MulByPow2 / Reduce / ScaleUp (Context methods)
+//	        :971 (Context.DivRoundByLastModulusManyNTT is a device call), Neg / MulByPow2 / Reduce / ScaleUp (Context methods)
 package ckks
 
 import (

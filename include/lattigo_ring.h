@@ -342,6 +342,84 @@ int lr_ckks_lincomb_constants(const uint64_t *moduli, const uint64_t *ntt_psi1, 
 int lr_ckks_lincomb(lr_context *ctxQ, int level, int n_terms, const lr_poly *const *terms_c0, const lr_poly *const *terms_c1,
                     const uint8_t *has_pre, const uint64_t *pre, const uint64_t *lo, const uint64_t *hi, const uint64_t *add_lo,
                     const uint64_t *add_hi, int accumulate, lr_poly *out_c0, lr_poly *out_c1);
+/* ------------------------------------------------------------------ CKKS Add / Sub of any scale, level and degree */
+/* evaluator.Add / AddNoMod / Sub / SubNoMod (ckks/evaluator.go:153-211) through evaluateInPlace (:227-342): the step between two products
+ * of recurse / recurseCheby (MulRelin, Add(res, tmp, res), Rescale) and of computePowerBasisCheby (ckks/chebyshev_evaluation.go:86-99).
+ * It is not a plain AddLvl: where the operands' scales differ the one of the smaller scale is first multiplied by uint64(ratio) with
+ * MultByConst -- into the evaluator's pool ciphertext, or in place when that operand is the receiver --, the components that one operand
+ * has beyond the other are copied, and Sub / SubNoMod negate them afterwards when they come from the subtrahend (:186-192, :203-209).
+ * Split as the linear combination above: the scalar lines and the element loops.
+ *
+ * lr_ckks_combine_constants: the scalar lines of evaluateInPlace and the degree rules of its four callers, literally.  HOST ONLY: no
+ * context, no device, thread-safe.
+ *   in : moduli[n_moduli]; op = LR_ADD | LR_ADD_NOMOD | LR_SUB | LR_SUB_NOMOD; degree (0..2), level and scale of operand a (op0), of
+ *        operand b (op1) and of the receiver before the call; receiver = which operand the receiver is (lr_ckks_combine_receiver; BOTH:
+ *        a is b is the receiver, Add(C, C, C)).  A receiver that is an operand carries that operand's degree, level and scale.
+ *   out: *level_after = the minimum of the three levels (:231); *scale_after = the larger scale (:328); *degree_after = the larger
+ *        operand degree (Resize :237 -- a receiver of higher degree is cut down to it); *mult_side = 0 none, 1 a, 2 b: in each of the
+ *        three branches :243-322 the operand of the SMALLER scale; mult[level_after+1] = per limb MForm(scaleUpExact(float64(r), 1, q_i))
+ *        with r = uint64(larger / smaller) (:669-671, :698-709), written only when *mult_side != 0.
+ *   The ratio is truncated: 1.5 multiplies by 1, and the multiplication still takes place (MRed by MForm(1) reduces the operand), as
+ *   in the reference.  The uint64 reaches MultByConst's float64 (:670), so above 2^53 it is rounded before scaleUpExact sees it.
+ *   Levels: the receiver is dropped by ctOut.Level() - min(a.Level, b.Level) (:238, DropLevel :901-914); one already at level 0 is left
+ *   alone (the error return is ignored); the words are produced for the limbs 0..level_after, which is all that the element loops read.
+ *   Where the reference panics the call returns LR_ERR_UNSUPPORTED: both operands of degree 0 (:117); a receiver whose degree is below
+ *   the larger operand degree (:121); a receiver above level 0 and below both operand levels (the difference at :238 wraps and :910
+ *   slices out of range); an operand to be multiplied that has degree 2 and is not the receiver (it would be written into the pool
+ *   ciphertext of degree 1, :106, and MultByConst :711-716 indexes out of range).
+ *   Domain, as for lr_ckks_lincomb_constants: finite positive scales, the ratio below 2^63, moduli odd and in [3, 2^61).  Outside it:
+ *   LR_ERR_ARG.  Inside it the reference's guards `uint64(ratio) != 0` (:249, :255, :275, :281, :302, :312) cannot fail: x > y > 0 gives
+ *   x / y >= 1.  A refused call writes NOTHING.
+ *   Checked in this order, messages "CKKS combine constants: " +
+ *   LR_ERR_ARG          "null argument" | "a count, the operation, the receiver, a degree or a level is out of range" |
+ *                       "a modulus is even, below 3 or not below 2^61" | "a scale is not finite and positive" |
+ *                       "the receiver is an operand and differs from it in degree, level or scale" | "a scale ratio is not below 2^63"
+ *   LR_ERR_UNSUPPORTED  "both operands have degree 0" | "the receiver's degree is below the larger operand degree" |
+ *                       "the receiver lies above level 0 and below both operand levels" |
+ *                       "the operand to be multiplied has degree 2 and is not the receiver" */
+typedef enum lr_ckks_combine_receiver {
+    LR_COMBINE_OUT_NEW = 0,     /* neither operand                  the third branch, :296 */
+    LR_COMBINE_OUT_A = 1,       /* ctOut == c0                      :243 */
+    LR_COMBINE_OUT_B = 2,       /* ctOut == c1                      :270 */
+    LR_COMBINE_OUT_BOTH = 3     /* ctOut == c0 == c1                :243 with equal scales */
+} lr_ckks_combine_receiver;
+int lr_ckks_combine_constants(const uint64_t *moduli, int n_moduli, int op, int a_degree, int a_level, double a_scale, int b_degree,
+                              int b_level, double b_scale, int out_degree, int out_level, double out_scale, int receiver,
+                              int *level_after, double *scale_after, int *degree_after, int *mult_side, uint64_t *mult);
+/* lr_ckks_combine: the element loops as one device call.  Per limb i <= level, coefficient j and component u <= max(a_degree, b_degree),
+ * with s(j) = j < N/2 ? lo : hi:
+ *     x = a_u[i][j]               (u <= a_degree)            y = b_u[i][j]      (b given and u <= b_degree)
+ *     if double_a:  x = CRed(x + x)                          Add(C, C, C) of computePowerBasisCheby, chebyshev_evaluation.go:92
+ *     if ma:        x = MRed(x, ma(j)[i])                    MultByConst :715, :728
+ *     if mb:        y = MRed(y, mb(j)[i])
+ *     both present: r = CRed(x + y) | x + y | CRed((x + q) - y) | (x + q) - y              ring/ring.go:26, :48, :70, :94
+ *     only x:       r = x                                    CopyLvl :335
+ *     only y:       r = y for the two additions, q - y for the two subtractions            :339, NegLvl :190 / :207 (q - 0 stays q)
+ *     if add and u == 0:  r = CRed(r + add(j)[i])            AddConst :433, :441
+ *     out_u[i][j] = r
+ * -- the same bits as today's sequence of lr_half_scalar_op (op 1, op 0) and lr_ewise (ADD.., NEG, COPY) calls on every input that
+ * sequence accepts (values need not be canonical): all of evaluateInPlace with Sub's tail; the Chebyshev step 2 x - r y; 2 x + constant
+ * (b NULL); the affine head m x + c of EvaluateCheby* (b NULL, ma_lo != ma_hi).  a: a_degree+1 polys; b: b_degree+1 polys, or NULL
+ * (b_degree is then not read, and op only has to be valid); out: max(a_degree, b_degree)+1 polys.  ma / mb / add: (lo, hi) host arrays
+ * of level+1 words each, or both NULL -- lr_ckks_combine_constants' mult for lo and hi alike; the words of AddConst and of a complex
+ * MultByConst are the caller's, as for lr_half_scalar_op (lr_ckks_lincomb_constants with n_terms == 0 yields AddConst's).
+ * Memory: out_u may be the very poly a_u or b_u (upstream's in-place case; every element is read before it is written); any other
+ * overlap with the receiver is refused.  An operand poly may have batch 1 and is then read for every member; otherwise all batches are
+ * equal, at most 32767 (21845 with three components: component and member share one grid axis).
+ * The constants travel in the launch's arguments, every limb in one launch: asynchronous on the context's stream, no host
+ * synchronisation, capturable.  Checks, in this order; a refused call writes nothing.  Messages "CKKS combine: " +
+ *   LR_ERR_ARG          "null argument" | "no operand given" | "the operation is not LR_ADD, LR_ADD_NOMOD, LR_SUB or LR_SUB_NOMOD" |
+ *                       "a degree is outside 0..2" | "a component is null" |
+ *                       "the two words of a multiplier or of the constant come together or not at all" | "a multiplier of b without b" |
+ *                       "the components of the receiver share memory" |
+ *                       "an operand shares memory with the receiver other than component by component in place"
+ *   LR_ERR_SHAPE        "level out of range" | "ring degree mismatch" | "a poly has fewer limbs than level + 1" |
+ *                       "the receiver's components carry one batch, an operand that batch or 1" | "batch above 32767" |
+ *                       "batch above 21845 at degree 2"
+ *   LR_ERR_UNSUPPORTED  "ring degree below 4" */
+int lr_ckks_combine(lr_context *ctxQ, int op, int level, int a_degree, const lr_poly *const *a, int b_degree, const lr_poly *const *b,
+                    int double_a, const uint64_t *ma_lo, const uint64_t *ma_hi, const uint64_t *mb_lo, const uint64_t *mb_hi,
+                    const uint64_t *add_lo, const uint64_t *add_hi, lr_poly *const *out);
 /* ring.PermuteNTT (ring/ring_galois.go:55) on limbs 0..level: out[i][j] = in[i][index(j)], index(j) =
  * bitrev(((gen * (2*bitrev(j)+1) mod 2N) - 1) / 2), computed on the fly.  PermuteNTTWithIndex (:89) with the
  * table of PermuteNTTIndex(gen, power, N) (:29) is the same call with gen^power mod 2N.  Not in place

@@ -5,6 +5,7 @@
 // order and meaning follow the reference (github.com/ldsec/lattigo/ring v1.3.1); where Go panics, these
 // throw ring::Error.  Header-only; link with -llattigo_ring_hip.
 #pragma once
+#include <algorithm>
 #include <complex>
 #include <cstdint>
 #include <stdexcept>
@@ -72,6 +73,32 @@ inline CkksLinCombConsts CkksLinCombConstants(const std::vector<uint64_t> &modul
     r.pre.resize(T * L1);
     r.lo.resize(T * L1);
     r.hi.resize(T * L1);
+    return r;
+}
+
+// What the scalar lines of evaluator.Add / AddNoMod / Sub / SubNoMod yield (lr_ckks_combine_constants: evaluateInPlace,
+// ckks/evaluator.go:227-342, and its callers' degree rules): the result's level, scale and degree, which operand MultByConst multiplies
+// (0 none, 1 a, 2 b) and by which Montgomery-form word per limb.
+struct CkksCombineOperand {
+    int degree;
+    int level;
+    double scale;
+};
+struct CkksCombineConsts {
+    int level_after = 0;
+    double scale_after = 0;
+    int degree_after = 0;
+    int mult_side = 0;
+    std::vector<uint64_t> mult;                // [level_after + 1] with mult_side != 0
+};
+// host only: no context, no device.  receiver: lr_ckks_combine_receiver
+inline CkksCombineConsts CkksCombineConstants(const std::vector<uint64_t> &moduli, int op, const CkksCombineOperand &a, const CkksCombineOperand &b,
+                                              const CkksCombineOperand &out, int receiver) {
+    CkksCombineConsts r;
+    r.mult.resize(moduli.size() ? moduli.size() : 1);
+    check(lr_ckks_combine_constants(moduli.data(), (int)moduli.size(), op, a.degree, a.level, a.scale, b.degree, b.level, b.scale, out.degree,
+                                    out.level, out.scale, receiver, &r.level_after, &r.scale_after, &r.degree_after, &r.mult_side, r.mult.data()));
+    r.mult.resize(r.mult_side ? (size_t)r.level_after + 1 : 0);
     return r;
 }
 
@@ -187,6 +214,26 @@ class Context {
         check(lr_ckks_lincomb(h_, consts.level_after, (int)terms.size(), t0.data(), t1.data(), consts.has_pre.data(), consts.pre.data(),
                               consts.lo.data(), consts.hi.data(), consts.has_const ? consts.add_lo.data() : nullptr,
                               consts.has_const ? consts.add_hi.data() : nullptr, accumulate ? 1 : 0, out0->handle(), out1->handle()));
+    }
+
+    // out = a (+|-) b over ciphertexts of any degree in one device call (lr_ckks_combine): a, b, out = the components' polys (b empty: no
+    // b); ma / mb / add = {lo, hi} words of level + 1 each, or null; op = LR_ADD | LR_ADD_NOMOD | LR_SUB | LR_SUB_NOMOD
+    using HalfWords = std::pair<std::vector<uint64_t>, std::vector<uint64_t>>;
+    void CkksCombine(int op, int level, const std::vector<const Poly *> &a, const std::vector<const Poly *> &b, const std::vector<Poly *> &out,
+                     bool doubleA = false, const HalfWords *ma = nullptr, const HalfWords *mb = nullptr, const HalfWords *add = nullptr) const {
+        std::vector<const lr_poly *> ha, hb;
+        std::vector<lr_poly *> ho;
+        for (const Poly *p : a) ha.push_back(p->handle());
+        for (const Poly *p : b) hb.push_back(p->handle());
+        for (Poly *p : out) ho.push_back(p->handle());
+        const size_t comps = std::max(ha.size(), hb.size());
+        if (ha.empty() || ha.size() > 3 || hb.size() > 3 || ho.size() < comps) throw Error(LR_ERR_ARG, "CkksCombine: one to three components per operand, the receiver the larger count");
+        for (const HalfWords *w : {ma, mb, add})
+            if (w && (w->first.size() < (size_t)level + 1 || w->second.size() < (size_t)level + 1)) throw Error(LR_ERR_ARG, "CkksCombine: need level + 1 words in each half");
+        const auto lo = [](const HalfWords *w) { return w ? w->first.data() : nullptr; };
+        const auto hi = [](const HalfWords *w) { return w ? w->second.data() : nullptr; };
+        check(lr_ckks_combine(h_, op, level, (int)ha.size() - 1, ha.data(), (int)hb.size() - 1, hb.empty() ? nullptr : hb.data(), doubleA ? 1 : 0, lo(ma),
+                              hi(ma), lo(mb), hi(mb), lo(add), hi(add), ho.data()));
     }
 
     void Sync() const { check(lr_context_sync(h_)); }

@@ -80,6 +80,9 @@ SYMBOLS = {
     "lr_ckks_lincomb_constants": [vp, vp, i32, C.c_double, i32, C.c_double, i32, C.c_double, C.c_double, i32, vp, vp, vp, vp,
                                   C.POINTER(i32), C.POINTER(C.c_double), vp, vp, vp, vp, vp, vp],
     "lr_ckks_lincomb": [vp, i32, i32, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lr_ckks_combine_constants": [vp, i32, i32, i32, i32, C.c_double, i32, i32, C.c_double, i32, i32, C.c_double, i32, C.POINTER(i32),
+                                  C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32), vp],
+    "lr_ckks_combine": [vp, i32, i32, i32, C.POINTER(vp), i32, C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
     "lr_permute_ntt": [vp, i32, vp, u64, vp],
     "lr_permute_ntt_index": [u64, u64, u64, u64p],
     "lr_permute": [vp, vp, u64, vp],

@@ -4,92 +4,16 @@
 //   lr_ckks_lincomb             the element side, one streaming pass per sixteen terms (lr_ckks_lincomb.hip)
 // The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launcher
 // it calls has a stand-in of its own (tests/cpp/ckks_lincomb_stub.cpp).
-#include <cmath>
-
-#include "lr_host.hpp"
+#include "lr_ckks_scalar.hpp"
 
 namespace lr_host {
 namespace {
+using namespace ckks_scalar;      // the scalar side: scaleUpExact, the half-vector words, the domain (shared with lr_ckks_combine.cpp)
 
 const char *const kWho = "CKKS linear combination: ";
 const char *const kWhoConst = "CKKS linear combination constants: ";
 
-// ---- the scalar side -------------------------------------------------------------------------------------------------------------
-const double kTwo63 = 9223372036854775808.0;
-
-// Go's uint64(f) / int64(f) are machine-specific out of range: the domain ends below 2^63 on either side
-bool magnitude_ok(double f) { return std::isfinite(f) && std::fabs(f) < kTwo63; }
-bool scale_ok(double f) { return std::isfinite(f) && f > 0; }
-
-// the integer part of a finite w >= 0, modulo q: below 2^64 the truncated word, above it mant * 2^e with e >= 12
-u64 trunc_mod(double w, u64 q) {
-    if (w < 18446744073709551616.0) return (u64)w % q;
-    int e2 = 0;
-    const double m = std::frexp(w, &e2);                      // w = m * 2^e2, 0.5 <= m < 1
-    const u64 mant = (u64)std::ldexp(m, 53);                  // exact: 53 bits
-    u128 p = 1 % q, b = 2 % q;
-    for (int e = e2 - 53; e; e >>= 1) {
-        if (e & 1) p = p * b % q;
-        b = b * b % q;
-    }
-    return (u64)((u128)(mant % q) * p % q);
-}
-
-// scaleUpExact (ckks/utils.go:22-49): big.NewFloat has 53 bits, so n * value and the + 0.5 round as doubles do (ties to even), Int()
-// truncates, and a negative value whose remainder is zero gives q, not 0.  The restatement the CKKS encoder's kernel carries
-// (scale_up_store, lr_ckks_encode.hip), for one modulus on the host.
-u64 scale_up_exact(double value, double n, u64 q) {
-    const bool neg = value < 0;
-    const double y = neg ? -n * value : n * value;
-    const u64 r = trunc_mod(y + 0.5, q);
-    return neg ? q - r : r;
-}
-
-// "determines if a scaling is required (which is the case if either real or imag have a rational part)", :466-488, :632-654
-bool has_fraction(double v) {
-    if (v == 0) return false;
-    const int64_t value_int = (int64_t)v;
-    return v - (double)value_int != 0;
-}
-
-struct Limb {
-    u64 q, qinv, psi;
-    BarrettConst bred;
-};
-
-// scaledConst for the coefficients below and above N / 2, before any MForm (:413-427, :436-438; :570-583, :595-596; :694-707, :719-720)
-void half_constants(double re, double im, double scale, const Limb &m, u64 *lo, u64 *hi) {
-    u64 sc = 0, sc_real = 0, sc_imag = 0;
-    if (re != 0) {
-        sc_real = scale_up_exact(re, scale, m.q);
-        sc = sc_real;
-    }
-    if (im != 0) {
-        sc_imag = mred(scale_up_exact(im, scale, m.q), m.psi, m.q, m.qinv);
-        sc = cred(sc + sc_imag, m.q);
-    }
-    *lo = sc;
-    if (im != 0) sc = cred(sc_real + (m.q - sc_imag), m.q);
-    *hi = sc;
-}
-
-// the same after MForm (:585, :597; :709, :721): with a real constant the second half keeps the first half's word
-void half_constants_mform(double re, double im, double scale, const Limb &m, u64 *lo, u64 *hi) {
-    u64 l, h;
-    half_constants(re, im, scale, m, &l, &h);
-    *lo = mform(l, m.q, m.bred.hi, m.bred.lo);
-    *hi = im != 0 ? mform(h, m.q, m.bred.hi, m.bred.lo) : *lo;
-}
-
 int refuse_const(const char *what) { return fail(LR_ERR_ARG, std::string(kWhoConst) + what); }
-
-// ---- the element side ------------------------------------------------------------------------------------------------------------
-// the words of two polys overlap
-bool overlap(const lr_poly *a, const lr_poly *b) {
-    const u64 *a1 = a->d + (long long)(a->batch - 1) * a->stride() + (long long)a->alloc_limbs * (long long)a->N;
-    const u64 *b1 = b->d + (long long)(b->batch - 1) * b->stride() + (long long)b->alloc_limbs * (long long)b->N;
-    return a->d < b1 && b->d < a1;
-}
 
 int refuse(int code, const char *what) { return fail(code, std::string(kWho) + what); }
 

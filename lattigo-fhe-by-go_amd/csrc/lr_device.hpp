@@ -323,6 +323,37 @@ inline LaunchVerdict launch_verdict(const LinCombLaunch &L, int limbs, int batch
                                                         limbs > lincomb_limbs_per_launch(L.count, L.has_add) || batch > 32767);
 }
 
+// out = a (+|-) b over CKKS ciphertexts of any degree (lr_ckks_combine.hip): the element loops of evaluator.Add / AddNoMod / Sub / SubNoMod
+// through evaluateInPlace (ckks/evaluator.go:227-342) with Sub's NegLvl tail (:186-192, :203-209), in one pass.  Per limb, coefficient j
+// and component u <= max(deg_a, deg_b), with s(j) = j < n/2 ? lo : hi:
+//   x = a_u (u <= deg_a), y = b_u (u <= deg_b; deg_b = -1: no b);  double_a: x = CRed(x + x);  mult_a: x = MRed(x, ma(j));
+//   mult_b: y = MRed(y, mb(j));  both: r = op(x, y);  only x: r = x;  only y: r = y, or q - y for the two subtractions;
+//   component 0 with has_add: r = CRed(r + add(j))
+// The constants travel in the kernel arguments, kCombineLimbWords per limb (ma_lo, ma_hi, mb_lo, mb_hi, add_lo, add_hi; zero where the
+// flag is off): kMaxLimbs limbs fill LinCombLaunch's budget of kLinCombWords exactly, so every level is one launch.
+constexpr int kCombineLimbWords = 6;
+constexpr int kCombineComps = 3;         // components of a ciphertext of degree 2
+static_assert(kCombineLimbWords * kMaxLimbs <= kLinCombWords, "every limb's words in one launch");
+struct CombineLaunch {
+    const u64 *a[kCombineComps], *b[kCombineComps];
+    u64 *out[kCombineComps];
+    long long a_stride[kCombineComps], b_stride[kCombineComps], out_stride[kCombineComps];     // between batch polys; 0: one poly read by every member
+    int n, op;                           // op: LR_ADD, LR_ADD_NOMOD, LR_SUB, LR_SUB_NOMOD
+    int deg_a, deg_b;                    // deg_a in 0..2, deg_b in -1..2
+    int double_a, mult_a, mult_b, has_add;
+    const LimbParams *lp;
+    u64 k[kCombineLimbWords * kMaxLimbs];
+};
+static_assert(sizeof(CombineLaunch) <= 4096, "CombineLaunch travels by value in the kernel arguments");
+LR_HD int combine_comps(int deg_a, int deg_b) { return (deg_a > deg_b ? deg_a : deg_b) + 1; }
+hipError_t launch_ckks_combine(const CombineLaunch &L, int limbs, int batch, hipStream_t stream);
+// (component on grid z next to the batch member: comps * batch <= 65535, which batch <= 32767 ensures up to degree 1)
+inline LaunchVerdict launch_verdict(const CombineLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.n < 4 || L.op < 0 || L.op > 3 || L.deg_a < 0 || L.deg_a >= kCombineComps || L.deg_b < -1 ||
+                                                        L.deg_b >= kCombineComps || limbs > kMaxLimbs || batch > 32767 ||
+                                                        (long long)combine_comps(L.deg_a, L.deg_b) * batch > 65535);
+}
+
 // key-switch inner product over all digits (lr_ewise.hip)
 struct KeyMacLaunch {
     const u64 *c2;                 // [beta][batch][limbs][N], NTT domain

@@ -45,6 +45,9 @@ LR_D ulonglong2 ld_shared(const ulonglong2 *p, long long stride, int e) { return
 LR_D ulonglong2 add2(ulonglong2 a, ulonglong2 b, u64 q) { return make_ulonglong2(cred(a.x + b.x, q), cred(a.y + b.y, q)); }
 // Context.Sub: CRed((a + q) - b); equal operands give CRed(q) = 0
 LR_D ulonglong2 sub2(ulonglong2 a, ulonglong2 b, u64 q) { return make_ulonglong2(cred((a.x + q) - b.x, q), cred((a.y + q) - b.y, q)); }
+// Context.AddNoMod / SubNoMod (ring/ring.go:48, :94): the same sums left unreduced
+LR_D ulonglong2 add2_nomod(ulonglong2 a, ulonglong2 b) { return make_ulonglong2(a.x + b.x, a.y + b.y); }
+LR_D ulonglong2 sub2_nomod(ulonglong2 a, ulonglong2 b, u64 q) { return make_ulonglong2((a.x + q) - b.x, (a.y + q) - b.y); }
 // Context.Neg: q - x without reduction, so a zero becomes q, as the reference stores it
 LR_D ulonglong2 neg2(ulonglong2 a, u64 q) { return make_ulonglong2(q - a.x, q - a.y); }
 LR_D ulonglong2 mul2(ulonglong2 a, ulonglong2 b, u64 q, u64 qinv) { return make_ulonglong2(mred(a.x, b.x, q, qinv), mred(a.y, b.y, q, qinv)); }

@@ -392,6 +392,31 @@ class Context:
                                     1 if accumulate else 0, out[0].h, out[1].h))
         return out
 
+    def CkksCombine(self, op, level, a, b, out, double_a=False, ma=None, mb=None, add=None):
+        """out = a (+|-) b over CKKS ciphertexts of any degree in one device call (lr_ckks_combine): the element loops of evaluator.Add /
+        AddNoMod / Sub / SubNoMod through evaluateInPlace (ckks/evaluator.go:227-342) with Sub's NegLvl tail, and the steps of the same
+        shape between the products of the Chebyshev drivers.  op: "ADD", "ADD_NOMOD", "SUB" or "SUB_NOMOD"; a, b, out: the components'
+        Polys (b None: no b); out[u] may be a[u] or b[u].  double_a: x = CRed(x + x) first; ma / mb: the multiplier of a / b, either one
+        array of level+1 words (ckks_combine_constants' mult) or (lo, hi); add: (add_lo, add_hi) for component 0, or None.  The same bits
+        as the sequence of HalfScalarOp "MRED" / "ADD" and AddLvl .. NegLvl, CopyLvl calls."""
+        L1 = level + 1
+
+        def half_words(w, what):
+            if w is None:
+                return None, None
+            lo, hi = w if isinstance(w, tuple) else (w, w)
+            lo, hi = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in (lo, hi))
+            if lo.size != L1 or hi.size != L1:
+                raise LatticeRingError(3, "CkksCombine: need %d words in each half of %s" % (L1, what))
+            return lo, hi
+        words = [half_words(ma, "ma"), half_words(mb, "mb"), half_words(add, "add")]
+        ptr = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        handles = lambda polys: (C.c_void_p * max(len(polys), 1))(*[p.h.value for p in polys])
+        check(lib().lr_ckks_combine(self.h, {"ADD": 0, "ADD_NOMOD": 1, "SUB": 2, "SUB_NOMOD": 3}[op], level, len(a) - 1, handles(a),
+                                    -1 if b is None else len(b) - 1, None if b is None else handles(b), 1 if double_a else 0,
+                                    *[ptr(x) for pair in words for x in pair], handles(out)))
+        return out
+
     def MultByMonomial(self, p1, monomialDeg, p2):  # ring/ring.go:663
         check(lib().lr_mult_by_monomial(self.h, p1.h, int(monomialDeg), p2.h))
 
@@ -496,6 +521,34 @@ def ckks_lincomb_constants(moduli, ntt_psi1, default_scale, res_level, res_scale
     rows = lambda a: a[:T * L1].reshape(T, L1).copy()
     return CkksLinCombConsts(level_after.value, scale_after.value, None if c0 is None else (add_lo[:L1].copy(), add_hi[:L1].copy()),
                              has_pre[:T].copy(), rows(pre), rows(lo), rows(hi))
+
+
+class CkksCombineConsts:
+    """what ckks_combine_constants yields: level_after, scale_after, degree_after, mult_side (0 none, 1 a, 2 b) and mult [level_after + 1]
+    (None when nothing is multiplied)"""
+
+    def __init__(self, level_after, scale_after, degree_after, mult_side, mult):
+        self.level_after, self.scale_after, self.degree_after, self.mult_side, self.mult = level_after, scale_after, degree_after, mult_side, mult
+
+
+CKKS_COMBINE_RECEIVER = {"new": 0, "a": 1, "b": 2, "both": 3}
+
+
+def ckks_combine_constants(moduli, op, a, b, out, receiver="new"):
+    """The scalar lines of evaluator.Add / AddNoMod / Sub / SubNoMod as the reference runs them (lr_ckks_combine_constants;
+    evaluateInPlace, ckks/evaluator.go:227-342, and its callers' degree rules).  Host only: needs no context and no device.
+    op: "ADD", "ADD_NOMOD", "SUB" or "SUB_NOMOD"; a, b, out: (degree, level, scale) of the operands and of the receiver before the call;
+    receiver: "new", "a", "b" or "both" (a is b is the receiver).  Returns a CkksCombineConsts; raises LatticeRingError where the
+    reference panics (LR_ERR_UNSUPPORTED) and outside the domain (LR_ERR_ARG)."""
+    moduli = [int(q) for q in moduli]
+    level_after, degree_after, mult_side, scale_after = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+    mult = np.zeros(max(len(moduli), 1), dtype=np.uint64)
+    check(lib().lr_ckks_combine_constants(_u64(moduli), len(moduli), {"ADD": 0, "ADD_NOMOD": 1, "SUB": 2, "SUB_NOMOD": 3}[op], int(a[0]), int(a[1]),
+                                          float(a[2]), int(b[0]), int(b[1]), float(b[2]), int(out[0]), int(out[1]), float(out[2]),
+                                          CKKS_COMBINE_RECEIVER[receiver], C.byref(level_after), C.byref(scale_after), C.byref(degree_after),
+                                          C.byref(mult_side), mult.ctypes.data_as(C.c_void_p)))
+    return CkksCombineConsts(level_after.value, scale_after.value, degree_after.value, mult_side.value,
+                             mult[:level_after.value + 1].copy() if mult_side.value else None)
 
 
 def NewContextWithParams(N, Moduli, device=0, options=None):
