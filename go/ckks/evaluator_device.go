@@ -17,8 +17,9 @@
 //	delete  Rescale              :933-968     -> below: upstream's scale loop; per level both components, CkksPlan.Rescale
 //	delete  RotateHoisted        :1252-1289   -> below: one decomposition, every rotation in one call, CkksPlan.RotateHoisted
 //	delete  switchKeyHoisted     :1291-1392   (its loops over Coeffs at :1356-1360 live inside the pipeline)
-//	delete  permuteNTT           :1452-1472   -> below, same signature: CkksPlan.PermuteNTT (RotateColumns, Conjugate and the
-//	                                             power-of-two composer rotateColumnsPow2 :1402-1427 call it and stay as they are)
+//	delete  permuteNTT           :1452-1472   -> below, same signature: CkksPlan.PermuteNTT (RotateColumns and Conjugate call it and stay
+//	                                             as they are)
+//	delete  rotateColumnsPow2    :1402-1424   -> below, same signature: the set bits of k as ONE call, CkksPlan.RotateChain
 //	delete  switchKeysInPlace    :1475-1558   -> below (the loops over Coeffs at :1519-1534 live inside the pipeline)
 //	delete  decomposeAndSplitNTT :1561-1591   (no caller left; its loops at :1580-1586 live inside the pipelines)
 //	patch   AddConst :373, MultByConstAndAdd :451, MultByConst :622, MultByi :746, DivByi :795 -- their element loops index Coeffs
@@ -329,8 +330,8 @@ func (eval *evaluator) switchKeysInPlace(level uint64, cx *ring.Poly, evakey *Sw
 }
 
 // permuteNTT (:1452): both components permuted, the second key-switched, the addition and the copy folded into the pipeline's last
-// pass.  RotateColumns, Conjugate and rotateColumnsPow2 call it with the index table of the rotation; the device gathers from the
-// Galois element, which the table determines.
+// pass.  RotateColumns and Conjugate call it with the index table of the rotation; the device gathers from the Galois element, which
+// the table determines.
 func (eval *evaluator) permuteNTT(ct0 *Ciphertext, index []uint64, evakey *SwitchingKey, ctOut *Ciphertext) {
 	eval.resident(ct0.value[0], ct0.value[1], ctOut.value[0], ctOut.value[1])
 	level := utils.MinUint64(ct0.Level(), ctOut.Level())
@@ -341,6 +342,24 @@ func (eval *evaluator) permuteNTT(ct0 *Ciphertext, index []uint64, evakey *Switc
 	}
 	eval.dev().plan.PermuteNTT(level, [2]*ring.Poly{ct0.value[0], ct0.value[1]}, eval.galoisElement(index), eval.keyImage(evakey),
 		[2]*ring.Poly{ctOut.value[0], ctOut.value[1]})
+}
+
+// rotateColumnsPow2 (:1402): the power-of-two composer behind every RotateColumns when only GenRotationKeysPow2's keys exist.  Upstream
+// copies ct0 into ctOut and calls permuteNTT once per set bit of k; here the Galois elements and key images of those bits go to the
+// device as one chain, which reads ct0 and writes ctOut (in place or not, no copy).  Chains go to the evaluator's own plan: the batcher
+// merges single rotations of concurrent callers, not chains.
+func (eval *evaluator) rotateColumnsPow2(ct0 *Ciphertext, k uint64, permuteNTTIndex map[uint64][]uint64, evakeyRotCol map[uint64]*SwitchingKey, ctOut *Ciphertext) {
+	level := utils.MinUint64(ct0.Level(), ctOut.Level())
+	eval.resident(ct0.value[0], ct0.value[1], ctOut.value[0], ctOut.value[1])
+	var gens []uint64
+	var keys []*ring.Poly
+	for evakeyIndex := uint64(1); k > 0; evakeyIndex, k = evakeyIndex<<1, k>>1 {
+		if k&1 == 1 {
+			gens = append(gens, eval.galoisElement(permuteNTTIndex[evakeyIndex]))
+			keys = append(keys, eval.keyImage(evakeyRotCol[evakeyIndex]))
+		}
+	}
+	eval.dev().plan.RotateChain(level, [2]*ring.Poly{ct0.value[0], ct0.value[1]}, gens, keys, false, [2]*ring.Poly{ctOut.value[0], ctOut.value[1]})
 }
 
 // RotateHoisted (:1252): one decomposition, every rotation's gather + inner product + ModDown in one device call.

@@ -160,6 +160,29 @@ func (p *CkksPlan) RotateHoisted(level uint64, ct0 [2]*Poly, galEls []uint64, ro
 	}
 }
 
+// RotateChain = a chain of evaluator.permuteNTT steps (ckks/evaluator.go:1452-1471) as ONE call: step i rotates the running ciphertext by
+// the Galois element galEls[i] under rotkeys[i] and replaces it (accumulate false: the loop of rotateColumnsPow2, :1414-1423) or is
+// added to it (accumulate true: the slot-sum loop RotateColumns; Add at equal scales); ctOut may be ct0; no step copies.
+func (p *CkksPlan) RotateChain(level uint64, ct0 [2]*Poly, galEls []uint64, rotkeys []*Poly, accumulate bool, ctOut [2]*Poly) {
+	p.contextQ.use(ct0[0], ct0[1])
+	p.contextQ.want(ctOut[0], ctOut[1])
+	n := len(galEls)
+	keys := polyTable(rotkeys)
+	defer C.free(unsafe.Pointer(keys))
+	var gens *C.uint64_t
+	if n > 0 {
+		gens = (*C.uint64_t)(unsafe.Pointer(&galEls[0]))
+	}
+	acc := C.int(0)
+	if accumulate {
+		acc = 1
+	}
+	call(func() C.int {
+		return C.lr_ckks_rotate_chain(p.h, C.int(level), ct0[0].d, ct0[1].d, C.int(n), gens, keys, acc, ctOut[0].d, ctOut[1].d)
+	})
+	done(ctOut[0], ctOut[1])
+}
+
 // polyArray views n handle slots of C memory as a Go slice (the pre-go-1.17 spelling of unsafe.Slice)
 func polyArray(raw unsafe.Pointer, n int) []*C.lr_poly {
 	return (*[1 << 28]*C.lr_poly)(raw)[:n:n]

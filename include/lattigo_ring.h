@@ -639,6 +639,28 @@ int lr_ckks_rescale(lr_ckks_plan *plan, lr_poly *c0, lr_poly *c1);
  * (a SwitchingKey image as for lr_ckks_switch_keys).  out may alias the input. */
 int lr_ckks_rotate(lr_ckks_plan *plan, int level, const lr_poly *c0, const lr_poly *c1, uint64_t gen,
                    const lr_poly *rotkey, lr_poly *out_c0, lr_poly *out_c1);
+/* A chain of evaluator.permuteNTT steps as ONE call (rotateColumnsPow2, ckks/evaluator.go:1402-1424 -- the path of every RotateColumns
+ * when only the power-of-two keys of GenRotationKeysPow2 exist -- and the slot-sum loop RotateColumns(ct, 2^i, tmp); Add(ct, tmp, ct)).
+ * The state (a0, a1) starts as (c0, c1) over Q[0..level], NTT domain; step i = 0 .. n_steps - 1, with Galois element gens[i] and key
+ * image keys[i], is permuteNTT (:1452-1471): (e0, e1) = PermuteNTT of both components by gens[i] (:1458-1459);
+ * (p0, p1) = switchKeysInPlace(level, e1, keys[i]) (:1464); (r0, r1) = (CRed(e0 + p0), p1) (:1466-1467); then
+ *   accumulate == 0:  (a0, a1) <- (r0, r1)                               rotateColumnsPow2 :1414-1423 (gens: the Galois elements of the
+ *                                                                        rotations by 2^i at the set bits of k, keys: their keys)
+ *   accumulate != 0:  (a0, a1) <- (CRed(r0 + a0), CRed(r1 + a1))         RotateColumns into a temporary, then Add at equal scales
+ * and (out_c0, out_c1) <- the last state; bit for bit the composed sequence for inputs in [0, q).  Any batch up to the plan's
+ * max_batch; (out_c0, out_c1) may be (c0, c1) or (c1, c0), an input that is not an output is left unchanged; one key handle may serve
+ * several steps; n_steps == 0 copies (gens and keys may then be NULL).  The polys need not share a stride.
+ * Checks, in this order: LR_ERR_ARG for a null argument or a null entry of keys, n_steps < 0, an even Galois element, out_c0 and out_c1
+ * the same poly; then LR_ERR_SHAPE for a level out of range, a batch beyond max_batch, a poly with fewer limbs than level + 1, of
+ * another degree or another batch, a key image with fewer than 2 * beta polys or |Q| + |P| limbs.  Nothing is written by a refused call.
+ * An accumulating step is one pass in front of the key switch (its input and the first component's addend, the running sum already in
+ * it) and the key switch, whose last pass adds the running second component: no Add is launched.  Plans or contexts with
+ * lr_options::no_epilogue, and rings whose forward transform has no epilogue, run the step as lr_ckks_rotate does and the two Adds
+ * after it.  A replacing step has no Add to lose and is lr_ckks_rotate's launches on every plan (measured), written
+ * straight into the outputs.  Same bits on every route.  An accumulating chain keeps four more polys over Q[0..level] per batch member
+ * in the plan. */
+int lr_ckks_rotate_chain(lr_ckks_plan *plan, int level, const lr_poly *c0, const lr_poly *c1, int n_steps, const uint64_t *gens,
+                         const lr_poly *const *keys, int accumulate, lr_poly *out_c0, lr_poly *out_c1);
 /* RotateHoisted + switchKeyHoisted (ckks/evaluator.go:1252-1391): n_rot rotations of one ciphertext share the
  * digit decomposition of its second component.  gens[r], rotkeys[r] -> (outs_c0[r], outs_c1[r]); not in place. */
 int lr_ckks_rotate_hoisted(lr_ckks_plan *plan, int level, const lr_poly *c0, const lr_poly *c1, int n_rot,

@@ -357,6 +357,31 @@ class BfvRotator {
     lr_ckks_plan *h_ = nullptr;
 };
 
+// The CKKS rotation chains of the key-switch plan over (contextQ, contextP).  Ciphertexts are pairs of Polys over Q[0..level] in the NTT
+// domain, keys the images of SwitchingKey.evakey; an output pair may be the input pair.
+class CkksRotator {
+  public:
+    CkksRotator(const Context *contextQ, const Context *contextP, int max_batch = 1, const lr_options *options = nullptr) {
+        check(lr_ckks_plan_create_ex(contextQ->handle(), contextP->handle(), max_batch, options, &h_));
+    }
+    ~CkksRotator() { lr_ckks_plan_destroy(h_); }
+    CkksRotator(const CkksRotator &) = delete;
+    CkksRotator &operator=(const CkksRotator &) = delete;
+    // a chain of permuteNTT steps (ckks/evaluator.go:1452) as one call: replaced by each rotation (rotateColumnsPow2 :1402) or added to
+    // it (the slot-sum loop RotateColumns; Add)
+    void RotateChain(int level, const Poly *c0, const Poly *c1, const std::vector<uint64_t> &galoisElements, const std::vector<const Poly *> &switchKeys,
+                     bool accumulate, Poly *out0, Poly *out1) {
+        if (galoisElements.size() != switchKeys.size()) throw Error(LR_ERR_ARG, "RotateChain: one key per Galois element");
+        std::vector<const lr_poly *> keys;
+        for (const Poly *p : switchKeys) keys.push_back(p ? p->handle() : nullptr);
+        check(lr_ckks_rotate_chain(h_, level, c0->handle(), c1->handle(), (int)galoisElements.size(), galoisElements.data(), keys.data(),
+                                   accumulate ? 1 : 0, out0->handle(), out1->handle()));
+    }
+
+  private:
+    lr_ckks_plan *h_ = nullptr;
+};
+
 // bfv.Encoder (bfv/encoder.go:10-182) for batches of plaintexts; slots are [batch][n] host arrays, plaintexts Polys over contextQ
 class BfvEncoder {
   public:

@@ -139,6 +139,7 @@ SYMBOLS = {
     "lr_context_timeline": [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)],
     "lr_selftest_division": [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)],
     "lr_ckks_rotate": [vp, i32, vp, vp, u64, vp, vp, vp],
+    "lr_ckks_rotate_chain": [vp, i32, vp, vp, i32, u64p, C.POINTER(vp), i32, vp, vp],
     "lr_ckks_rotate_hoisted": [vp, i32, vp, vp, i32, u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
     "lr_bfv_plan_create": [vp, vp, u64, i32, C.POINTER(vp)],
     "lr_bfv_plan_create_ex": [vp, vp, u64, i32, vp, C.POINTER(vp)],

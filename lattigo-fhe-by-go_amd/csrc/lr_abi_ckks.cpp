@@ -426,7 +426,8 @@ int ks_ntt_tail(lr_ckks_plan *pl, int level, int batch, const KeySwitchAcc &acc,
     };
     const Component comp[2] = {
         {acc.p[0], fin ? fin->out0 : acc.p[0], fin ? fin->plus0 : nullptr, acc.stride[0], fin ? fin->out_stride : acc.stride[0], fin ? fin->plus_stride : 0},
-        {acc.p[1], fin ? fin->out1 : acc.p[1], fin ? fin->plus1 : nullptr, acc.stride[1], fin ? fin->out_stride : acc.stride[1], fin ? fin->plus_stride : 0}};
+        {acc.p[1], fin ? fin->out1 : acc.p[1], fin ? fin->plus1 : nullptr, acc.stride[1],
+         fin ? (fin->out1_stride ? fin->out1_stride : fin->out_stride) : acc.stride[1], fin ? (fin->plus1_stride ? fin->plus1_stride : fin->plus_stride) : 0}};
     const Rows pr{pl->poolPP.d, z.sP, 0, 1};
     LR_TRY(bx->poolQ.ensure(cQ, (size_t)2 * batch * sQ));
     u64 *ext_out = bx->poolQ.d;

@@ -457,6 +457,27 @@ inline LaunchVerdict launch_verdict(const BfvRelinFoldLaunch &L, int limbs, int 
                                                         L.out[0] == L.out[1] || L.out[0] == L.base[1] || L.out[1] == L.base[0]);
 }
 hipError_t launch_bfv_relin_fold(const BfvRelinFoldLaunch &L, int limbs, int batch, hipStream_t stream);
+
+// One step of an accumulating CKKS rotation chain in front of its key switch (lr_ckks_rotate_chain; the two PermuteNTT calls of
+// permuteNTT, ckks/evaluator.go:1458-1459, and the first component's half of the Add that follows the rotation in the slot-sum loop):
+// see ckks_chain_step_kernel (lr_ckks_chain.hip).  NTT domain, limbs 0 .. level.
+struct CkksChainStepLaunch {
+    const u64 *a0, *a1;      // the chain's state before the step
+    long long a0_stride, a1_stride;
+    u64 *plus0;              // CRed(PermuteNTT(a0, g) + a0): the addend of the key switch's first component
+    u64 *cx;                 // PermuteNTT(a1, g): the key switch's input
+    long long plus_stride, cx_stride;
+    int n, logn;
+    u32 gen;                 // g, odd, reduced modulo 2N
+    const LimbParams *lp;
+};
+// (a gather: no output is an input; batch and component share grid z)
+inline LaunchVerdict launch_verdict(const CkksChainStepLaunch &L, int limbs, int batch) {
+    return launch_verdict(limbs <= 0 || batch <= 0, L.logn < 1 || L.logn > 30 || (1 << L.logn) != L.n || limbs > kMaxLimbs || batch > 32767 || !(L.gen & 1u) ||
+                                                        L.gen >= 2u * (u32)L.n || L.plus0 == L.cx || L.plus0 == L.a0 || L.plus0 == L.a1 || L.cx == L.a0 ||
+                                                        L.cx == L.a1);
+}
+hipError_t launch_ckks_chain_step(const CkksChainStepLaunch &L, int limbs, int batch, hipStream_t stream);
 // Context.MultByMonomial (ring/ring.go:663): out = in * X^shift in Z_q[X]/(X^N+1), shift already reduced modulo 2N;
 // like the reference, negated coefficients are q - x without reduction (0 becomes q).  Not in place.
 hipError_t launch_monomial(const GaloisLaunch &L, int limbs, int batch, hipStream_t stream);

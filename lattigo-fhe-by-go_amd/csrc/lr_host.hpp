@@ -378,7 +378,8 @@ struct lr_ckks_plan {
     Pool c2QiQ, c2QiP, poolPP, c2, c0, c1, c2x, q1, q2, permQ, permP;
     Pool encQ, encP;       // pk-encryption temporaries over Q||P (lr_ckks_encrypt_pk)
     Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q; lr_bfv_relinearize_deg: two of them per group of a pass; lr_abi_bfv_eval.cpp)
-    Pool chainP;           // bfv rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_abi_bfv_eval.cpp)
+    Pool chainP;           // rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_abi_bfv_eval.cpp; with bfvP the two
+                           // pairs of an accumulating lr_ckks_rotate_chain, lr_ckks_chain.cpp)
     Pool zerosQ;           // one poly of zeros over Q: the `plus` operand of the NTT epilogue where a caller has none
     Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_plan_decomposition)
     // small batches: independent launches of one pipeline side by side (PlanFork); stream and events are created at the first fork
@@ -566,11 +567,14 @@ struct KeySwitchAcc {
 };
 // `fin` (optional): the ModDown results go to fin->out0/out1 with fin->plus0/plus1 added (CRed), i.e. the two
 // Context.Add calls that follow the key switch in MulRelin (:1103-1104) ride on the last ModDown pass
+// A second component that lies at another stride than the first (lr_ckks_rotate_chain: the caller's polys on one side, a pool on the
+// other) says so in out1_stride / plus1_stride; 0 = the first component's, which is what every other caller leaves it at.
 struct KeySwitchEpilogue {
     u64 *out0, *out1;
     long long out_stride;
     const u64 *plus0, *plus1;
     long long plus_stride;
+    long long out1_stride = 0, plus1_stride = 0;
 };
 
 // Fork: launches of the calling thread that go to a plan's auxiliary stream instead of the context's (PlanFork, lr_abi_ckks.cpp): two independent

@@ -824,6 +824,29 @@ class CkksPlan:
             idx <<= 1
             k >>= 1
 
+    def RotateChain(self, level, ct0, gens, keys, accumulate, ctOut):
+        """a chain of evaluator.permuteNTT steps as one call (lr_ckks_rotate_chain): step i rotates the running ciphertext by the Galois
+        element gens[i] under keys[i] and replaces it (accumulate False: rotateColumnsPow2, ckks/evaluator.go:1402-1424) or is added to
+        it (True: the slot-sum loop RotateColumns; Add); ctOut may be ct0; no step copies"""
+        n = len(gens)
+        if len(keys) != n:
+            raise ValueError("one key per Galois element")
+        g = (C.c_uint64 * max(n, 1))(*[int(x) for x in gens])
+        ks = (C.c_void_p * max(n, 1))(*[k.h.value if k is not None else None for k in keys])
+        check(lib().lr_ckks_rotate_chain(self.h, level, ct0[0].h, ct0[1].h, n, g, ks, 1 if accumulate else 0, ctOut[0].h, ctOut[1].h))
+
+    def RotateColumnsPow2Chain(self, level, ct0, k, pow2_keys, ctOut):
+        """RotateColumnsPow2 as ONE call: the set bits of k become the steps of a replace chain"""
+        gens, keys, idx = [], [], 1
+        while k > 0:
+            if k & 1:
+                gen, key = pow2_keys[idx]
+                gens.append(gen)
+                keys.append(key)
+            idx <<= 1
+            k >>= 1
+        self.RotateChain(level, ct0, gens, keys, False, ctOut)
+
     def RotateHoisted(self, level, ct0, gens, rotkeys, ctOuts):
         """evaluator.RotateHoisted (ckks/evaluator.go:1252): ctOuts[r] = rotation of ct0 by the Galois element gens[r]."""
         n = len(gens)
