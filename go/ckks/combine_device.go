@@ -26,11 +26,13 @@
 //	delete  computePowerBasisCheby :60-101 -> below: the recursion, MulRelinNew and Rescale are upstream's; Add(C[n], C[n], C[n]) and
 //	                                      then Sub(C[n], C[c], C[n]) or AddConst(C[n], -1, C[n]) (:92-99) become ONE Context.CkksCombine
 //	                                      call with doubleA: 3 row passes per component where the two or three calls move up to 7
-//	patch   EvaluateChebyFast :16-17, EvaluateChebyEco :42-43: the two lines `eval.MultByConst(C[1], 2/(cheby.b-cheby.a), C[1])` and
-//	                                      `eval.AddConst(C[1], (-cheby.a-cheby.b)/(cheby.b-cheby.a), C[1])` are replaced by the one
-//	                                      line `eval.affineInPlace(C[1], 2/(cheby.b-cheby.a), (-cheby.a-cheby.b)/(cheby.b-cheby.a))`
-//	                                      (below): both constants' words from ONE ring.CkksLinCombConstants call, the element loops
-//	                                      as ONE Context.CkksCombine call
+//	        EvaluateChebyFast :10-32, EvaluateChebyEco :36-58 are deleted whole and have their replacement bodies in
+//	                                      power_basis_device.go (its patch list); there the two lines :16-17 / :42-43,
+//	                                      `eval.MultByConst(C[1], 2/(cheby.b-cheby.a), C[1])` and
+//	                                      `eval.AddConst(C[1], (-cheby.a-cheby.b)/(cheby.b-cheby.a), C[1])`, are the one line
+//	                                      `eval.affineInPlace(C[1], 2/(cheby.b-cheby.a), (-cheby.a-cheby.b)/(cheby.b-cheby.a))`
+//	                                      (defined below): both constants' words from ONE ring.CkksLinCombConstants call, the
+//	                                      element loops as ONE Context.CkksCombine call
 //	keep    recurseCheby :104 and, in polynomial_evaluation.go, recurse: they call MulRelin, Add, Rescale and
 //	                                      evaluatePolyFromPowerBasis, each of which is a device call
 package ckks

@@ -44,7 +44,8 @@
 //	        upstream's outputs, the same on every run.  The 1e-15 filter on the coefficients is upstream's.  AddConst and
 //	        MultByConstAndAdd keep their patch above for their other callers (recurse and recurseCheby call Add / MulRelin / Rescale
 //	        around this leaf and stay as they are; Add / AddNoMod / Sub / SubNoMod with evaluateInPlace, computePowerBasisCheby and the
-//	        head of EvaluateChebyFast / Eco have their replacement bodies and their patch list in combine_device.go).
+//	        helper of EvaluateChebyFast / Eco's head have their replacement bodies and their patch list in combine_device.go; the four
+//	        EvaluatePoly* / EvaluateCheby* entry points and PowerOf2 have theirs in power_basis_device.go).
 //
 //	keep    DropLevel :901 (it re-slices Coeffs: metadata; the device image is sized by cap(Coeffs) and keeps its stride), RescaleMany
 //	        :971 (Context.DivRoundByLastModulusManyNTT is a device call), Neg / MulByPow2 / Reduce / ScaleUp (Context methods)

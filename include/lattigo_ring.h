@@ -661,6 +661,85 @@ int lr_ckks_rotate(lr_ckks_plan *plan, int level, const lr_poly *c0, const lr_po
  * in the plan. */
 int lr_ckks_rotate_chain(lr_ckks_plan *plan, int level, const lr_poly *c0, const lr_poly *c1, int n_steps, const uint64_t *gens,
                          const lr_poly *const *keys, int accumulate, lr_poly *out_c0, lr_poly *out_c1);
+/* ------------------------------------------------------------------ CKKS power basis (monomial and Chebyshev) */
+/* The products of EvaluatePoly* / EvaluateCheby*: computePowerBasis (ckks/polynomial_evaluation.go:76-93), C[n] = C[a] C[b], and
+ * computePowerBasisCheby (ckks/chebyshev_evaluation.go:60-101), C[n] = 2 C[a] C[b] - C[c], with a = ceil(n / 2), b = n >> 1, c = a - b
+ * and C[0] the constant 1; each product is MulRelinNew, Rescale(., ckksContext.scale, .) and, Chebyshev, Add(C[n], C[n], C[n]) followed
+ * by AddConst(C[n], -1, C[n]) (c == 0) or Sub(C[n], C[c], C[n]).  PowerOf2 (ckks/algorithms.go:9-31) is computePowerBasis(2^k).  Split as
+ * the calls above: the scalar lines and the element loops.  The recurse / recurseCheby drivers stay with the caller.
+ *
+ * lr_ckks_power_basis_schedule: the scalar lines, literally.  HOST ONLY: no context, no device, thread-safe.
+ *   in : moduli[n_moduli]; default_scale = ckksContext.scale, Rescale's threshold; chebyshev != 0: computePowerBasisCheby; level and scale
+ *        of C[1]; targets[n_targets], each in 1 .. 65535: the n of the caller's computePowerBasis(n) calls, in its order; capacity = the
+ *        products that `products` holds and the rows that mult and add hold, n_moduli words each.
+ *   out: *n_products; products[k], k < *n_products, in the order the reference creates them: for each target the recursion of :78-92 /
+ *        :70-99 -- first a, then b, each only when not yet present (c is 0 or 1 and C[1] is always present, so c never recurses); a
+ *        target that is 1 or already present adds nothing.  Per product (lr_ckks_basis_product): scale = s_a s_b (:1038) at
+ *        mul_level = min of the operands' levels (:1005); Rescale's loop `scale >= threshold * float64(q_level) / 2 && level != 0`
+ *        (:945-961; at level 0 nothing, the error return is ignored by the caller) divides the scale by float64(q_level) n_rescales
+ *        times; tail 1 is lr_ckks_combine_constants(LR_SUB, a = C[n] after Add(C, C, C), b = C[1], receiver = a): mult_side, the mult
+ *        row, the larger scale, the level; tail 2 leaves level and scale and its add row is scaleUpExact(-1, scale, q_i) for
+ *        i <= level_after, one word per limb for both halves of the row (the constant is real).  Rows and words that are not used are 0.
+ *   Domain, as for lr_ckks_lincomb_constants and lr_ckks_combine_constants: finite positive scales (every product's included), a scale
+ *   ratio below 2^63, moduli odd and in [3, 2^61).  A refused call writes NOTHING, with one exception: "more products than capacity"
+ *   sets *n_products to the number needed, so a caller sizes its buffers with capacity == 0 (products, mult and add may then be NULL)
+ *   and calls again.  Every refusal is LR_ERR_ARG; checked in this order, messages "CKKS power basis schedule: " +
+ *     "null argument" | "a count or a level is out of range" | "a target is 0 or above 65535" |
+ *     "a modulus is even, below 3 or not below 2^61" | "a scale is not finite and positive" (default_scale, c1_scale) |
+ *     "more products than capacity" | then per product, in order: "a scale is not finite and positive" (s_a s_b) |
+ *     "a scale ratio is not below 2^63" (tail 1).
+ *   Example of the last: PN12QP109, Chebyshev, targets beyond 2 -- the products stall at level 0, their scales square, and the ratio
+ *   to C[1] leaves the domain; the monomial form of the same call is accepted with n_rescales == 0. */
+typedef struct lr_ckks_basis_product {
+    uint32_t n, a, b, c;     /* C[n] = C[a] C[b]; a = ceil(n/2), b = n >> 1; Chebyshev: c = a - b (0: the constant 1, else 1); monomial: 0 */
+    int32_t  mul_level;      /* min(level of C[a], level of C[b]): MulRelinNew :1005, MulRelin :1020 */
+    int32_t  n_rescales;     /* iterations of Rescale's loop :945-961; 0 at level 0 or below the threshold */
+    int32_t  level_after;
+    int32_t  layer;          /* 1 + the largest layer among C[a], C[b]; C[1] is layer 0 */
+    int32_t  tail;           /* 0 none (monomial) | 1: 2 x - C[c] (Add :92, Sub :98) | 2: 2 x + const (Add :92, AddConst(-1) :96) */
+    int32_t  mult_side;      /* tail 1: lr_ckks_combine_constants' mult_side for Sub(C[n], C[c], C[n]), receiver = a; else 0 */
+    double   scale_after;
+} lr_ckks_basis_product;
+int lr_ckks_power_basis_schedule(const uint64_t *moduli, int n_moduli, double default_scale, int chebyshev, int c1_level, double c1_scale,
+                                 int n_targets, const uint32_t *targets, int capacity, int *n_products, lr_ckks_basis_product *products,
+                                 uint64_t *mult, uint64_t *add);      /* mult, add: [capacity][n_moduli] */
+/* lr_ckks_power_basis: the element loops of a schedule as ONE device call.  Every C is a batch of c1_c0->batch ciphertexts of degree 1 in
+ * the NTT domain; C[1] = (c1_c0, c1_c1) at c1_level; (outs_c0[k], outs_c1[k]) receives C[products[k].n] on limbs 0 .. level_after and
+ * needs level_after + 1 limbs -- its logical limb count is left alone, the limbs above level_after are not written.  mult and add are
+ * the schedule's rows, row_words words apart.  evk: the relinearisation key's image as for lr_ckks_mulrelin.  Bit for bit the composed
+ * sequence per product -- lr_ckks_mulrelin at mul_level, n_rescales times lr_ckks_rescale, then the lr_ckks_combine call of the tail
+ * (double_a with LR_SUB against C[1] and the mult row on mult_side, or with the add row) -- for inputs in [0, q).  The inputs are left
+ * unchanged.  Any batch up to the plan's max_batch.
+ * Merged route (default, where the forward transform has the epilogue): the products are grouped by (layer, mul_level, n_rescales) and
+ * a group is cut into chunks of max(1, max_batch / batch) products; per chunk ONE MulRelin over products * batch members, whose
+ * operands are read in place through a pointer table, into a staging pair of the plan; n_rescales one-level divisions of that pair (the
+ * reference's loop, not the Many form); ONE tail pass that writes every C[n] to its polys.  The pointer tables and the
+ * products' words travel in a small device table of the plan, filled by an asynchronous copy from eight pinned slots that an event
+ * guards: the call is asynchronous on the contexts' stream (the device images are reused in stream order from call to call, which
+ * lr_context_set_stream preserves when it replaces a stream).  It waits on the host in three
+ * bounded cases: a slot handed out again while its copy is pending waits for that copy and so for the kernels queued before it (more
+ * than eight chunks in flight); a slot, the staging pair or a pool of the plan that grows synchronises the stream, as the plan's other
+ * calls do.  Not capturable.  A chunk of one product has nothing to merge and runs as the product stands.  Plans or contexts with lr_options::no_epilogue,
+ * rings whose forward transform has no epilogue, batches above 32767 and the one shape measured level with the sequence (the widest
+ * chunk a pair, 8 ciphertexts or more, N <= 2^15) run product by product from the existing calls: MulRelin, the
+ * divisions and the lr_ckks_combine call of the tail -- a product that is divided goes through the plan's staging pair and its tail
+ * writes the output, because the output holds level_after + 1 limbs only and nothing above them is written.  Same bits on every route.
+ * The plan keeps the staging pair: two polys over Q[0..mul_level] per member of the largest chunk.
+ * Checks, in this order; a refused call writes nothing.  Messages "CKKS power basis: " + (the shared checks of the plan's calls without it)
+ *   LR_ERR_ARG          "null argument" (plan, C[1], evk) | "negative product count" | "null argument" (products, mult, add, outs) |
+ *                       "an output is null" | "row_words is below c1_level + 1" | "the schedule is not self-consistent": per product,
+ *                       an operand that is neither 1 nor an earlier product of a lower layer, n below 2 or listed before, mul_level
+ *                       not the minimum of its operands' level_after (C[1]: c1_level), a tail or mult_side outside 0..2, n_rescales
+ *                       outside 0..mul_level, level_after != mul_level - n_rescales, tail 1 with c != 1 |
+ *                       "two outputs share memory" | "an output shares memory with C[1]"
+ *   LR_ERR_SHAPE        "batch exceeds the plan's max_batch" | "level out of range" | "ring degree mismatch" |
+ *                       "poly has fewer limbs than level+1" | "batch mismatch" (C[1] at c1_level, then each output at its level_after) |
+ *                       "the two polys of an output must share their stride" | "evaluation key: need batch >= 2*beta and |Q|+|P| limbs"
+ *   LR_ERR_UNSUPPORTED  "ring degree below 4"
+ *   LR_ERR_ARG          the two contexts on different streams */
+int lr_ckks_power_basis(lr_ckks_plan *plan, int n_products, const lr_ckks_basis_product *products, const uint64_t *mult,
+                        const uint64_t *add, int row_words, int c1_level, const lr_poly *c1_c0, const lr_poly *c1_c1, const lr_poly *evk,
+                        lr_poly *const *outs_c0, lr_poly *const *outs_c1);
 /* RotateHoisted + switchKeyHoisted (ckks/evaluator.go:1252-1391): n_rot rotations of one ciphertext share the
  * digit decomposition of its second component.  gens[r], rotkeys[r] -> (outs_c0[r], outs_c1[r]); not in place. */
 int lr_ckks_rotate_hoisted(lr_ckks_plan *plan, int level, const lr_poly *c0, const lr_poly *c1, int n_rot,

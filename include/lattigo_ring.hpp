@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lattigo_ring.h"
@@ -99,6 +100,33 @@ inline CkksCombineConsts CkksCombineConstants(const std::vector<uint64_t> &modul
     check(lr_ckks_combine_constants(moduli.data(), (int)moduli.size(), op, a.degree, a.level, a.scale, b.degree, b.level, b.scale, out.degree,
                                     out.level, out.scale, receiver, &r.level_after, &r.scale_after, &r.degree_after, &r.mult_side, r.mult.data()));
     r.mult.resize(r.mult_side ? (size_t)r.level_after + 1 : 0);
+    return r;
+}
+
+// What the scalar lines of the power basis yield (lr_ckks_power_basis_schedule: computePowerBasis, ckks/polynomial_evaluation.go:76-93,
+// and computePowerBasisCheby, ckks/chebyshev_evaluation.go:60-101): the products in the reference's order of creation and their rows of
+// moduli.size() words each (the multiplier of tail 1, the addend of tail 2; zero where unused).
+struct CkksBasisSchedule {
+    std::vector<lr_ckks_basis_product> products;
+    std::vector<uint64_t> mult, add;
+    int row_words = 0;
+};
+// host only: no context, no device.  targets: the n of the caller's computePowerBasis(n) calls, in its order
+inline CkksBasisSchedule CkksPowerBasisSchedule(const std::vector<uint64_t> &moduli, double default_scale, bool chebyshev, int c1_level, double c1_scale,
+                                                const std::vector<uint32_t> &targets) {
+    CkksBasisSchedule r;
+    r.row_words = (int)moduli.size();
+    int n = -1;
+    // the capacity protocol: the count first, then buffers of that size
+    const int rc = lr_ckks_power_basis_schedule(moduli.data(), (int)moduli.size(), default_scale, chebyshev ? 1 : 0, c1_level, c1_scale, (int)targets.size(),
+                                                targets.data(), 0, &n, nullptr, nullptr, nullptr);
+    if (rc != LR_OK && n < 0) check(rc);
+    r.products.resize((size_t)n + 1);
+    r.mult.assign((size_t)n * moduli.size() + 1, 0);
+    r.add.assign((size_t)n * moduli.size() + 1, 0);
+    check(lr_ckks_power_basis_schedule(moduli.data(), (int)moduli.size(), default_scale, chebyshev ? 1 : 0, c1_level, c1_scale, (int)targets.size(),
+                                       targets.data(), n, &n, r.products.data(), r.mult.data(), r.add.data()));
+    r.products.resize((size_t)n);
     return r;
 }
 
@@ -376,6 +404,18 @@ class CkksRotator {
         for (const Poly *p : switchKeys) keys.push_back(p ? p->handle() : nullptr);
         check(lr_ckks_rotate_chain(h_, level, c0->handle(), c1->handle(), (int)galoisElements.size(), galoisElements.data(), keys.data(),
                                    accumulate ? 1 : 0, out0->handle(), out1->handle()));
+    }
+    // the products of a power basis as one call: outs[k] = (out0, out1) receives C[schedule.products[k].n] on limbs 0 .. level_after
+    void PowerBasis(int c1_level, const Poly *c1_0, const Poly *c1_1, const CkksBasisSchedule &schedule, const Poly *evakey,
+                    const std::vector<std::pair<Poly *, Poly *>> &outs) {
+        if (outs.size() != schedule.products.size()) throw Error(LR_ERR_ARG, "PowerBasis: one output per product");
+        std::vector<lr_poly *> o0, o1;
+        for (const auto &o : outs) {
+            o0.push_back(o.first ? o.first->handle() : nullptr);
+            o1.push_back(o.second ? o.second->handle() : nullptr);
+        }
+        check(lr_ckks_power_basis(h_, (int)outs.size(), schedule.products.data(), schedule.mult.data(), schedule.add.data(), schedule.row_words, c1_level,
+                                  c1_0->handle(), c1_1->handle(), evakey->handle(), o0.data(), o1.data()));
     }
 
   private:

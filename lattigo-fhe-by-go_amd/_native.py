@@ -38,6 +38,12 @@ class Options(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BasisProduct(C.Structure):
+    """lr_ckks_basis_product (include/lattigo_ring.h), field for field"""
+    _fields_ = [(n, C.c_uint32) for n in ("n", "a", "b", "c")] + [(n, C.c_int32) for n in (
+        "mul_level", "n_rescales", "level_after", "layer", "tail", "mult_side")] + [("scale_after", C.c_double)]
+
+
 # every symbol declared in include/lattigo_ring.h: name -> argtypes
 SYMBOLS = {
     "lr_last_error_string": [],
@@ -140,6 +146,8 @@ SYMBOLS = {
     "lr_selftest_division": [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)],
     "lr_ckks_rotate": [vp, i32, vp, vp, u64, vp, vp, vp],
     "lr_ckks_rotate_chain": [vp, i32, vp, vp, i32, u64p, C.POINTER(vp), i32, vp, vp],
+    "lr_ckks_power_basis_schedule": [vp, i32, C.c_double, i32, i32, C.c_double, i32, vp, i32, C.POINTER(i32), vp, vp, vp],
+    "lr_ckks_power_basis": [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)],
     "lr_ckks_rotate_hoisted": [vp, i32, vp, vp, i32, u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
     "lr_bfv_plan_create": [vp, vp, u64, i32, C.POINTER(vp)],
     "lr_bfv_plan_create_ex": [vp, vp, u64, i32, vp, C.POINTER(vp)],

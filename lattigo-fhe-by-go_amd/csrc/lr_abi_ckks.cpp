@@ -846,13 +846,10 @@ extern "C" int lr_ckks_decrypt(lr_ckks_plan *pl, int level, const lr_poly *const
     });
 }
 
-extern "C" int lr_ckks_rescale(lr_ckks_plan *pl, lr_poly *c0, lr_poly *c1) {
-    return guarded([&]() -> int {
-    if (!pl || !c0 || !c1) return fail(LR_ERR_ARG, "null argument");
-    lr_context *c = pl->cQ;
-    LR_TRY(check_rescale(c, c0));
-    LR_TRY(check_rescale(c, c1));
-    LR_HIP(hipSetDevice(c->device));
+namespace lr_host {
+
+// one level of Rescale's loop on both components, each checked (check_rescale); the device is current
+int ckks_rescale_core(lr_context *c, lr_poly *c0, lr_poly *c1) {
     // ckks/evaluator.go:958-960 divides the two components one after the other.  They are independent, and at a small batch every
     // launch of one component leaves most of the chip idle: where the two polys can be addressed as ONE batch -- base + p * stride
     // reaches both, i.e. always for one poly each (stride = the distance between them) and for batches laid out back to back --
@@ -873,5 +870,17 @@ extern "C" int lr_ckks_rescale(lr_ckks_plan *pl, lr_poly *c0, lr_poly *c1) {
     }
     LR_TRY(rescale_ntt_domain(c, c0, true));
     return rescale_ntt_domain(c, c1, true);
+}
+
+}  // namespace lr_host
+
+extern "C" int lr_ckks_rescale(lr_ckks_plan *pl, lr_poly *c0, lr_poly *c1) {
+    return guarded([&]() -> int {
+    if (!pl || !c0 || !c1) return fail(LR_ERR_ARG, "null argument");
+    lr_context *c = pl->cQ;
+    LR_TRY(check_rescale(c, c0));
+    LR_TRY(check_rescale(c, c1));
+    LR_HIP(hipSetDevice(c->device));
+    return ckks_rescale_core(c, c0, c1);
     });
 }

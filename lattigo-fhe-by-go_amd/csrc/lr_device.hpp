@@ -478,6 +478,33 @@ inline LaunchVerdict launch_verdict(const CkksChainStepLaunch &L, int limbs, int
                                                         L.cx == L.a1);
 }
 hipError_t launch_ckks_chain_step(const CkksChainStepLaunch &L, int limbs, int batch, hipStream_t stream);
+
+// The tail of the products of one chunk of a CKKS power basis (lr_ckks_power_basis; the steps after MulRelin and Rescale in
+// computePowerBasis / computePowerBasisCheby, ckks/chebyshev_evaluation.go:92-99): see basis_tail_kernel (lr_ckks_basis.hip).  The chunk's
+// `products * batch` members lie back to back in the staging pair, first components then second ones; what differs per product travels
+// in a device table: one BasisTailProduct each, then `products` rows of `row` multiplier words, then as many rows of addend words.
+struct BasisTailProduct {
+    u64 *out[2];             // C[n]'s two polys
+    long long out_stride;    // between their batch members (one stride for both)
+    int tail;                // 0 copy | 1: 2 x - C[1] | 2: 2 x + const
+    int mult_side;           // tail 1: 0 none | 1: x is multiplied | 2: C[1] is
+};
+struct BasisTailLaunch {
+    const u64 *stage;                  // [2][members][stage_stride]
+    long long stage_stride;
+    const u64 *c1[2];                  // C[1], the subtrahend of tail 1
+    long long c1_stride[2];
+    const BasisTailProduct *products;  // device, [products]
+    const u64 *mult, *add;             // device, [products][row] each
+    int row, batch, n;
+    const LimbParams *lp;
+};
+// (member and component share grid z; the staging pair is never an output: the host code hands out a pool of its own)
+inline LaunchVerdict launch_verdict(const BasisTailLaunch &L, int limbs, int products) {
+    return launch_verdict(limbs <= 0 || products <= 0, L.n < 2 || (L.n & 1) || limbs > kMaxLimbs || limbs > L.row || L.batch < 1 ||
+                                                           (long long)products * L.batch > 32767 || !L.stage || !L.products || !L.mult || !L.add);
+}
+hipError_t launch_ckks_basis_tail(const BasisTailLaunch &L, int limbs, int products, hipStream_t stream);
 // Context.MultByMonomial (ring/ring.go:663): out = in * X^shift in Z_q[X]/(X^N+1), shift already reduced modulo 2N;
 // like the reference, negated coefficients are q - x without reduction (0 becomes q).  Not in place.
 hipError_t launch_monomial(const GaloisLaunch &L, int limbs, int batch, hipStream_t stream);

@@ -328,6 +328,60 @@ struct Pool {
     }
 };
 
+// Small host-filled tables for kernels whose per-member words and pointers do not fit the launch arguments (lr_ckks_power_basis): a ring
+// of slots, each a pinned host block and its device image.  A call fills a slot's pinned block, enqueues the copy on its stream and
+// records the slot's event behind it; the slot is handed out again only when that event has passed, so no later call rewrites words an
+// earlier call's copy may still read.  The device image is reused in stream order: copy and consumers share the handle's stream, and
+// that order has to hold from call to call -- lr_context_set_stream keeps it (the new stream waits for the old one's work).
+// Back-pressure, bounded: the event sits behind the copy, and the copy behind every kernel enqueued before it, so handing out a slot
+// that is still in flight waits on the host for everything up to kSlots chunks back; growing a slot synchronises the stream.
+struct TableSlots {
+    static constexpr int kSlots = 8;
+    struct Slot {
+        unsigned char *h = nullptr, *d = nullptr;
+        size_t bytes = 0;
+        hipEvent_t copied = nullptr;
+        bool in_flight = false;
+    } slot[kSlots];
+    int next = 0;
+    // the next slot with room for `bytes`, its last copy finished; growing one waits for the stream (its device image may be in use)
+    int take(hipStream_t stream, size_t bytes, Slot **out) {
+        Slot &s = slot[next];
+        next = (next + 1) % kSlots;
+        if (!s.copied) LR_HIP(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+        if (s.in_flight) {
+            LR_HIP(hipEventSynchronize(s.copied));
+            s.in_flight = false;
+        }
+        if (s.bytes < bytes) {
+            LR_HIP(hipStreamSynchronize(stream));
+            if (s.h) (void)hipHostFree(s.h);
+            if (s.d) (void)hipFree(s.d);
+            s.h = s.d = nullptr;
+            s.bytes = 0;
+            LR_HIP(hipHostMalloc((void **)&s.h, bytes));
+            LR_HIP(hipMalloc((void **)&s.d, bytes));
+            s.bytes = bytes;
+        }
+        *out = &s;
+        return LR_OK;
+    }
+    // the slot's first `bytes` bytes to its device image, on `stream`
+    int send(hipStream_t stream, Slot *s, size_t bytes) {
+        LR_HIP(hipMemcpyAsync(s->d, s->h, bytes, hipMemcpyHostToDevice, stream));
+        LR_HIP(hipEventRecord(s->copied, stream));
+        s->in_flight = true;
+        return LR_OK;
+    }
+    ~TableSlots() {
+        for (Slot &s : slot) {
+            if (s.h) (void)hipHostFree(s.h);
+            if (s.d) (void)hipFree(s.d);
+            if (s.copied) (void)hipEventDestroy(s.copied);
+        }
+    }
+};
+
 }  // namespace lr_host
 
 struct lr_bext {
@@ -380,6 +434,8 @@ struct lr_ckks_plan {
     Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q; lr_bfv_relinearize_deg: two of them per group of a pass; lr_abi_bfv_eval.cpp)
     Pool chainP;           // rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_abi_bfv_eval.cpp; with bfvP the two
                            // pairs of an accumulating lr_ckks_rotate_chain, lr_ckks_chain.cpp)
+    Pool basisS;           // lr_ckks_power_basis: the staging pair of a chunk's merged products, [2][members][mul_level + 1][N] (lr_ckks_basis.cpp)
+    TableSlots basisT;     // ... and its tables: the operands' pointers, the products' entries and words
     Pool zerosQ;           // one poly of zeros over Q: the `plus` operand of the NTT epilogue where a caller has none
     Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_plan_decomposition)
     // small batches: independent launches of one pipeline side by side (PlanFork); stream and events are created at the first fork
@@ -629,6 +685,7 @@ int check_cts(const lr_ckks_plan *pl, int level, int batch, std::initializer_lis
 int check_call(const lr_ckks_plan *pl, int level, int batch, std::initializer_list<const lr_poly *> cts);
 int begin_pipeline(const lr_ckks_plan *pl);
 int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride);
+int ckks_rescale_core(lr_context *c, lr_poly *c0, lr_poly *c1);
 
 }  // namespace lr_host
 using namespace lr_host;

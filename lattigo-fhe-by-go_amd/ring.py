@@ -551,6 +551,49 @@ def ckks_combine_constants(moduli, op, a, b, out, receiver="new"):
                              mult[:level_after.value + 1].copy() if mult_side.value else None)
 
 
+class CkksBasisSchedule:
+    """what ckks_power_basis_schedule yields: products (a list of _native.BasisProduct in the reference's order of creation), mult and
+    add [len(products)][len(moduli)] (the words of the Chebyshev tails, zero where unused), and index: n -> position in products"""
+
+    def __init__(self, products, mult, add):
+        self.products, self.mult, self.add = products, mult, add
+        self.index = {int(p.n): k for k, p in enumerate(products)}
+
+    def level(self, n, c1_level):
+        return c1_level if n == 1 else self.products[self.index[n]].level_after
+
+
+def ckks_power_basis_targets(degree, fast=True):
+    """The n of the computePowerBasis / computePowerBasisCheby calls of EvaluateChebyFast / EvaluatePolyFast (fast) or EvaluateChebyEco /
+    EvaluatePolyEco for a polynomial of that degree, in their order (ckks/chebyshev_evaluation.go:20-29, :46-55;
+    ckks/polynomial_evaluation.go:17-26, :42-51): 2 .. 2^L, then 2^i for L < i < M, with M = bits.Len64(degree - 1), L = M >> 1 or 1."""
+    M = (int(degree) - 1).bit_length()
+    L = M >> 1 if fast else 1
+    return list(range(2, (1 << L) + 1)) + [1 << i for i in range(L + 1, M)]
+
+
+def ckks_power_basis_schedule(moduli, default_scale, chebyshev, c1_level, c1_scale, targets):
+    """The scalar lines of the power basis as the reference runs it (lr_ckks_power_basis_schedule; computePowerBasis,
+    ckks/polynomial_evaluation.go:76-93, computePowerBasisCheby, ckks/chebyshev_evaluation.go:60-101): which products, and per product
+    the level, Rescale's trip count, the scale and the words of the Chebyshev tail.  Host only: needs no context and no device.
+    targets: the n of the caller's computePowerBasis(n) calls, in order (ckks_power_basis_targets).  Returns a CkksBasisSchedule."""
+    moduli = [int(q) for q in moduli]
+    L, T = len(moduli), len(targets)
+    if any(not 1 <= int(t) <= 65535 for t in targets):      # before the narrowing to 32 bits, which would wrap
+        raise LatticeRingError(4, "CKKS power basis schedule: a target is 0 or above 65535")
+    tg = (C.c_uint32 * max(T, 1))(*[int(t) for t in targets])
+    count = C.c_int(-1)
+    args = (_u64(moduli), L, float(default_scale), 1 if chebyshev else 0, int(c1_level), float(c1_scale), T, tg)
+    rc = lib().lr_ckks_power_basis_schedule(*args, 0, C.byref(count), None, None, None)
+    if rc != 0 and count.value < 0:
+        check(rc)
+    n = max(count.value, 0)
+    products = (nat.BasisProduct * max(n, 1))()
+    mult, add = np.zeros((max(n, 1), L), dtype=np.uint64), np.zeros((max(n, 1), L), dtype=np.uint64)
+    check(lib().lr_ckks_power_basis_schedule(*args, n, C.byref(count), products, mult.ctypes.data_as(C.c_void_p), add.ctypes.data_as(C.c_void_p)))
+    return CkksBasisSchedule([products[k] for k in range(count.value)], mult[:count.value].copy(), add[:count.value].copy())
+
+
 def NewContextWithParams(N, Moduli, device=0, options=None):
     """ring.NewContextWithParams (ring/ring_context.go:60).  Raises LatticeRingError
     LR_ERR_NOT_NTT_FRIENDLY where the reference returns its error value.  options: an Options (lr_options) or None for the defaults."""
@@ -846,6 +889,27 @@ class CkksPlan:
             idx <<= 1
             k >>= 1
         self.RotateChain(level, ct0, gens, keys, False, ctOut)
+
+    def PowerBasis(self, level, c1, schedule, evakey, outs):
+        """The products of a power basis as one call (lr_ckks_power_basis): c1 = C[1] at `level`, schedule: a CkksBasisSchedule
+        (ckks_power_basis_schedule), outs[k] = (out0, out1) receives C[schedule.products[k].n] on limbs 0 .. level_after.  The same bits
+        as per product MulRelin, Rescale (n_rescales times) and the CkksCombine call of the Chebyshev tail."""
+        n = len(schedule.products)
+        if len(outs) != n:
+            raise ValueError("one output per product")
+        prods = (nat.BasisProduct * max(n, 1))(*schedule.products)
+        if n == 0:      # an empty basis (targets [] or [1]): the call checks C[1] and the key and launches nothing
+            mult = add = np.zeros((1, level + 1), dtype=np.uint64)
+        else:
+            mult = np.ascontiguousarray(schedule.mult, dtype=np.uint64).reshape(n, -1)
+            add = np.ascontiguousarray(schedule.add, dtype=np.uint64).reshape(n, -1)
+        if mult.shape != add.shape:
+            raise LatticeRingError(3, "PowerBasis: mult and add have one shape")
+        o0 = (C.c_void_p * max(n, 1))(*[o[0].h.value if o[0] is not None else None for o in outs])
+        o1 = (C.c_void_p * max(n, 1))(*[o[1].h.value if o[1] is not None else None for o in outs])
+        check(lib().lr_ckks_power_basis(self.h, n, prods, mult.ctypes.data_as(C.c_void_p), add.ctypes.data_as(C.c_void_p),
+                                        mult.shape[1], level, c1[0].h, c1[1].h, evakey.h, o0, o1))
+        return outs
 
     def RotateHoisted(self, level, ct0, gens, rotkeys, ctOuts):
         """evaluator.RotateHoisted (ckks/evaluator.go:1252): ctOuts[r] = rotation of ct0 by the Galois element gens[r]."""
