@@ -9,9 +9,9 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 [ -n "$LR_BUILD_DIAG" ] && FLAGS="$FLAGS -DLR_BUILD_DIAG=1"
 mkdir -p build
 # the C ABI, one translation unit per handle family (lr_host.hpp is what they share)
-ABI_UNITS="lr_abi_core lr_abi_ring lr_abi_bext lr_abi_ckks lr_abi_batcher lr_abi_bfv lr_abi_bfv_eval lr_abi_bfv_batcher lr_abi_peer lr_bfv_encoder lr_ckks_encoder lr_bfv_encryptor lr_ckks_encryptor lr_keygen lr_collective lr_refresh lr_setup lr_ckks_lincomb lr_ckks_combine lr_ckks_chain lr_ckks_basis"
+ABI_UNITS="lr_abi_core lr_abi_ring lr_abi_bext lr_abi_ckks lr_abi_batcher lr_abi_bfv lr_abi_bfv_eval lr_abi_bfv_batcher lr_abi_peer lr_bfv_encoder lr_ckks_encoder lr_bfv_encryptor lr_ckks_encryptor lr_keygen lr_collective lr_refresh lr_setup lr_abi_ckks_eval lr_abi_ckks_scalar"
 link() {
-  $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../liblattigo_ring_hip.so build/lr_ntt.o build/lr_ewise.o build/lr_bext.o build/lr_bfv_encode.o build/lr_ckks_encode.o build/lr_bfv_encrypt.o build/lr_ckks_encrypt.o build/lr_keygen_kernels.o build/lr_collective_kernels.o build/lr_refresh_kernels.o build/lr_setup_kernels.o build/lr_ckks_lincomb_kernels.o build/lr_ckks_combine_kernels.o build/lr_ckks_chain_kernels.o build/lr_ckks_basis_kernels.o $(for u in $ABI_UNITS; do echo build/$u.o; done) build/lr_precompute.o build/lr_asm.o build/lr_asm_blob.o
+  $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../liblattigo_ring_hip.so build/lr_ntt.o build/lr_ewise.o build/lr_bext.o build/lr_bfv_encode.o build/lr_ckks_encode.o build/lr_bfv_encrypt.o build/lr_ckks_encrypt.o build/lr_ckks_eval.o build/lr_keygen_kernels.o build/lr_collective_kernels.o build/lr_refresh_kernels.o build/lr_setup_kernels.o $(for u in $ABI_UNITS; do echo build/$u.o; done) build/lr_precompute.o build/lr_asm.o build/lr_asm_blob.o
   echo "built $(cd .. && pwd)/liblattigo_ring_hip.so"
 }
 # developer shortcut: `build.sh lr_abi_ckks.cpp lr_ewise.hip` recompiles only the named sources and relinks (everything else must
@@ -24,10 +24,6 @@ if [ $# -gt 0 ]; then
       lr_collective.hip) $HIPCC $FLAGS -c $f -o build/lr_collective_kernels.o & spids+=($!) ;;
       lr_refresh.hip) $HIPCC $FLAGS -c $f -o build/lr_refresh_kernels.o & spids+=($!) ;;
       lr_setup.hip) $HIPCC $FLAGS -c $f -o build/lr_setup_kernels.o & spids+=($!) ;;
-      lr_ckks_lincomb.hip) $HIPCC $FLAGS -c $f -o build/lr_ckks_lincomb_kernels.o & spids+=($!) ;;
-      lr_ckks_combine.hip) $HIPCC $FLAGS -c $f -o build/lr_ckks_combine_kernels.o & spids+=($!) ;;
-      lr_ckks_chain.hip) $HIPCC $FLAGS -c $f -o build/lr_ckks_chain_kernels.o & spids+=($!) ;;
-      lr_ckks_basis.hip) $HIPCC $FLAGS -c $f -o build/lr_ckks_basis_kernels.o & spids+=($!) ;;
       *.hip) $HIPCC $FLAGS -c $f -o build/${f%.hip}.o & spids+=($!) ;;
       *.cpp) $HIPCC $FLAGS -x hip -c $f -o build/${f%.cpp}.o & spids+=($!) ;;
     esac
@@ -40,11 +36,11 @@ fi
 # the diagnostics ones too) on a bounded pool, and build/lr_asm_blob.cpp with their names and block sizes.  LLVM overrides the tools' directory
 python3 asmgen/catalogue.py build build
 pids=()
-for f in lr_ntt.hip lr_ewise.hip lr_bext.hip lr_bfv_encode.hip lr_ckks_encode.hip lr_bfv_encrypt.hip lr_ckks_encrypt.hip; do
+for f in lr_ntt.hip lr_ewise.hip lr_bext.hip lr_bfv_encode.hip lr_ckks_encode.hip lr_bfv_encrypt.hip lr_ckks_encrypt.hip lr_ckks_eval.hip; do
   $HIPCC $FLAGS -c $f -o build/${f%.hip}.o &
   pids+=($!)
 done
-# (lr_keygen.cpp and lr_keygen.hip share a stem, as do lr_collective.*, lr_refresh.*, lr_setup.*, lr_ckks_lincomb.*, lr_ckks_combine.*, lr_ckks_chain.* and lr_ckks_basis.*: the kernels' objects take another name)
+# (lr_keygen.cpp and lr_keygen.hip share a stem, as do lr_collective.*, lr_refresh.* and lr_setup.*: the kernels' objects take another name)
 $HIPCC $FLAGS -c lr_keygen.hip -o build/lr_keygen_kernels.o &
 pids+=($!)
 $HIPCC $FLAGS -c lr_collective.hip -o build/lr_collective_kernels.o &
@@ -52,14 +48,6 @@ pids+=($!)
 $HIPCC $FLAGS -c lr_refresh.hip -o build/lr_refresh_kernels.o &
 pids+=($!)
 $HIPCC $FLAGS -c lr_setup.hip -o build/lr_setup_kernels.o &
-pids+=($!)
-$HIPCC $FLAGS -c lr_ckks_lincomb.hip -o build/lr_ckks_lincomb_kernels.o &
-pids+=($!)
-$HIPCC $FLAGS -c lr_ckks_combine.hip -o build/lr_ckks_combine_kernels.o &
-pids+=($!)
-$HIPCC $FLAGS -c lr_ckks_chain.hip -o build/lr_ckks_chain_kernels.o &
-pids+=($!)
-$HIPCC $FLAGS -c lr_ckks_basis.hip -o build/lr_ckks_basis_kernels.o &
 pids+=($!)
 for u in $ABI_UNITS; do
   $HIPCC $FLAGS -x hip -c $u.cpp -o build/$u.o &

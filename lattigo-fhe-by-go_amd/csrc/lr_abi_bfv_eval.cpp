@@ -18,17 +18,6 @@
 namespace lr_host {
 namespace {
 
-// a component of a ciphertext: the caller's poly or one half of a pool pair
-struct Comp {
-    u64 *d;
-    long long stride;
-    Comp(u64 *d_, long long stride_) : d(d_), stride(stride_) {}
-    Comp(const lr_poly *p) : d(p->d), stride(p->stride()) {}
-};
-
-// the plan or its context asks for the call-by-call shape (lr_options::no_epilogue, as lr_setup reads it)
-bool plan_call_by_call(const lr_ckks_plan *pl) { return pl->opt.no_epilogue || pl->cQ->opt.no_epilogue; }
-
 // words of one poly over Q
 long long poly_words(const lr_context *cQ) { return (long long)cQ->h.L() * (long long)cQ->h.N; }
 
@@ -44,7 +33,7 @@ int bfv_permute_pair(lr_ckks_plan *pl, int batch, const Comp &a0, const Comp &a1
     const long long s = poly_words(cQ);
     const ComponentPair ins = component_pair(a0.d, a0.stride, a1.d, a1.stride, batch);
     if (batch == 1 && !pl->opt.no_pair && ins)
-        // one ciphertext: both components in one launch, the strides are the distances between them (see lr_ckks_rotate)
+        // one ciphertext: both components in one launch, the strides are the distances between them (see ckks_rotate_step)
         return run_permute(cQ, false, L1, 2, a0.d, ins.stride, pl->c0.d, component_distance(pl->c0.d, pl->c2x.d), gen);   // :723-724
     LR_TRY(run_permute(cQ, false, L1, batch, a0.d, a0.stride, pl->c0.d, s, gen));        // :723
     return run_permute(cQ, false, L1, batch, a1.d, a1.stride, pl->c2x.d, s, gen);        // :724
@@ -352,10 +341,8 @@ extern "C" int lr_bfv_relinearize_deg(lr_ckks_plan *pl, const lr_poly *const *ct
     LR_TRY(check_batch(pl, batch));
     for (int k = 0; k <= degree; ++k) LR_TRY(check_ct(pl, level, ct[k], batch));
     LR_TRY(check_cts(pl, level, batch, {o0, o1}));
-    const int alpha = pl->dec->alpha, beta = (level + 1 + alpha - 1) / alpha;
     for (int k = 0; k + 2 <= degree; ++k)
-        if (evks[k]->N != pl->cQ->h.N || evks[k]->batch < 2 * beta || evks[k]->limbs < pl->cQ->h.L() + pl->cP->h.L())
-            return fail(LR_ERR_SHAPE, "evaluation key: need batch >= 2*beta and |Q|+|P| limbs");
+        if (!switching_key_ok(pl, level, evks[k])) return fail(LR_ERR_SHAPE, "evaluation key: need batch >= 2*beta and |Q|+|P| limbs");
     return relin_core(pl, ct, degree, evks, o0, o1);
     });
 }

@@ -1,11 +1,9 @@
-// lr_abi_ckks.cpp -- C ABI: lr_ckks_plan, the key switch itself (ks_*, switch_keys_core, bfv_switch_keys_core / _grouped) and the
-// ckks.Evaluator call sequences over it (switchKeysInPlace, MulRelin, rotations, hoisted rotations, pk-encrypt, decrypt, Rescale).  The
-// BFV evaluator's pipelines over the same key switch are lr_abi_bfv_eval.cpp.
+// lr_abi_ckks.cpp -- C ABI: lr_ckks_plan, the key switch itself (ks_*, switch_keys_core, bfv_switch_keys_core / _grouped), the checks the
+// pipelines' entry points share, and the calls that sit on the key switch's own stages or beside it: switchKeysInPlace, the hoisted
+// rotations (they take the decomposition and the inner product apart), pk-encrypt and decrypt.  The evaluators' pipelines over the key
+// switch are lr_abi_ckks_eval.cpp (MulRelin, rotations and chains, Rescale, the power basis) and lr_abi_bfv_eval.cpp.
 #include "lr_host.hpp"
 
-// ------------------------------------------------------------------------------------------
-// ckks.Evaluator call sequences
-// ------------------------------------------------------------------------------------------
 namespace lr_host {
 // live plans per device that are not lanes of a batcher: one = a lone evaluator, whose small launches may run side by side (PlanFork)
 std::atomic<int> &standalone_plans(int device) {
@@ -571,34 +569,6 @@ int lr_host::bfv_switch_keys_grouped(lr_ckks_plan *pl, int batch, int groups, co
     return ks_coeff_tail(pl, level, members, acc);
 }
 
-// permuteNTT (ckks/evaluator.go:1448-1468): RotateColumns with a specific rotation key / Conjugate.
-// gen = the Galois element (ring.PermuteNTTIndex's `gen^power`); the two trailing Context calls (:1466-1467)
-// ride on the last ModDown pass.
-extern "C" int lr_ckks_rotate(lr_ckks_plan *pl, int level, const lr_poly *c0, const lr_poly *c1, uint64_t gen, const lr_poly *rotkey,
-                              lr_poly *o0, lr_poly *o1) {
-    return guarded([&]() -> int {
-    if (!pl || !c0 || !c1 || !rotkey || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
-    const int batch = c0->batch;
-    LR_TRY(check_call(pl, level, batch, {c0, c1, o0, o1}));
-    if (o0->stride() != o1->stride()) return fail(LR_ERR_SHAPE, "output polys must share their stride");
-    lr_context *cQ = pl->cQ;
-    LR_TRY(begin_pipeline(pl));
-    const int n = (int)cQ->h.N, L1 = level + 1;
-    const long long s = (long long)L1 * n;
-    for (Pool *p : {&pl->c0, &pl->c2x, &pl->q1, &pl->q2}) LR_TRY(p->ensure(cQ, (size_t)batch * s));
-    const ComponentPair ins = component_pair(c0->d, c0->stride(), c1->d, c1->stride(), batch);
-    if (batch == 1 && !pl->opt.no_pair && ins) {
-        // one ciphertext: both components in one launch, the strides are the distances between them (see ks_ntt_tail)
-        LR_TRY(run_permute_ntt(cQ, L1, 2, c0->d, ins.stride, pl->c0.d, component_distance(pl->c0.d, pl->c2x.d), gen));    // :1458-1459
-    } else {
-        LR_TRY(run_permute_ntt(cQ, L1, batch, c0->d, c0->stride(), pl->c0.d, s, gen));    // :1458
-        LR_TRY(run_permute_ntt(cQ, L1, batch, c1->d, c1->stride(), pl->c2x.d, s, gen));   // :1459
-    }
-    KeySwitchEpilogue fin{o0->d, o1->d, o0->stride(), pl->c0.d, nullptr, s};
-    return switch_keys_core(pl, level, batch, pl->c2x.d, s, rotkey, {{pl->q1.d, pl->q2.d}, {s, s}}, &fin);   // :1464-1467
-    });
-}
-
 // RotateHoisted + switchKeyHoisted (ckks/evaluator.go:1252-1391): n_rot rotations of one ciphertext share the
 // digit decomposition; per rotation the digits are permuted, multiplied into the rotation key and brought down.
 extern "C" int lr_ckks_rotate_hoisted(lr_ckks_plan *pl, int level, const lr_poly *c0, const lr_poly *c1, int n_rot,
@@ -644,86 +614,6 @@ extern "C" int lr_ckks_rotate_hoisted(lr_ckks_plan *pl, int level, const lr_poly
         }
     }
     return LR_OK;
-    });
-}
-
-namespace lr_host {
-
-// ckks/evaluator.go:1080-1104 after the argument checks: T holds the four operands (strided or through a pointer table)
-int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride) {
-    lr_context *cQ = pl->cQ;
-    LR_TRY(begin_pipeline(pl));
-    const int n = (int)cQ->h.N, L1 = level + 1;
-    const long long s = (long long)L1 * n;
-    for (Pool *p : {&pl->c0, &pl->c1, &pl->c2x, &pl->q1, &pl->q2}) LR_TRY(p->ensure(cQ, (size_t)batch * s));
-    // :1080-1095: MForm x2, MulCoeffsMontgomery x3, MulCoeffsMontgomeryAndAdd, one pass
-    T.c0 = pl->c0.d; T.c1 = pl->c1.d; T.c2 = pl->c2x.d;
-    T.c_stride = T.c1_stride = T.c2_stride = s;
-    T.n = n;
-    T.lp = cQ->d_lp;
-    LR_HIP(launch_tensor(T, L1, batch, cQ->stream));
-    // :1101 key switch of the degree-2 part, :1103-1104 the two additions fused into its last pass
-    KeySwitchEpilogue fin{o0, o1, o_stride, pl->c0.d, pl->c1.d, s};
-    return switch_keys_core(pl, level, batch, pl->c2x.d, s, evk, {{pl->q1.d, pl->q2.d}, {s, s}}, &fin);
-}
-
-}  // namespace lr_host
-
-extern "C" int lr_ckks_mulrelin(lr_ckks_plan *pl, int level, const lr_poly *a0, const lr_poly *a1, const lr_poly *b0,
-                                const lr_poly *b1, const lr_poly *evk, lr_poly *o0, lr_poly *o1) {
-    return guarded([&]() -> int {
-    if (!pl || !a0 || !a1 || !b0 || !b1 || !evk || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
-    const int batch = a0->batch;
-    LR_TRY(check_call(pl, level, batch, {a0, a1, b0, b1, o0, o1}));
-    if (o0->stride() != o1->stride()) return fail(LR_ERR_SHAPE, "output polys must share their stride");
-    TensorLaunch T;
-    T.a0 = a0->d; T.a1 = a1->d; T.b0 = b0->d; T.b1 = b1->d;
-    T.a0_stride = a0->stride(); T.a1_stride = a1->stride(); T.b0_stride = b0->stride(); T.b1_stride = b1->stride();
-    return mulrelin_core(pl, level, batch, T, evk, o0->d, o1->d, o0->stride());
-    });
-}
-
-
-// MulRelin with evakey == nil (ckks/evaluator.go:1038-1111): the degree-2 tensor, no key switch.  The squaring branch
-// (:1083-1088, c1 = 2 c0 c1 by AddLvl) and the regular one (:1090-1096, MulCoeffsMontgomeryAndAddLvl) produce the same canonical
-// residues when ct0 == ct1, so one kernel serves both.  Outputs may alias the inputs (the reference goes through its pools then).
-extern "C" int lr_ckks_mul_norelin(lr_ckks_plan *pl, int level, const lr_poly *a0, const lr_poly *a1, const lr_poly *b0,
-                                   const lr_poly *b1, lr_poly *o0, lr_poly *o1, lr_poly *o2) {
-    return guarded([&]() -> int {
-    if (!pl || !a0 || !a1 || !b0 || !b1 || !o0 || !o1 || !o2) return fail(LR_ERR_ARG, "null argument");
-    const int batch = a0->batch;
-    LR_TRY(check_call(pl, level, batch, {a0, a1, b0, b1, o0, o1, o2}));
-    lr_context *cQ = pl->cQ;
-    LR_HIP(hipSetDevice(cQ->device));
-    TensorLaunch T;
-    T.a0 = a0->d; T.a1 = a1->d; T.b0 = b0->d; T.b1 = b1->d;
-    T.a0_stride = a0->stride(); T.a1_stride = a1->stride(); T.b0_stride = b0->stride(); T.b1_stride = b1->stride();
-    T.c0 = o0->d; T.c1 = o1->d; T.c2 = o2->d;
-    T.c_stride = o0->stride(); T.c1_stride = o1->stride(); T.c2_stride = o2->stride();
-    T.n = (int)cQ->h.N;
-    T.lp = cQ->d_lp;
-    LR_HIP(launch_tensor(T, level + 1, batch, cQ->stream));
-    return LR_OK;
-    });
-}
-
-// MulRelin, plaintext x ciphertext (ckks/evaluator.go:1113-1131): out_k = MRed(MForm(pt), ct_k), k = 0, 1
-extern "C" int lr_ckks_mul_plain(lr_ckks_plan *pl, int level, const lr_poly *pt, const lr_poly *c0, const lr_poly *c1,
-                                 lr_poly *o0, lr_poly *o1) {
-    return guarded([&]() -> int {
-    if (!pl || !pt || !c0 || !c1 || !o0 || !o1) return fail(LR_ERR_ARG, "null argument");
-    const int batch = c0->batch;
-    LR_TRY(check_call(pl, level, batch, {c0, c1, o0, o1}));
-    if (pt->N != pl->cQ->h.N || pt->limbs < level + 1 || (pt->batch != batch && pt->batch != 1)) return fail(LR_ERR_SHAPE, "plaintext: limbs or batch");
-    lr_context *cQ = pl->cQ;
-    LR_HIP(hipSetDevice(cQ->device));
-    const int n = (int)cQ->h.N, L1 = level + 1;
-    const long long s = (long long)L1 * n;
-    LR_TRY(pl->c0.ensure(cQ, (size_t)pt->batch * s));
-    LR_TRY(run_ewise(cQ, LR_MFORM, L1, pt->batch, pt->d, pt->stride(), nullptr, 0, pl->c0.d, s, nullptr));            // :1129
-    const long long ms = pt->batch == 1 && batch > 1 ? 0 : s;
-    LR_TRY(run_ewise(cQ, LR_MUL_MONT, L1, batch, pl->c0.d, ms, c0->d, c0->stride(), o0->d, o0->stride(), nullptr));   // :1130
-    return run_ewise(cQ, LR_MUL_MONT, L1, batch, pl->c0.d, ms, c1->d, c1->stride(), o1->d, o1->stride(), nullptr);    // :1131
     });
 }
 
@@ -843,44 +733,5 @@ extern "C" int lr_ckks_decrypt(lr_ckks_plan *pl, int level, const lr_poly *const
     }
     if ((degree & 7) != 7) LR_TRY(run_ewise(cQ, LR_REDUCE, L1, batch, pt->d, pt->stride(), nullptr, 0, pt->d, pt->stride(), nullptr));    // :75
     return LR_OK;
-    });
-}
-
-namespace lr_host {
-
-// one level of Rescale's loop on both components, each checked (check_rescale); the device is current
-int ckks_rescale_core(lr_context *c, lr_poly *c0, lr_poly *c1) {
-    // ckks/evaluator.go:958-960 divides the two components one after the other.  They are independent, and at a small batch every
-    // launch of one component leaves most of the chip idle: where the two polys can be addressed as ONE batch -- base + p * stride
-    // reaches both, i.e. always for one poly each (stride = the distance between them) and for batches laid out back to back --
-    // every launch carries both (PN15QP880, one ciphertext: 121 -> 66 us).
-    lr_poly *lo = c0->d <= c1->d ? c0 : c1, *hi = lo == c0 ? c1 : c0;
-    const bool same_shape = c0->limbs == c1->limbs && c0->batch == c1->batch && c0->N == c1->N && c0->d != c1->d;
-    const ComponentPair pair = component_pair(lo->d, lo->stride(), hi->d, hi->stride(), lo->batch);
-    const bool one_each = pair.kind == ComponentPair::OneEach && pair.stride >= (long long)lo->limbs * (long long)lo->N;
-    if (!c->opt.rescale_unpaired && same_shape && (one_each || pair.kind == ComponentPair::BackToBack) &&
-        (long long)c0->batch * 2 * c0->limbs <= c->opt.pair_max_workgroups) {
-        lr_poly both = *lo;
-        both.owned = false;
-        both.batch = 2 * lo->batch;
-        both.stride_words = pair.stride;
-        LR_TRY(rescale_ntt_domain(c, &both, true));
-        c0->limbs = c1->limbs = both.limbs;
-        return LR_OK;
-    }
-    LR_TRY(rescale_ntt_domain(c, c0, true));
-    return rescale_ntt_domain(c, c1, true);
-}
-
-}  // namespace lr_host
-
-extern "C" int lr_ckks_rescale(lr_ckks_plan *pl, lr_poly *c0, lr_poly *c1) {
-    return guarded([&]() -> int {
-    if (!pl || !c0 || !c1) return fail(LR_ERR_ARG, "null argument");
-    lr_context *c = pl->cQ;
-    LR_TRY(check_rescale(c, c0));
-    LR_TRY(check_rescale(c, c1));
-    LR_HIP(hipSetDevice(c->device));
-    return ckks_rescale_core(c, c0, c1);
     });
 }

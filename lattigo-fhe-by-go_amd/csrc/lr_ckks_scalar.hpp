@@ -1,7 +1,7 @@
 // lr_ckks_scalar.hpp -- the scalar lines that ckks.Evaluator's constant-by-ciphertext methods share (AddConst, MultByConst,
 // MultByConstAndAdd; ckks/evaluator.go:373-734), restated for one modulus on the host: scaleUpExact, the two half-vector words before and
 // after MForm, and the domain on which Go's float-to-integer conversions are defined.  Included by the host-only constants functions
-// (lr_ckks_lincomb.cpp, lr_ckks_combine.cpp); no context, no device, no state.
+// (lr_abi_ckks_scalar.cpp); no context, no device, no state.
 #pragma once
 #include <cmath>
 
@@ -51,6 +51,8 @@ struct Limb {
     u64 q, qinv, psi;
     BarrettConst bred;
 };
+// psi = the limb's root word (ntt_psi1); 0 where every constant is real
+inline Limb limb_of(u64 q, u64 psi = 0) { return Limb{q, montgomery_const(q), psi, barrett_const(q)}; }
 
 // scaledConst for the coefficients below and above N / 2, before any MForm (:413-427, :436-438; :570-583, :595-596; :694-707, :719-720)
 inline void half_constants(double re, double im, double scale, const Limb &m, u64 *lo, u64 *hi) {
@@ -76,11 +78,12 @@ inline void half_constants_mform(double re, double im, double scale, const Limb 
     *hi = im != 0 ? mform(h, m.q, m.bred.hi, m.bred.lo) : *lo;
 }
 
-// the words of two polys overlap
-inline bool overlap(const lr_poly *a, const lr_poly *b) {
-    const u64 *a1 = a->d + (long long)(a->batch - 1) * a->stride() + (long long)a->alloc_limbs * (long long)a->N;
-    const u64 *b1 = b->d + (long long)(b->batch - 1) * b->stride() + (long long)b->alloc_limbs * (long long)b->N;
-    return a->d < b1 && b->d < a1;
+// MultByConst(ct, uint64(ratio), ...): the uint64 becomes a float64 again (:669-671), an integer constant at scale 1 with no imaginary
+// part (:698-709), so one word serves both halves
+inline u64 integer_multiplier_word(double ratio, const Limb &m) {
+    u64 w, unused;
+    half_constants_mform((double)(u64)ratio, 0, 1, m, &w, &unused);
+    return w;
 }
 
 }  // namespace ckks_scalar

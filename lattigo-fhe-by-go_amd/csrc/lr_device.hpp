@@ -287,7 +287,7 @@ struct HalfScalarLaunch {
     LimbScalars lo, hi;
 };
 
-// res = c0 + sum c_k ct_k (lr_ckks_lincomb.hip): evaluatePolyFromPowerBasis' chain AddConst, MultByConstAndAdd ... (ckks/
+// res = c0 + sum c_k ct_k (lr_ckks_eval.hip): evaluatePolyFromPowerBasis' chain AddConst, MultByConstAndAdd ... (ckks/
 // polynomial_evaluation.go:142-159) on both components of a degree-1 ciphertext in one pass.  Per limb, coefficient j and component u:
 //   acc = accumulate ? out_u : 0;  component 0 with has_add: acc = CRed(acc + (j < n/2 ? add_lo : add_hi))
 //   for k < count: bit k of pre_mask: acc = MRed(acc, pre_k);  acc = CRed(acc + MRed(x_k,u, j < n/2 ? lo_k : hi_k))
@@ -323,7 +323,7 @@ inline LaunchVerdict launch_verdict(const LinCombLaunch &L, int limbs, int batch
                                                         limbs > lincomb_limbs_per_launch(L.count, L.has_add) || batch > 32767);
 }
 
-// out = a (+|-) b over CKKS ciphertexts of any degree (lr_ckks_combine.hip): the element loops of evaluator.Add / AddNoMod / Sub / SubNoMod
+// out = a (+|-) b over CKKS ciphertexts of any degree (lr_ckks_eval.hip): the element loops of evaluator.Add / AddNoMod / Sub / SubNoMod
 // through evaluateInPlace (ckks/evaluator.go:227-342) with Sub's NegLvl tail (:186-192, :203-209), in one pass.  Per limb, coefficient j
 // and component u <= max(deg_a, deg_b), with s(j) = j < n/2 ? lo : hi:
 //   x = a_u (u <= deg_a), y = b_u (u <= deg_b; deg_b = -1: no b);  double_a: x = CRed(x + x);  mult_a: x = MRed(x, ma(j));
@@ -460,7 +460,7 @@ hipError_t launch_bfv_relin_fold(const BfvRelinFoldLaunch &L, int limbs, int bat
 
 // One step of an accumulating CKKS rotation chain in front of its key switch (lr_ckks_rotate_chain; the two PermuteNTT calls of
 // permuteNTT, ckks/evaluator.go:1458-1459, and the first component's half of the Add that follows the rotation in the slot-sum loop):
-// see ckks_chain_step_kernel (lr_ckks_chain.hip).  NTT domain, limbs 0 .. level.
+// see ckks_chain_step_kernel (lr_ckks_eval.hip).  NTT domain, limbs 0 .. level.
 struct CkksChainStepLaunch {
     const u64 *a0, *a1;      // the chain's state before the step
     long long a0_stride, a1_stride;
@@ -480,7 +480,7 @@ inline LaunchVerdict launch_verdict(const CkksChainStepLaunch &L, int limbs, int
 hipError_t launch_ckks_chain_step(const CkksChainStepLaunch &L, int limbs, int batch, hipStream_t stream);
 
 // The tail of the products of one chunk of a CKKS power basis (lr_ckks_power_basis; the steps after MulRelin and Rescale in
-// computePowerBasis / computePowerBasisCheby, ckks/chebyshev_evaluation.go:92-99): see basis_tail_kernel (lr_ckks_basis.hip).  The chunk's
+// computePowerBasis / computePowerBasisCheby, ckks/chebyshev_evaluation.go:92-99): see basis_tail_kernel (lr_ckks_eval.hip).  The chunk's
 // `products * batch` members lie back to back in the staging pair, first components then second ones; what differs per product travels
 // in a device table: one BasisTailProduct each, then `products` rows of `row` multiplier words, then as many rows of addend words.
 struct BasisTailProduct {

@@ -433,8 +433,8 @@ struct lr_ckks_plan {
     Pool encQ, encP;       // pk-encryption temporaries over Q||P (lr_ckks_encrypt_pk)
     Pool bfvP;             // bfv relinearize: keyswitchpool[2], [3] (two polys over Q; lr_bfv_relinearize_deg: two of them per group of a pass; lr_abi_bfv_eval.cpp)
     Pool chainP;           // rotation chains: the second pair of polys over Q that state and accumulators alternate on (lr_abi_bfv_eval.cpp; with bfvP the two
-                           // pairs of an accumulating lr_ckks_rotate_chain, lr_ckks_chain.cpp)
-    Pool basisS;           // lr_ckks_power_basis: the staging pair of a chunk's merged products, [2][members][mul_level + 1][N] (lr_ckks_basis.cpp)
+                           // pairs of an accumulating lr_ckks_rotate_chain, lr_abi_ckks_eval.cpp)
+    Pool basisS;           // lr_ckks_power_basis: the staging pair of a chunk's merged products, [2][members][mul_level + 1][N] (lr_abi_ckks_eval.cpp)
     TableSlots basisT;     // ... and its tables: the operands' pointers, the products' entries and words
     Pool zerosQ;           // one poly of zeros over Q: the `plus` operand of the NTT epilogue where a caller has none
     Pool stageQ, stageP;   // N = 2^16: the extensions land here and the transforms go out of place (fused top stage, see ks_plan_decomposition)
@@ -599,7 +599,7 @@ struct DigitExtension {
 //   bfv_add_pair                    (lr_abi_bfv_eval.cpp: lr_bfv_relinearize and the composed route of lr_bfv_relinearize_deg) batch == 1; inputs
 //                                   and outputs both; no output over the other component's operand; the two addends back to back
 //   bfv_permute_pair                (lr_abi_bfv_eval.cpp: lr_bfv_rotate and the composed rotation chains) batch == 1; (the outputs are two pools)
-//   lr_ckks_rotate                  batch == 1; (the outputs are two pools)
+//   ckks_rotate_step                (lr_abi_ckks_eval.cpp: lr_ckks_rotate and the composed rotation chains) batch == 1; (the outputs are two pools)
 //   lr_ckks_rescale                 !rescale_unpaired; the lower address first; one poly each only at a distance >= limbs * N (no overlap);
 //                                   same shapes; 2 * batch * limbs <= pair_max_workgroups
 // Only the rescale asks for a positive distance.  With the outputs of ks_ntt_tail at a negative one, N = 2^16 and Options::no_exttop, the
@@ -672,7 +672,22 @@ int moddown_pq_core(lr_bext *b, int level, const u64 *p1Q, long long p1Q_stride,
 bool moddown_epilogue_available(const lr_bext *b);
 DigitShape digit_shape(const lr_decomposer *d, int level, int crt);
 int decompose_core(lr_decomposer *d, int level, int crt, Rows in, int batch, Rows outQ, const Rows *outP, DigitExtension how = DigitExtension());
-// lr_abi_ckks.cpp: the key switch and the pipelines over it (the BFV evaluator's: lr_abi_bfv_eval.cpp)
+// what the two evaluator units (lr_abi_ckks_eval.cpp, lr_abi_bfv_eval.cpp) share
+// a component of a ciphertext: the caller's poly or one half of a pool pair
+struct Comp {
+    u64 *d;
+    long long stride;
+    Comp(u64 *d_, long long stride_) : d(d_), stride(stride_) {}
+    Comp(const lr_poly *p) : d(p->d), stride(p->stride()) {}
+};
+// the plan or its context asks for the call-by-call shape (lr_options::no_epilogue, as lr_setup reads it)
+inline bool plan_call_by_call(const lr_ckks_plan *pl) { return pl->opt.no_epilogue || pl->cQ->opt.no_epilogue; }
+// a switching key (evaluation or rotation key) serves a key switch at `level`: the ring, 2 * beta polys, |Q| + |P| limbs
+inline bool switching_key_ok(const lr_ckks_plan *pl, int level, const lr_poly *key) {
+    const int alpha = pl->dec->alpha, beta = (level + 1 + alpha - 1) / alpha;
+    return key->N == pl->cQ->h.N && key->batch >= 2 * beta && key->limbs >= pl->cQ->h.L() + pl->cP->h.L();
+}
+// lr_abi_ckks.cpp: the plan, the key switch and the calls next to it (the evaluators' pipelines over it: lr_abi_ckks_eval.cpp, lr_abi_bfv_eval.cpp)
 std::atomic<int> &standalone_plans(int device);
 int run_permute(lr_context *c, bool ntt_domain, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride, u64 gen, const u64 *const *in_table = nullptr);
 int run_permute_ntt(lr_context *c, int limbs, int batch, const u64 *in, long long in_stride, u64 *out, long long out_stride, u64 gen, const u64 *const *in_table = nullptr);
@@ -684,8 +699,8 @@ int check_batch(const lr_ckks_plan *pl, int batch);
 int check_cts(const lr_ckks_plan *pl, int level, int batch, std::initializer_list<const lr_poly *> cts);
 int check_call(const lr_ckks_plan *pl, int level, int batch, std::initializer_list<const lr_poly *> cts);
 int begin_pipeline(const lr_ckks_plan *pl);
+// lr_abi_ckks_eval.cpp (the batcher's merged MulRelin runs on it)
 int mulrelin_core(lr_ckks_plan *pl, int level, int batch, TensorLaunch T, const lr_poly *evk, u64 *o0, u64 *o1, long long o_stride);
-int ckks_rescale_core(lr_context *c, lr_poly *c0, lr_poly *c1);
 
 }  // namespace lr_host
 using namespace lr_host;

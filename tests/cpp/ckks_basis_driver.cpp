@@ -1,7 +1,7 @@
 // The CKKS power basis' host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_ckks_basis_sanitizers.py):
-// the REAL host code -- lr_ckks_basis.cpp, lr_ckks_combine.cpp, lr_abi_*.cpp (MulRelin, the key switch and Rescale are in lr_abi_ckks.cpp
-// and lr_abi_ring.cpp), lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in, the recording launch stubs
-// of tests/cpp/hipstub/, ckks_basis_stub.cpp and ckks_combine_stub.cpp.  lr_ckks_power_basis_schedule and lr_ckks_power_basis over
+// the REAL host code -- lr_abi_*.cpp (the basis, MulRelin and Rescale are in lr_abi_ckks_eval.cpp and lr_abi_ckks_scalar.cpp, the key switch
+// in lr_abi_ckks.cpp, the division in lr_abi_ring.cpp), lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP
+// stand-in and the recording launch stubs of tests/cpp/hipstub/.  lr_ckks_power_basis_schedule and lr_ckks_power_basis over
 //   * N = 2^12, 2^15 and 2^14 (the merged route) and 2^10 (no transform epilogue: composed), |Q| = 5 with |P| = 3 or 2;
 //   * the default plan and lr_options::no_epilogue (composed at every degree);
 //   * Chebyshev and monomial schedules with a layer of four products, C[1] at the top level and below it, scales that make products
@@ -147,7 +147,7 @@ static void run(const Plan &P, const Sched &S, int batch, bool counted) {
             const auto chunks = chunks_of(S, std::max(1, P.max_batch / batch));
             size_t widest = 1;
             for (const auto &chunk : chunks) widest = std::max(widest, chunk.size());
-            // (basis_route, lr_ckks_basis.cpp: a call whose widest chunk is a pair, at a batch of 8 or more up to N = 2^15, merges nothing)
+            // (basis_route, lr_abi_ckks_eval.cpp: a call whose widest chunk is a pair, at a batch of 8 or more up to N = 2^15, merges nothing)
             const bool merges = P.merged && !(widest == 2 && batch >= 8 && P.r.logn <= 15);
             for (const auto &chunk : chunks) {
                 if (merges && chunk.size() > 1) {

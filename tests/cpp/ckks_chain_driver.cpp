@@ -1,6 +1,6 @@
 // The CKKS rotation chain's host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_ckks_chain_sanitizers.py):
-// the REAL host code -- lr_ckks_chain.cpp, lr_abi_*.cpp (the key switch is in lr_abi_ckks.cpp), lr_host.hpp, lr_precompute.cpp -- compiled
-// with g++ against the host-only HIP stand-in, the recording launch stubs of tests/cpp/hipstub/ and ckks_chain_stub.cpp.
+// the REAL host code -- lr_abi_*.cpp (the chain is in lr_abi_ckks_eval.cpp, the key switch in lr_abi_ckks.cpp), lr_host.hpp,
+// lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/.
 // lr_ckks_rotate_chain over
 //   * N = 2^12, 2^14 and 2^15 (accumulating chains on the fused route) and 2^10 (no transform epilogue: composed), |Q| = 5 with |P| = 3 or 2;
 //   * the default plan, lr_options::no_epilogue (composed at every degree) and no_pair;
@@ -72,7 +72,7 @@ static void calls(const Plan &P, int level, int batch, bool counted) {
     const unsigned long long steps0 = lr::g_ckks_chain_step_launches.load();
     unsigned long long steps = 0;
     auto ran = [&](int n, int acc) {
-        if (P.fused && acc) steps += (unsigned long long)n;      // (chain_route, lr_ckks_chain.cpp: a replacing chain is composed everywhere)
+        if (P.fused && acc) steps += (unsigned long long)n;      // (chain_route, lr_abi_ckks_eval.cpp: a replacing chain is composed everywhere)
     };
     for (int acc = 0; acc < 2; ++acc)
         for (int n = 0; n <= 3; ++n) {

@@ -1,8 +1,7 @@
 // The host side of the CKKS linear combination under AddressSanitizer + UBSan and under ThreadSanitizer
-// (tests/test_host_ckks_lincomb_sanitizers.py): the REAL host code -- lr_ckks_lincomb.cpp with lr_abi_*.cpp, lr_host.hpp,
-// lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in, the recording launch stubs of tests/cpp/hipstub/ and the
-// stand-in of the unit's own launcher (ckks_lincomb_stub.cpp), which keeps every launch and touches the first and the last word of every
-// row a kernel would read or write.  Every refusal in the stated order with the message its caller reads; the split of 0, 1, 16, 17 and 33
+// (tests/test_host_ckks_lincomb_sanitizers.py): the REAL host code -- lr_abi_*.cpp (lr_abi_ckks_eval.cpp, lr_abi_ckks_scalar.cpp), lr_host.hpp,
+// lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/; the
+// stand-in of the pass's launcher keeps every launch and touches the first and the last word of every row a kernel would read or write.  Every refusal in the stated order with the message its caller reads; the split of 0, 1, 16, 17 and 33
 // terms into launches -- the term ranges, the accumulate flags, the constant on the first pass only, the limb ranges and the words of
 // every limb -- on polys whose members lie apart by more than their limbs and at a level below their limb count; the constants function
 // on two threads.  Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes on polys: parity is the GPU
@@ -32,15 +31,6 @@ extern std::mutex g_lincomb_mu;
 extern std::vector<LinCombRecord> g_lincomb_log;
 }  // namespace lr
 
-static std::atomic<int> g_fail{0};
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
 // a refused call: the code, no launch of any kind, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
 static std::vector<std::string> g_refusal_log;
 #define REFUSED(call, code)                                                                       \
@@ -50,16 +40,11 @@ static std::vector<std::string> g_refusal_log;
         CHECK(lr::g_stub_launches.load() == a_ && lr::g_lincomb_launches.load() == b_);           \
         g_refusal_log.push_back(lr_last_error_string());                                          \
     } while (0)
+#include "driver_check.hpp"      // CHECK, OK, poly()
 
 // DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
 static const uint64_t M8[8] = {1125899908022273ull, 1099512938497ull,    1099514314753ull,    1099515691009ull,
                                36028797019488257ull, 1125899908612097ull, 1125899909398529ull, 36028797023420417ull};
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
 
 static std::vector<lr::LinCombRecord> take_log() {
     std::lock_guard<std::mutex> lock(lr::g_lincomb_mu);

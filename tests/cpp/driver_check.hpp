@@ -1,5 +1,6 @@
-// What the drivers of the BFV evaluator's and the key switch's host side share (key_switch_driver.cpp, bfv_chain_driver.cpp,
-// bfv_relin_deg_driver.cpp): the check macros with their counters, the primes and the poly allocator.  TEST INFRASTRUCTURE.
+// What the drivers of the two evaluators' and the key switch's host side share (key_switch_driver.cpp, bfv_chain_driver.cpp,
+// bfv_relin_deg_driver.cpp, ckks_chain_driver.cpp, ckks_basis_driver.cpp, ckks_lincomb_driver.cpp, ckks_combine_driver.cpp): the check
+// macros with their counters, the primes and the poly allocator.  TEST INFRASTRUCTURE.
 #pragma once
 #include <atomic>
 #include <cstdint>
@@ -30,7 +31,8 @@ static std::atomic<int> g_fail{0}, g_calls{0}, g_refusals{0};
         ++g_calls;   \
     } while (0)
 #endif
-// a refusal: the code, and no launch (single-threaded part only)
+// a refusal: the code, and no launch (single-threaded part only; a driver that also keeps the message defines its own REFUSED first)
+#ifndef REFUSED
 #define REFUSED(x, code)                                                   \
     do {                                                                   \
         const unsigned long long before_ = lr::g_stub_launches.load();     \
@@ -38,6 +40,7 @@ static std::atomic<int> g_fail{0}, g_calls{0}, g_refusals{0};
         CHECK(lr::g_stub_launches.load() == before_);                      \
         ++g_refusals;                                                      \
     } while (0)
+#endif
 
 // DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
 static const uint64_t Q5[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 36028797019488257ull};

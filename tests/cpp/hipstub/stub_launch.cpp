@@ -1,4 +1,4 @@
-// Recording stand-ins for the kernel launchers of lr_device.hpp (lr_ntt.hip, lr_ewise.hip, lr_bext.hip, lr_asm.cpp), for the CPU-sanitizer
+// Recording stand-ins for the kernel launchers of lr_device.hpp (lr_ntt.hip, lr_ewise.hip, lr_bext.hip, lr_ckks_eval.hip, lr_asm.cpp), for the CPU-sanitizer
 // build of the host side (see hip/hip_runtime.h in this directory).  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.
 //
 // What a stub does instead of launching a kernel:
@@ -13,6 +13,8 @@
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
+#include <mutex>
+#include <vector>
 
 #include "lattigo_ring.h"
 #include "lr_device.hpp"
@@ -354,6 +356,106 @@ bool ext_epilogue_supported(const ExtTables &t, int n_in, int n) {
 hipError_t launch_div_selftest(u64, int, int, unsigned long long *d_mismatches, hipStream_t) {
     g_stub_launches.fetch_add(1);
     *d_mismatches = 0;
+    return hipSuccess;
+}
+
+// The launchers of lr_ckks_eval.hip (lr_abi_ckks_eval.cpp).  Each asks the product's launch_verdict and touches the first and the last
+// word of every row (and table entry) the real kernel would read or write.  The linear combination and the combine pass keep a copy of
+// every launch for their drivers to read and count on counters of their own; the chain step and the basis tail count as launches that
+// the drivers' REFUSED macro watches.
+std::atomic<unsigned long long> g_lincomb_launches{0};
+struct LinCombRecord {
+    LinCombLaunch L;
+    int limbs, batch;
+};
+std::mutex g_lincomb_mu;
+std::vector<LinCombRecord> g_lincomb_log;
+
+hipError_t launch_ckks_lincomb(const LinCombLaunch &L, int limbs, int batch, hipStream_t) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    g_lincomb_launches.fetch_add(1);
+    rd(L.lp + L.limb0, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = L.limb0; i < L.limb0 + limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            for (int u = 0; u < 2; ++u) {
+                for (int k = 0; k < L.count; ++k) rd(L.term[k].c[u] + b * L.term[k].stride[u] + row, L.n);
+                wr(L.out[u] + b * L.out_stride[u] + row, L.n);
+            }
+        }
+    std::lock_guard<std::mutex> lock(g_lincomb_mu);
+    g_lincomb_log.push_back(LinCombRecord{L, limbs, batch});
+    return hipSuccess;
+}
+
+std::atomic<unsigned long long> g_combine_launches{0};
+struct CombineRecord {
+    CombineLaunch L;
+    int limbs, batch;
+};
+std::mutex g_combine_mu;
+std::vector<CombineRecord> g_combine_log;
+
+hipError_t launch_ckks_combine(const CombineLaunch &L, int limbs, int batch, hipStream_t) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    g_combine_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    const int comps = combine_comps(L.deg_a, L.deg_b);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            for (int u = 0; u < comps; ++u) {
+                if (u <= L.deg_a) rd(L.a[u] + b * L.a_stride[u] + row, L.n);
+                if (u <= L.deg_b) rd(L.b[u] + b * L.b_stride[u] + row, L.n);
+                wr(L.out[u] + b * L.out_stride[u] + row, L.n);
+            }
+        }
+    std::lock_guard<std::mutex> lock(g_combine_mu);
+    g_combine_log.push_back(CombineRecord{L, limbs, batch});
+    return hipSuccess;
+}
+
+std::atomic<unsigned long long> g_ckks_chain_step_launches{0};
+
+hipError_t launch_ckks_chain_step(const CkksChainStepLaunch &L, int limbs, int batch, hipStream_t) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, batch)) return verdict_error(v);
+    g_stub_launches.fetch_add(1);
+    g_ckks_chain_step_launches.fetch_add(1);
+    rd(L.lp, limbs);
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < limbs; ++i) {
+            const long long row = (long long)i * L.n;
+            rd(L.a0 + b * L.a0_stride + row, L.n);
+            rd(L.a1 + b * L.a1_stride + row, L.n);
+            wr(L.plus0 + b * L.plus_stride + row, L.n);
+            wr(L.cx + b * L.cx_stride + row, L.n);
+        }
+    return hipSuccess;
+}
+
+std::atomic<unsigned long long> g_ckks_basis_tail_launches{0}, g_ckks_basis_tail_products{0};
+
+hipError_t launch_ckks_basis_tail(const BasisTailLaunch &L, int limbs, int products, hipStream_t) {
+    if (const LaunchVerdict v = launch_verdict(L, limbs, products)) return verdict_error(v);
+    g_stub_launches.fetch_add(1);
+    g_ckks_basis_tail_launches.fetch_add(1);
+    g_ckks_basis_tail_products.fetch_add((unsigned long long)products);
+    rd(L.lp, limbs);
+    const long long members = (long long)products * L.batch;
+    for (int k = 0; k < products; ++k) {
+        rd(L.products + k, 1);
+        const BasisTailProduct P = L.products[k];
+        rd(L.mult + (long long)k * L.row, limbs);
+        rd(L.add + (long long)k * L.row, limbs);
+        for (int u = 0; u < 2; ++u)
+            for (int b = 0; b < L.batch; ++b)
+                for (int i = 0; i < limbs; ++i) {
+                    const long long row = (long long)i * L.n;
+                    rd(L.stage + (u * members + (long long)k * L.batch + b) * L.stage_stride + row, L.n);
+                    if (P.tail == 1) rd(L.c1[u] + b * L.c1_stride[u] + row, L.n);
+                    wr(P.out[u] + b * P.out_stride + row, L.n);
+                }
+    }
     return hipSuccess;
 }
 

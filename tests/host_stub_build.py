@@ -1,6 +1,7 @@
 """The CPU build of the product's host side that the sanitizer tests share: every lattigo-fhe-by-go_amd/csrc/lr_abi_*.cpp, lr_host.hpp and
 lr_precompute.cpp, compiled with g++ against the host-only HIP stand-in and the recording launch stubs of tests/cpp/hipstub/ (hipstub.cpp,
-stub_launch.cpp), and linked with one driver from tests/cpp/.  The handles whose units stay out of the lr_abi_*.cpp set (the encoders, the
+stub_launch.cpp: the launchers of both evaluator units, lr_abi_bfv_eval.cpp and lr_abi_ckks_eval.cpp, among them), and linked with one
+driver from tests/cpp/.  The handles whose units stay out of the lr_abi_*.cpp set (the encoders, the
 encryptors, the key generator, the collective handle) name their unit and the stand-ins of their launchers; the shared set links as it does
 without them."""
 import concurrent.futures as cf

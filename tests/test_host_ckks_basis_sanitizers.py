@@ -1,9 +1,9 @@
-"""The CKKS power basis' host side (lattigo-fhe-by-go_amd/csrc/lr_ckks_basis.cpp: the schedule's recursion and scalar lines, the argument
+"""The CKKS power basis' host side (lattigo-fhe-by-go_amd/csrc/lr_abi_ckks_scalar.cpp and lr_abi_ckks_eval.cpp: the schedule's recursion and scalar lines, the argument
 and shape checks in the header's order, the route decision, the grouping into layers and chunks, the pointer tables and words in their
 pinned slots, the staging pair and its divisions, the views the composed route rescales) under AddressSanitizer + UBSan and under
 ThreadSanitizer (CPU build only, each run as its own executable), driven by tests/cpp/ckks_basis_driver.cpp: both routes, four degrees,
 two option sets, three max_batch values, ten schedules, outputs of exactly level_after + 1 limbs, first calls on fresh plans, the launch
-counts of each route, two plans on two threads, and every refusal.  The stand-in of the new launcher (tests/cpp/ckks_basis_stub.cpp)
+counts of each route, two plans on two threads, and every refusal.  The stand-in of its launcher (tests/cpp/hipstub/stub_launch.cpp)
 touches the first and the last word of every row and table entry the kernel would read or write, so a wrong pool size, stride, level or
 table offset is a sanitizer report."""
 import os
@@ -19,8 +19,7 @@ from host_stub_build import build_host_driver
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_ckks_basis_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_basis_driver", flags, tag, units=("lr_ckks_basis", "lr_ckks_combine"),
-                            stubs=("ckks_basis_stub", "ckks_combine_stub"))
+    exe = build_host_driver(str(tmp_path), "ckks_basis_driver", flags, tag)
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the routes, not the caller's env
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])

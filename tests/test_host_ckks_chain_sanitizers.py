@@ -1,10 +1,10 @@
-"""The CKKS rotation chain's host side (lattigo-fhe-by-go_amd/csrc/lr_ckks_chain.cpp: the argument and shape checks in the header's order,
+"""The CKKS rotation chain's host side (lattigo-fhe-by-go_amd/csrc/lr_abi_ckks_eval.cpp: the argument and shape checks in the header's order,
 the route decision, the two pool pairs that state and destination alternate on, the copy for crossed outputs, the second stride of the
 key switch's last pass, the detour of a one-step accumulating chain in place) under AddressSanitizer + UBSan and under ThreadSanitizer
 (CPU build only, each run as its own executable), driven by tests/cpp/ckks_chain_driver.cpp: lr_ckks_rotate_chain on both routes, four
 degrees, three option sets, levels 0, 2 and the top, batches 1, 2 and max_batch, every aliasing the header allows and polys of three
 different strides, first calls on fresh plans, the launch counts of each route, two plans on two threads, and every refusal.  The stand-in
-of the new launcher (tests/cpp/ckks_chain_stub.cpp) touches the first and the last word of every row the kernel would read or write, so a
+of its launcher (tests/cpp/hipstub/stub_launch.cpp) touches the first and the last word of every row the kernel would read or write, so a
 wrong pool size, stride or level is a sanitizer report."""
 import os
 import subprocess
@@ -19,7 +19,7 @@ from host_stub_build import build_host_driver
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_ckks_chain_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_chain_driver", flags, tag, units=("lr_ckks_chain",), stubs=("ckks_chain_stub",))
+    exe = build_host_driver(str(tmp_path), "ckks_chain_driver", flags, tag)
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the routes, not the caller's env
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])

@@ -1,4 +1,4 @@
-"""The host side of the CKKS combine call (lattigo-fhe-by-go_amd/csrc/lr_ckks_combine.cpp: the argument checks in their stated order, the
+"""The host side of the CKKS combine call (lattigo-fhe-by-go_amd/csrc/lr_abi_ckks_eval.cpp and lr_abi_ckks_scalar.cpp: the argument checks in their stated order, the
 one launch with its addresses, strides, degrees, flags and the six words of every limb, the host-only constants function) under
 AddressSanitizer + UBSan and under ThreadSanitizer (CPU build only), driven by the stand-alone program tests/cpp/ckks_combine_driver.cpp:
 every degree pair with b present and absent and every flag combination, batches 1 and 3, an operand of batch 1, a level below the polys'
@@ -18,7 +18,7 @@ from host_stub_build import build_host_driver, expected_refusals, refusal_messag
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_ckks_combine_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_combine_driver", flags, tag, units=["lr_ckks_combine"], stubs=["ckks_combine_stub"])
+    exe = build_host_driver(str(tmp_path), "ckks_combine_driver", flags, tag)
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     print(res.stdout)

@@ -1,4 +1,4 @@
-"""The host side of the CKKS linear combination (lattigo-fhe-by-go_amd/csrc/lr_ckks_lincomb.cpp: the argument checks in their stated
+"""The host side of the CKKS linear combination (lattigo-fhe-by-go_amd/csrc/lr_abi_ckks_eval.cpp and lr_abi_ckks_scalar.cpp: the argument checks in their stated
 order, the passes of sixteen terms, the limb ranges a launch's arguments have room for, the words of every limb, the host-only constants
 function) under AddressSanitizer + UBSan and under ThreadSanitizer (CPU build only), driven by the stand-alone program
 tests/cpp/ckks_lincomb_driver.cpp: 0, 1, 16, 17 and 33 terms with and without the constant, on top of the receiver and from zero, batches
@@ -18,7 +18,7 @@ from host_stub_build import build_host_driver, expected_refusals, refusal_messag
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
 ])
 def test_ckks_lincomb_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_lincomb_driver", flags, tag, units=["lr_ckks_lincomb"], stubs=["ckks_lincomb_stub"])
+    exe = build_host_driver(str(tmp_path), "ckks_lincomb_driver", flags, tag)
     clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
     print(res.stdout)
