@@ -8,56 +8,44 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 # experiments and lets lr_options::ntt_timeline / ntt_persist select them; the default build ships neither
 [ -n "$LR_BUILD_DIAG" ] && FLAGS="$FLAGS -DLR_BUILD_DIAG=1"
 mkdir -p build
-# the C ABI, one translation unit per handle family (lr_host.hpp is what they share)
-ABI_UNITS="lr_abi_core lr_abi_ring lr_abi_bext lr_abi_ckks lr_abi_batcher lr_abi_bfv lr_abi_bfv_eval lr_abi_bfv_batcher lr_abi_peer lr_bfv_encoder lr_ckks_encoder lr_bfv_encryptor lr_ckks_encryptor lr_keygen lr_collective lr_refresh lr_setup lr_abi_ckks_eval lr_abi_ckks_scalar"
+# The sources: every kernel file and every host unit of this directory (the C ABI, one translation unit per handle family, with lr_host.hpp
+# as what they share; lr_precompute.cpp; lr_asm.cpp), and the generated build/lr_asm_blob.cpp.  An object is named after its whole source
+# file name -- lr_keygen.hip and lr_keygen.cpp give build/lr_keygen.hip.o and build/lr_keygen.cpp.o -- and the library links all of them.
+SOURCES="$(echo lr_*.hip lr_*.cpp) build/lr_asm_blob.cpp"
+objects() { for f in "$@"; do echo "build/$(basename "$f").o"; done; }
+compile() {
+  case $1 in
+    build/*.cpp) g++ -O1 -fPIC -c "$1" -o "$(objects "$1")" ;;             # generated tables: no device code
+    *.hip) $HIPCC $FLAGS -c "$1" -o "$(objects "$1")" ;;
+    *.cpp) $HIPCC $FLAGS -x hip -c "$1" -o "$(objects "$1")" ;;
+  esac
+}
+# compiles the named sources, at most ${MAX_JOBS:-16} at a time (a failed compile stops the script where it is waited for: set -e)
+compile_all() {
+  local pids=()
+  for f in "$@"; do
+    if [ ${#pids[@]} -ge "${MAX_JOBS:-16}" ]; then
+      wait "${pids[0]}"
+      pids=("${pids[@]:1}")
+    fi
+    compile "$f" &
+    pids+=($!)
+  done
+  for p in "${pids[@]}"; do wait "$p"; done
+}
 link() {
-  $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../liblattigo_ring_hip.so build/lr_ntt.o build/lr_ewise.o build/lr_bext.o build/lr_bfv_encode.o build/lr_ckks_encode.o build/lr_bfv_encrypt.o build/lr_ckks_encrypt.o build/lr_ckks_eval.o build/lr_keygen_kernels.o build/lr_collective_kernels.o build/lr_refresh_kernels.o build/lr_setup_kernels.o $(for u in $ABI_UNITS; do echo build/$u.o; done) build/lr_precompute.o build/lr_asm.o build/lr_asm_blob.o
+  $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../liblattigo_ring_hip.so $(objects $SOURCES)
   echo "built $(cd .. && pwd)/liblattigo_ring_hip.so"
 }
 # developer shortcut: `build.sh lr_abi_ckks.cpp lr_ewise.hip` recompiles only the named sources and relinks (everything else must
 # have been built before); without arguments the whole library is built from scratch, which is what __graft_entry__.build() runs
 if [ $# -gt 0 ]; then
-  spids=()
-  for f in "$@"; do
-    case $f in
-      lr_keygen.hip) $HIPCC $FLAGS -c $f -o build/lr_keygen_kernels.o & spids+=($!) ;;
-      lr_collective.hip) $HIPCC $FLAGS -c $f -o build/lr_collective_kernels.o & spids+=($!) ;;
-      lr_refresh.hip) $HIPCC $FLAGS -c $f -o build/lr_refresh_kernels.o & spids+=($!) ;;
-      lr_setup.hip) $HIPCC $FLAGS -c $f -o build/lr_setup_kernels.o & spids+=($!) ;;
-      *.hip) $HIPCC $FLAGS -c $f -o build/${f%.hip}.o & spids+=($!) ;;
-      *.cpp) $HIPCC $FLAGS -x hip -c $f -o build/${f%.cpp}.o & spids+=($!) ;;
-    esac
-  done
-  for p in "${spids[@]}"; do wait $p; done     # (a failed compile stops here: set -e)
+  compile_all "$@"
   link
   exit 0
 fi
 # hand-scheduled assembly kernels: generate -> assemble -> embed, every code object of asmgen/catalogue.py (shipped(); with LR_BUILD_DIAG
 # the diagnostics ones too) on a bounded pool, and build/lr_asm_blob.cpp with their names and block sizes.  LLVM overrides the tools' directory
 python3 asmgen/catalogue.py build build
-pids=()
-for f in lr_ntt.hip lr_ewise.hip lr_bext.hip lr_bfv_encode.hip lr_ckks_encode.hip lr_bfv_encrypt.hip lr_ckks_encrypt.hip lr_ckks_eval.hip; do
-  $HIPCC $FLAGS -c $f -o build/${f%.hip}.o &
-  pids+=($!)
-done
-# (lr_keygen.cpp and lr_keygen.hip share a stem, as do lr_collective.*, lr_refresh.* and lr_setup.*: the kernels' objects take another name)
-$HIPCC $FLAGS -c lr_keygen.hip -o build/lr_keygen_kernels.o &
-pids+=($!)
-$HIPCC $FLAGS -c lr_collective.hip -o build/lr_collective_kernels.o &
-pids+=($!)
-$HIPCC $FLAGS -c lr_refresh.hip -o build/lr_refresh_kernels.o &
-pids+=($!)
-$HIPCC $FLAGS -c lr_setup.hip -o build/lr_setup_kernels.o &
-pids+=($!)
-for u in $ABI_UNITS; do
-  $HIPCC $FLAGS -x hip -c $u.cpp -o build/$u.o &
-  pids+=($!)
-done
-$HIPCC $FLAGS -x hip -c lr_precompute.cpp -o build/lr_precompute.o &
-pids+=($!)
-$HIPCC $FLAGS -x hip -c lr_asm.cpp -o build/lr_asm.o &
-pids+=($!)
-g++ -O1 -fPIC -c build/lr_asm_blob.cpp -o build/lr_asm_blob.o &
-pids+=($!)
-for p in "${pids[@]}"; do wait $p; done
+compile_all $SOURCES
 link

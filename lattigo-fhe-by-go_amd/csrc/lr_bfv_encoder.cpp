@@ -1,6 +1,6 @@
 // lr_bfv_encoder.cpp -- C ABI: lr_bfv_encoder, bfv.Encoder (bfv/encoder.go:28-182) for a batch of plaintexts on the device.
-// The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// of lr_bfv_encode.hip have a stand-in of their own (tests/cpp/bfv_encoder_stub.cpp).
+// The host sanitizer build (tests/host_stub_build.py) compiles this unit with every other; the launchers of lr_bfv_encode.hip have their
+// stand-in in tests/cpp/hipstub/stub_bfv_encode.cpp.
 #include "lr_host.hpp"
 
 // what bfv.NewEncoder builds (bfv/encoder.go:28-68), plus the staging of the host-value entry points

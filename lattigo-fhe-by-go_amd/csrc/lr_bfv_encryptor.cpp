@@ -1,9 +1,9 @@
 // lr_bfv_encryptor.cpp -- C ABI: lr_bfv_encryptor and lr_bfv_decryptor, pkEncryptor.encrypt / skEncryptor.encrypt (bfv/encryptor.go:169-223,
 // 306-345) and decryptor.Decrypt (bfv/decryptor.go:55-75) for a batch of ciphertexts on the device.  The randomness arrives in the compact
 // form the reference's samplers decide before they write limbs and is expanded by the kernels of lr_bfv_encrypt.hip.
-// The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// of lr_bfv_encrypt.hip have a stand-in of their own (tests/cpp/bfv_encryptor_stub.cpp).  What it shares with lr_ckks_encryptor.cpp,
-// lr_keygen.cpp and lr_collective.cpp is lr_qp_handle.hpp.
+// The host sanitizer build (tests/host_stub_build.py) compiles this unit with every other; the launchers of lr_bfv_encrypt.hip have their
+// stand-in in tests/cpp/hipstub/stub_bfv_encrypt.cpp.  What it shares with lr_ckks_encryptor.cpp, lr_keygen.cpp and lr_collective.cpp is
+// lr_qp_handle.hpp.
 #include "lr_qp_handle.hpp"
 
 // what newEncryptor builds (bfv/encryptor.go:100-119); the contexts, the scalars and the staging of the host-randomness entry points

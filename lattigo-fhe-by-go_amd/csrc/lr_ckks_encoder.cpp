@@ -1,6 +1,6 @@
 // lr_ckks_encoder.cpp -- C ABI: lr_ckks_encoder, ckks.Encoder (ckks/encoder.go:31-226) for a batch of plaintexts on the device.
-// The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// of lr_ckks_encode.hip have a stand-in of their own (tests/cpp/ckks_encoder_stub.cpp).
+// The host sanitizer build (tests/host_stub_build.py) compiles this unit with every other; the launchers of lr_ckks_encode.hip have their
+// stand-in in tests/cpp/hipstub/stub_ckks_encode.cpp.
 #include "lr_host.hpp"
 
 #include <cmath>

@@ -1,9 +1,9 @@
 // lr_ckks_encryptor.cpp -- C ABI: lr_ckks_encryptor, pkEncryptor.encrypt and skEncryptor.encrypt (ckks/encryptor.go:179-237, 318-362) for a
 // batch of ciphertexts on the device.  The randomness arrives in the compact form the reference's samplers decide before they write limbs
 // (the format of lr_bfv_encryptor) and is expanded by the kernels of lr_ckks_encrypt.hip and lr_bfv_encrypt.hip.
-// The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// it calls have a stand-in of their own (tests/cpp/ckks_encryptor_stub.cpp).  What it shares with lr_bfv_encryptor.cpp, lr_keygen.cpp and
-// lr_collective.cpp is lr_qp_handle.hpp.
+// The host sanitizer build (tests/host_stub_build.py) compiles this unit with every other; the launchers of lr_ckks_encrypt.hip have their
+// stand-in in tests/cpp/hipstub/stub_ckks_encrypt.cpp.  What it shares with lr_bfv_encryptor.cpp, lr_keygen.cpp and lr_collective.cpp is
+// lr_qp_handle.hpp.
 #include "lr_qp_handle.hpp"
 
 // what newEncryptor builds (ckks/encryptor.go:100-119); the contexts, the scalars and the staging of the host-randomness entry points

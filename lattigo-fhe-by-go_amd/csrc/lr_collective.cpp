@@ -3,8 +3,8 @@
 // (dckks/public_keyswitching.go:63-93, dbfv/public_keyswitching.go:111-148) and AggregateShares / KeySwitch of all four as one n-ary fold.
 // The randomness arrives in the compact form of the encryptors (lr_bfv_encryptor).  Kernels: lr_collective.hip, the expansions of
 // lr_ckks_encrypt.hip and lr_bfv_encrypt.hip, launch_mul2 and launch_ckks_pk_fast where the lines are pkEncryptor.encrypt's.
-// The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// it calls have a stand-in of their own (tests/cpp/collective_stub.cpp).  What it shares with the encryptors and lr_keygen.cpp is
+// The host sanitizer build (tests/host_stub_build.py) compiles this unit with every other; the launchers of lr_collective.hip have their
+// stand-in in tests/cpp/hipstub/stub_collective.cpp.  What it shares with the encryptors and lr_keygen.cpp is
 // lr_qp_handle.hpp.
 #include "lr_qp_handle.hpp"
 

@@ -2,9 +2,9 @@
 // GenPublicKey, newSwitchingKey and what GenRelinKey, GenSwitchingKey and genrotKey put in front of it.  The randomness arrives in the
 // compact form of the encryptors (lr_bfv_encryptor); the uniform halves are the caller's polys.  Kernels: lr_keygen.hip and the expansion
 // of lr_ckks_encrypt.hip.
-// The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// it calls have a stand-in of their own (tests/cpp/keygen_stub.cpp).  That is why the extern "C" entry points live here and not in a
-// lr_abi_keygen.cpp.  What it shares with the encryptors and lr_collective.cpp is lr_qp_handle.hpp.
+// The host sanitizer build (tests/host_stub_build.py) compiles this unit with every other; the launchers of lr_keygen.hip have their
+// stand-in in tests/cpp/hipstub/stub_keygen.cpp.  The extern "C" entry points live here, beside the handle.  What it shares with the
+// encryptors and lr_collective.cpp is lr_qp_handle.hpp.
 #include "lr_qp_handle.hpp"
 
 // what NewKeyGenerator builds (ckks/keygen.go:79-94); the contexts, the scalars and the staging of the host-randomness entry points

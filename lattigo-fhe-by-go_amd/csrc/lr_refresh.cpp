@@ -4,8 +4,8 @@
 // (:182-190), Finalize (:193-197), lift (:199-205).  The noise arrives in the encryptors' compact form, the CKKS mask as word planes of
 // signed multi-word integers, the BFV mask as one row of values below t.  Kernels: lr_refresh.hip, the expansions of lr_ckks_encrypt.hip
 // and lr_bfv_encrypt.hip, launch_fold, launch_bfv_lift and launch_simple_scale; the ModDowns are lr_bext's.
-// The unit's name keeps it out of the lr_abi_*.cpp set, as lr_keygen.cpp's and lr_collective.cpp's do; what it shares with them is
-// lr_qp_handle.hpp.
+// The launchers of lr_refresh.hip have their stand-in for the host sanitizer build in tests/cpp/hipstub/stub_refresh.cpp; what the unit
+// shares with lr_keygen.cpp and lr_collective.cpp is lr_qp_handle.hpp.
 #include "lr_qp_handle.hpp"
 
 // what the two NewRefreshProtocol constructors build (dckks/public_refresh.go:23-35, dbfv/public_refresh.go:79-96); the contexts, the

@@ -4,8 +4,8 @@
 // every Aggregate* as one n-ary fold over all of Q||P.  The dckks twins compute the same lines but for relinkey_gen_naive.go:73-75 (below).
 // The randomness arrives in the compact form of the encryptors; crs and crp are the caller's polys.  Kernels: lr_setup.hip, the expansion
 // of lr_ckks_encrypt.hip and the fold of lr_collective.hip.
-// The unit's name keeps it out of the lr_abi_*.cpp set that the shared sanitizer build links against its fixed launch stubs: the launchers
-// it calls have a stand-in of their own (tests/cpp/setup_stub.cpp), as for lr_keygen.cpp.
+// The host sanitizer build (tests/host_stub_build.py) compiles this unit with every other; the launchers of lr_setup.hip have their
+// stand-in in tests/cpp/hipstub/stub_setup.cpp.
 #include "lr_qp_handle.hpp"
 
 // what the four New*Protocol constructors build: polypool / tmpPoly over Q||P, and here the pool of the transformed samples of one pass

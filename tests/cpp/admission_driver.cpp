@@ -13,23 +13,12 @@
 #include <cstring>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#include "driver_check.hpp"
 
 namespace lr {
 extern thread_local int g_stub_last_ext[5];
 extern thread_local int g_stub_last_keymac_wide[2];
 }
-
-static int g_fail = 0;
-#define OK(x)                                                                                                    \
-    do {                                                                                                         \
-        if ((x) != LR_OK) {                                                                                      \
-            std::fprintf(stderr, "failed: %s (line %d): %s\n", #x, __LINE__, lr_last_error_string());            \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
 
 int main(int argc, char **argv) {
     int a = 1;
@@ -81,5 +70,5 @@ int main(int argc, char **argv) {
             OK(lr_context_destroy(cp));
         }
     }
-    return g_fail ? 1 : 0;
+    return g_fail.load() ? 1 : 0;
 }

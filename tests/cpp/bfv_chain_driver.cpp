@@ -221,8 +221,6 @@ int main() {
         drop(B);
     }
     CHECK(lr::g_bfv_chain_step_crossed.load() == 0);                       // no step pass ever got the other component's operand as an output
-    CHECK(hipstub_live_allocations() == 0);                                // every pool and table went with its handle
-    std::printf("bfv_chain: calls %d, refusals %d, step launches %llu, failures %d\n", g_calls.load(), g_refusals.load(),
-                lr::g_bfv_chain_step_launches.load(), g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS, g_refusals, "bfv_chain: calls %d, refusals %d, step launches %llu", g_calls.load(), g_refusals.load(),
+                lr::g_bfv_chain_step_launches.load());
 }

@@ -1,10 +1,10 @@
 // The BFV encryptor's and decryptor's host side under AddressSanitizer + UBSan and under ThreadSanitizer
-// (tests/test_host_bfv_encryptor_sanitizers.py): the REAL host code -- lr_bfv_encryptor.cpp with lr_abi_*.cpp, lr_host.hpp,
-// lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in, the recording launch stubs of tests/cpp/hipstub/ and the
-// encryptor's own (bfv_encryptor_stub.cpp), which touch the first and the last byte of everything a kernel would read or write.
-// pk and sk, fast and through P, host and device-pointer randomness, both shapes (lr_options::no_epilogue), batches 1, 3 and max_batch
-// with the pools and the staging buffer reused across calls, wide polys, shared and per-ciphertext keys; Decrypt at degrees 0, 1, 2 and 9;
-// two handles on two threads; the recorded launch sequence of both shapes for pk through P; every refusal.
+// (tests/test_host_bfv_encryptor_sanitizers.py): the REAL host code -- lr_bfv_encryptor.cpp with every other host unit of the library --
+// compiled with g++ against the host-only HIP stand-in and the launch stand-ins of tests/cpp/hipstub/, which touch the first and the last
+// byte of everything a kernel would read or write. pk and sk, fast and through P, host and device-pointer randomness, both shapes
+// (lr_options::no_epilogue), batches 1, 3 and max_batch with the pools and the staging buffer reused across calls, wide polys, shared and
+// per-ciphertext keys; Decrypt at degrees 0, 1, 2 and 9; two handles on two threads; the recorded launch sequence of both shapes for pk
+// through P; every refusal.
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <atomic>
 #include <cstdint>
@@ -14,9 +14,8 @@
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#define REFUSED REFUSED_MSG      // here a refusal is logged with its message
+#include "driver_check.hpp"
 
 namespace lr {
 extern std::atomic<unsigned long long> g_stub_launches, g_encryptor_stub_launches;
@@ -28,50 +27,13 @@ int encryptor_stub_limbs(int i);
 int encryptor_stub_batch(int i);
 }  // namespace lr
 
-static std::atomic<int> g_fail{0};
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-// a refused call: the code as CHECK sees it, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
-static std::vector<std::string> g_refusal_log;
-#define REFUSED(cond)                                    \
-    do {                                                 \
-        CHECK(cond);                                     \
-        g_refusal_log.push_back(lr_last_error_string()); \
-    } while (0)
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16): three for Q, one for P
-static const uint64_t Qm[4] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull};
 static const int NQ = 3, NP = 1, MAXB = 5;
 
 static unsigned long long launches() { return lr::g_stub_launches.load() + lr::g_encryptor_stub_launches.load(); }
 
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
-
-struct Rings {
-    lr_context *q = nullptr, *p = nullptr;
-    Rings(uint64_t N, const lr_options *opt) {
-        OK(opt ? lr_context_create_ex(N, Qm, NQ, 0, opt, &q) : lr_context_create(N, Qm, NQ, 0, &q));
-        OK(opt ? lr_context_create_ex(N, Qm + NQ, NP, 0, opt, &p) : lr_context_create(N, Qm + NQ, NP, 0, &p));
-    }
-    ~Rings() {
-        OK(lr_context_destroy(p));
-        OK(lr_context_destroy(q));
-    }
-};
-
 // one encryptor and one decryptor through every call shape; returns the number of accepted calls
 static int exercise(uint64_t N, const lr_options *opt) {
-    Rings r(N, opt);
+    Rings r(N, Qm, NQ, NP, opt);
     lr_bfv_encryptor *enc = nullptr;
     lr_bfv_decryptor *dec = nullptr;
     OK(opt ? lr_bfv_encryptor_create_ex(r.q, r.p, MAXB, opt, &enc) : lr_bfv_encryptor_create(r.q, r.p, MAXB, &enc));
@@ -125,7 +87,7 @@ static void sequences() {
         lr_options opt;
         OK(lr_options_init(&opt));
         opt.no_epilogue = call_by_call;
-        Rings r(N, &opt);
+        Rings r(N, Qm, NQ, NP, &opt);
         lr_bfv_encryptor *enc = nullptr;
         OK(lr_bfv_encryptor_create_ex(r.q, r.p, batch, &opt, &enc));
         lr_poly *pk0 = poly(r.q, NQ + NP, 1), *pk1 = poly(r.q, NQ + NP, 1), *pt = poly(r.q, NQ, 1), *c0 = poly(r.q, NQ, batch), *c1 = poly(r.q, NQ, batch);
@@ -163,7 +125,7 @@ static void sequences() {
 static int refusals() {
     const uint64_t N = 16;
     int count = 0;
-    Rings r(N, nullptr), other(N, nullptr);
+    Rings r(N, Qm, NQ, NP, nullptr), other(N, Qm, NQ, NP, nullptr);
     lr_context *small = nullptr, *big = nullptr;
     OK(lr_context_create(4, Qm, NQ, 0, &small));
     OK(lr_context_create(2 * N, Qm + NQ, NP, 0, &big));
@@ -280,11 +242,5 @@ int main() {
         b.join();
         calls += threaded.load();
     }
-    CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
-    CHECK((int)g_refusal_log.size() == refused);
-    std::printf("refusal messages begin\n");
-    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
-    std::printf("refusal messages end\n");
-    std::printf("bfv_encryptor: calls %d, refusals %d, failures %d\n", calls, refused, g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS | EVENTS | LOG, refused, "bfv_encryptor: calls %d, refusals %d", calls, refused);
 }

@@ -10,33 +10,16 @@
 #include <cstdio>
 #include <vector>
 
-#include "lattigo_ring.h"
+#include "driver_check.hpp"
 
 namespace lr {
 extern std::atomic<unsigned long long> g_stub_launches;
 }
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
 
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16): Q, and two more as QMul
-static const uint64_t Qm[4] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull};
-static const uint64_t Mm[2] = {1125899908612097ull, 1125899909398529ull};
+// Q: Qm's first four; QMul: P3's first two
 static const int NQ = 4, MAXB = 130;
 static const uint64_t N = 1 << 10;
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
 
 struct Operands {
     std::vector<lr_poly *> a, b, o;
@@ -65,7 +48,7 @@ static int call_mul(lr_bfv_plan *pl, const std::vector<lr_poly *> &a, const std:
 int main() {
     lr_context *q = nullptr, *m = nullptr;
     OK(lr_context_create(N, Qm, NQ, 0, &q));
-    OK(lr_context_create(N, Mm, 2, 0, &m));
+    OK(lr_context_create(N, P3, 2, 0, &m));
     int calls = 0, refusals = 0;
     for (int variant = 0; variant < 3; ++variant) {
         lr_options opt;
@@ -141,6 +124,5 @@ int main() {
     }
     OK(lr_context_destroy(m));
     OK(lr_context_destroy(q));
-    std::printf("bfv_mul_deg: calls %d, refusals %d, failures %d\n", calls, refusals, g_fail);
-    return g_fail ? 1 : 0;
+    return driver_end(0, refusals, "bfv_mul_deg: calls %d, refusals %d", calls, refusals);
 }

@@ -252,8 +252,6 @@ int main() {
         drop(B);
     }
     CHECK(lr::g_bfv_relin_fold_crossed.load() == 0);                       // no fold ever got a term or the other component as an output
-    CHECK(hipstub_live_allocations() == 0);                                // every pool and table went with its handle
-    std::printf("bfv_relin_deg: calls %d, refusals %d, fold launches %llu, failures %d\n", g_calls.load(), g_refusals.load(),
-                lr::g_bfv_relin_fold_launches.load(), g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS, g_refusals, "bfv_relin_deg: calls %d, refusals %d, fold launches %llu", g_calls.load(), g_refusals.load(),
+                lr::g_bfv_relin_fold_launches.load());
 }

@@ -389,10 +389,6 @@ int main() {
         drop(A);
         drop(B);
     }
-    CHECK(hipstub_live_allocations() == 0);                                // every pool, slot and table went with its handle
-    CHECK(hipstub_live_events() == 0);
-    std::printf("ckks_basis: calls %d, refusals %d, tail launches %llu, tail products %llu, combine launches %llu, failures %d\n", g_calls.load(),
-                g_refusals.load(), lr::g_ckks_basis_tail_launches.load(), lr::g_ckks_basis_tail_products.load(), lr::g_combine_launches.load(),
-                g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS | EVENTS, g_refusals, "ckks_basis: calls %d, refusals %d, tail launches %llu, tail products %llu, combine launches %llu", g_calls.load(),
+                g_refusals.load(), lr::g_ckks_basis_tail_launches.load(), lr::g_ckks_basis_tail_products.load(), lr::g_combine_launches.load());
 }

@@ -191,8 +191,6 @@ int main() {
         drop(A);
         drop(B);
     }
-    CHECK(hipstub_live_allocations() == 0);                                // every pool and table went with its handle
-    std::printf("ckks_chain: calls %d, refusals %d, step launches %llu, failures %d\n", g_calls.load(), g_refusals.load(),
-                lr::g_ckks_chain_step_launches.load(), g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS, g_refusals, "ckks_chain: calls %d, refusals %d, step launches %llu", g_calls.load(), g_refusals.load(),
+                lr::g_ckks_chain_step_launches.load());
 }

@@ -16,9 +16,6 @@
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
 #include "lr_device.hpp"
 
 namespace lr {
@@ -31,20 +28,8 @@ extern std::mutex g_combine_mu;
 extern std::vector<CombineRecord> g_combine_log;
 }  // namespace lr
 
-// a refused call: the code, no launch of any kind, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
-static std::vector<std::string> g_refusal_log;
-#define REFUSED(call, code)                                                                       \
-    do {                                                                                          \
-        const unsigned long long a_ = lr::g_stub_launches.load(), b_ = lr::g_combine_launches.load(); \
-        CHECK((call) == (code));                                                                  \
-        CHECK(lr::g_stub_launches.load() == a_ && lr::g_combine_launches.load() == b_);           \
-        g_refusal_log.push_back(lr_last_error_string());                                          \
-    } while (0)
-#include "driver_check.hpp"      // CHECK, OK, poly()
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
-static const uint64_t M8[8] = {1125899908022273ull, 1099512938497ull,    1099514314753ull,    1099515691009ull,
-                               36028797019488257ull, 1125899908612097ull, 1125899909398529ull, 36028797023420417ull};
+#define REFUSED REFUSED_MSG_NO_LAUNCH      // here a refusal launches nothing of any kind and is logged with its message
+#include "driver_check.hpp"
 
 static std::vector<lr::CombineRecord> take_log() {
     std::lock_guard<std::mutex> lock(lr::g_combine_mu);
@@ -300,11 +285,5 @@ int main() {
         b.join();
         CHECK(done.load() == 2);
     }
-    CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
-    CHECK((int)g_refusal_log.size() == refused);
-    std::printf("refusal messages begin\n");
-    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
-    std::printf("refusal messages end\n");
-    std::printf("ckks combine: calls %d, launches %llu, refusals %d, failures %d\n", calls, lr::g_combine_launches.load(), refused, g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS | EVENTS | LOG, refused, "ckks combine: calls %d, launches %llu, refusals %d", calls, lr::g_combine_launches.load(), refused);
 }

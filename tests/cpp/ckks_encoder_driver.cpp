@@ -1,10 +1,9 @@
 // The CKKS encoder's host side under AddressSanitizer + UBSan (tests/test_host_ckks_encoder_sanitizers.py): the REAL host code --
-// lr_ckks_encoder.cpp with lr_abi_*.cpp, lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in, the recording
-// launch stubs of tests/cpp/hipstub/ and the encoder's own (ckks_encoder_stub.cpp), which touch the first and the last word of everything a
-// kernel would read or write.  Both routes (by slot count and by lr_options::ckks_encoder_tiled), batches 1 and max_batch (256 at N = 2^4: the
-// one-kernel form of fused Encode), slot counts 1, 8
-// and N / 2, the lowest and the highest level, a caller's root table and the library's, host-value and device-pointer entry points, wide
-// plaintext polys, the table builders and every refusal.
+// lr_ckks_encoder.cpp with every other host unit of the library -- compiled with g++ against the host-only HIP stand-in and the launch
+// stand-ins of tests/cpp/hipstub/, which touch the first and the last word of everything a kernel would read or write.  Both routes (by
+// slot count and by lr_options::ckks_encoder_tiled), batches 1 and max_batch (256 at N = 2^4: the one-kernel form of fused Encode), slot
+// counts 1, 8 and N / 2, the lowest and the highest level, a caller's root table and the library's, host-value and device-pointer entry
+// points, wide plaintext polys, the table builders and every refusal.
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <atomic>
 #include <cmath>
@@ -14,35 +13,15 @@
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#include "driver_check.hpp"
 
 namespace lr {
 extern std::atomic<unsigned long long> g_stub_launches, g_ckks_stub_launches, g_ckks_stub_fused, g_ckks_stub_stages;
 }
 
-static int g_fail = 0;
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
-static const uint64_t Qm[4] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull};
 static const int NQ = 3;
 
 static unsigned long long launches() { return lr::g_stub_launches.load() + lr::g_ckks_stub_launches.load(); }
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
 
 static int log2_of(uint64_t x) {
     int l = 0;
@@ -197,7 +176,5 @@ int main() {
         OK(lr_context_destroy(other));
         OK(lr_context_destroy(q));
     }
-    CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
-    std::printf("ckks_encoder: calls %d, refusals %d, failures %d\n", calls, refused, g_fail);
-    return g_fail ? 1 : 0;
+    return driver_end(ALLOCATIONS | EVENTS, refused, "ckks_encoder: calls %d, refusals %d", calls, refused);
 }

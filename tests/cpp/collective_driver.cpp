@@ -1,11 +1,10 @@
 // The collective handle's host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_collective_sanitizers.py):
-// the REAL host code -- lr_collective.cpp with lr_abi_*.cpp, lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP
-// stand-in, the recording launch stubs of tests/cpp/hipstub/ and the stand-ins of the handle's own launchers (collective_stub.cpp,
-// ckks_encryptor_stub.cpp, bfv_encryptor_stub.cpp), which touch the first and the last byte of everything a kernel would read or write.
-// Every entry point in its host and device-pointer form, both shapes (lr_options::no_epilogue), batches 1, 3 and max_batch with the pool
-// and the staging buffer reused across consecutive host-form calls, wide polys, shared and per-ciphertext keys, |P| = 1 and |P| = 2,
-// every level, 33 shares (a second fold pass) with out aliasing a share and the base; two handles on two threads; the launch counts of
-// both shapes; every refusal.
+// the REAL host code -- lr_collective.cpp with every other host unit of the library -- compiled with g++ against the host-only HIP stand-in
+// and the launch stand-ins of tests/cpp/hipstub/, which touch the first and the last byte of everything a kernel would read or write. Every
+// entry point in its host and device-pointer form, both shapes (lr_options::no_epilogue), batches 1, 3 and max_batch with the pool and the
+// staging buffer reused across consecutive host-form calls, wide polys, shared and per-ciphertext keys, |P| = 1 and |P| = 2, every level,
+// 33 shares (a second fold pass) with out aliasing a share and the base; two handles on two threads; the launch counts of both shapes;
+// every refusal.
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <atomic>
 #include <cstdint>
@@ -15,58 +14,19 @@
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#define REFUSED REFUSED_MSG      // here a refusal is logged with its message
+#include "driver_check.hpp"
 
 namespace lr {
 extern std::atomic<unsigned long long> g_stub_launches, g_encryptor_stub_launches, g_ckks_expand_launches, g_ckks_fast_launches, g_cks_share_launches,
     g_pcks_addend_launches, g_fold_launches;
 }  // namespace lr
 
-static std::atomic<int> g_fail{0};
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-// a refused call: the code as CHECK sees it, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
-static std::vector<std::string> g_refusal_log;
-#define REFUSED(cond)                                    \
-    do {                                                 \
-        CHECK(cond);                                     \
-        g_refusal_log.push_back(lr_last_error_string()); \
-    } while (0)
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
-static const uint64_t Qm[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 1099516280833ull};
 static const int MAXB = 5, SHARES = 33;
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
-
-struct Rings {
-    lr_context *q = nullptr, *p = nullptr;
-    int nq, np;
-    Rings(uint64_t N, int nq_, int np_, const lr_options *opt) : nq(nq_), np(np_) {
-        OK(opt ? lr_context_create_ex(N, Qm, nq, 0, opt, &q) : lr_context_create(N, Qm, nq, 0, &q));
-        OK(opt ? lr_context_create_ex(N, Qm + nq, np, 0, opt, &p) : lr_context_create(N, Qm + nq, np, 0, &p));
-    }
-    ~Rings() {
-        OK(lr_context_destroy(p));
-        OK(lr_context_destroy(q));
-    }
-};
 
 // one handle through every entry point; returns the number of accepted calls
 static int exercise(uint64_t N, int nq, int np, const lr_options *opt) {
-    Rings r(N, nq, np, opt);
+    Rings r(N, Qm, nq, np, opt);
     const int rows = nq + np;
     lr_collective *col = nullptr;
     OK(opt ? lr_collective_create_ex(r.q, r.p, MAXB, opt, &col) : lr_collective_create(r.q, r.p, MAXB, &col));
@@ -135,7 +95,7 @@ static void sequences() {
         lr_options opt;
         OK(lr_options_init(&opt));
         opt.no_epilogue = cbc;
-        Rings r(N, nq, np, &opt);
+        Rings r(N, Qm, nq, np, &opt);
         lr_collective *col = nullptr;
         lr_bext *bext = nullptr;
         OK(lr_collective_create_ex(r.q, r.p, n, &opt, &col));
@@ -201,7 +161,7 @@ static int refusals() {
     const uint64_t N = 16;
     const int nq = 3, np = 1, rows = 4, top = 2;
     int count = 0;
-    Rings r(N, nq, np, nullptr), other(N, nq, np, nullptr);
+    Rings r(N, Qm, nq, np, nullptr), other(N, Qm, nq, np, nullptr);
     lr_context *small = nullptr, *smallp = nullptr, *big = nullptr, *dev1 = nullptr;
     OK(lr_context_create(4, Qm, nq, 0, &small));
     OK(lr_context_create(4, Qm + nq, np, 0, &smallp));
@@ -362,11 +322,5 @@ int main() {
         b.join();
         calls += threaded.load();
     }
-    CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
-    CHECK((int)g_refusal_log.size() == refused);
-    std::printf("refusal messages begin\n");
-    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
-    std::printf("refusal messages end\n");
-    std::printf("collective: calls %d, refusals %d, failures %d\n", calls, refused, g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS | EVENTS | LOG, refused, "collective: calls %d, refusals %d", calls, refused);
 }

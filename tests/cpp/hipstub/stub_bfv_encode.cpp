@@ -1,8 +1,4 @@
-// Recording stand-ins for the launchers of lr_bfv_encode.hip, for the CPU-sanitizer build of the BFV encoder's host side
-// (tests/test_host_bfv_encoder_sanitizers.py); the companion of hipstub/stub_launch.cpp, which stays as it is.  TEST INFRASTRUCTURE: no
-// arithmetic of the hot path lives here.  A stub counts the launch and touches the first and the last word of everything the real kernel
-// would read or write -- the slot values, the tables, the one-limb rows, every limb of every plaintext -- at the addresses the launch names:
-// "device" memory is malloc'ed at its exact size, so a wrong size, stride or batch count in the host code is an AddressSanitizer report.
+// Recording stand-ins for the launchers of lr_bfv_encode.hip (stub_touch.hpp says what a stand-in does): each counts its launch.
 #include <atomic>
 
 #include "lr_device.hpp"

@@ -1,9 +1,5 @@
-// Recording stand-ins for the launchers of lr_bfv_encrypt.hip, for the CPU-sanitizer build of the BFV encryptor's host side
-// (tests/test_host_bfv_encryptor_sanitizers.py); the companion of hipstub/stub_launch.cpp, which stays as it is.  TEST INFRASTRUCTURE: no
-// arithmetic of the hot path lives here.  A stub records its name with the count of shared-stub launches before it (the driver reads the
-// call order from that) and touches the first and the last byte of everything the real kernel would read or write -- the bit planes, the
-// noise bytes, every limb of every poly -- at the addresses the launch names: "device" memory is malloc'ed at its exact size, so a wrong
-// size, stride or batch count in the host code is an AddressSanitizer report.
+// Recording stand-ins for the launchers of lr_bfv_encrypt.hip (stub_touch.hpp says what a stand-in does): each records its name with the
+// count of shared-stub launches before it, from which a driver reads the call order.
 #include <atomic>
 #include <mutex>
 #include <string>

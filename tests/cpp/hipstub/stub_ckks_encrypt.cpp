@@ -1,8 +1,4 @@
-// Stand-ins for the launchers of lr_ckks_encrypt.hip, for the CPU-sanitizer build of the CKKS encryptor's host side
-// (tests/test_host_ckks_encryptor_sanitizers.py); the companion of bfv_encryptor_stub.cpp, which serves the launchers the two encryptors
-// share and stays as it is.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.  A stub counts its launch and touches the
-// first and the last byte of everything the real kernel would read or write at the addresses the launch names: "device" memory is
-// malloc'ed at its exact size, so a wrong size, stride, part offset or batch count in the host code is an AddressSanitizer report.
+// Stand-ins for the launchers of lr_ckks_encrypt.hip (stub_touch.hpp says what a stand-in does): each counts its launch.
 #include <atomic>
 
 #include "lr_device.hpp"
@@ -10,7 +6,7 @@
 
 namespace lr {
 
-extern std::atomic<unsigned long long> g_encryptor_stub_launches;      // bfv_encryptor_stub.cpp
+extern std::atomic<unsigned long long> g_encryptor_stub_launches;      // stub_bfv_encrypt.cpp
 std::atomic<unsigned long long> g_ckks_expand_launches{0}, g_ckks_fast_launches{0};
 
 hipError_t launch_ckks_expand(const CkksExpandLaunch &L, int limbs, int batch, hipStream_t) {

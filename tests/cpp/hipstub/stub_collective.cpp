@@ -1,9 +1,4 @@
-// Stand-ins for the launchers of lr_collective.hip, for the CPU-sanitizer build of the collective handle's host side
-// (tests/test_host_collective_sanitizers.py); the expansions and the pk pass it shares with the encryptors are served by
-// ckks_encryptor_stub.cpp and bfv_encryptor_stub.cpp, which stay as they are.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives
-// here.  A stub counts its launch and touches the first and the last byte of everything the real kernel would read or write at the
-// addresses the launch names: "device" memory is malloc'ed at its exact size, so a wrong size, stride, level or share count in the host
-// code is an AddressSanitizer report.
+// Stand-ins for the launchers of lr_collective.hip (stub_touch.hpp says what a stand-in does): each counts its launch.
 #include <atomic>
 
 #include "lr_device.hpp"

@@ -1,8 +1,4 @@
-// Stand-ins for the launchers of lr_keygen.hip, for the CPU-sanitizer build of the key generator's host side
-// (tests/test_host_keygen_sanitizers.py); the expansion it shares with the CKKS encryptor is served by ckks_encryptor_stub.cpp, which
-// stays as it is.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.  A stub counts its launch and touches the first and the
-// last byte of everything the real kernel would read or write at the addresses the launch names: "device" memory is malloc'ed at its
-// exact size, so a wrong size, stride, digit or key count in the host code is an AddressSanitizer report.
+// Stand-ins for the launchers of lr_keygen.hip (stub_touch.hpp says what a stand-in does): each counts its launch.
 #include <atomic>
 
 #include "lr_device.hpp"

@@ -1,6 +1,8 @@
-// What the launch stand-ins under tests/cpp share: the touches that stand for a kernel's reads and writes.  "Device" memory is malloc'ed at
-// its exact size, so touching the first and the last byte of a range the launch names turns a wrong size, stride or count in the host code
-// into an AddressSanitizer report.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.
+// What the launch stand-ins of this directory share (stub_launch.cpp, and one stub_<kernel file>.cpp per handle's kernel file), for the CPU
+// build of the host side that the sanitizer tests run (tests/host_stub_build.py): the touches that stand for a kernel's reads and writes.
+// A stand-in counts or records its launch and touches the first and the last byte of everything the real kernel would read or write, at
+// the addresses the launch names.  "Device" memory is malloc'ed at its exact size, so a wrong size, stride, level or count in the host
+// code is an AddressSanitizer report.  TEST INFRASTRUCTURE: no arithmetic of the hot path lives here.
 #pragma once
 #include "lr_arith.hpp"
 

@@ -17,37 +17,16 @@
 #include <thread>
 #include <vector>
 
-#include "lattigo_ring.h"
+#include "driver_check.hpp"
 
-extern "C" {
-void hipstub_fail_memcpy_async_after(long calls, long bytes);
-long hipstub_live_allocations(void);
-}
-
-static std::atomic<int> g_fail{0};
-#define CHECK(cond)                                                                          \
-    do {                                                                                     \
-        if (!(cond)) {                                                                       \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            g_fail.fetch_add(1);                                                             \
-        }                                                                                    \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-
-// DefaultParams[PN15QP880]'s first primes: congruent to 1 modulo 2^16, so NTT-friendly for every degree used here
-static const uint64_t Qm[4] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull};
-static const uint64_t Pm[2] = {1125899908612097ull, 1125899909398529ull};
+// Q: Qm's first four, P: P3's first two (congruent to 1 modulo 2^16, so NTT-friendly for every degree used here); Q16 and P16 in the N = 2^16 section
 static const int NQ = 4, NP = 2, LEVEL = 3, BETA = 2;
-// DefaultParams[PN16QP1761]'s first primes: congruent to 1 modulo 2^17 (the N = 2^16 section)
-static const uint64_t Qm16[4] = {36028797019488257ull, 35184372744193ull, 35184373006337ull, 35184376545281ull};
-static const uint64_t Pm16[2] = {36028797023420417ull, 36028797024206849ull};
 
 struct Ct {
     lr_poly *c[2];
 };
 static lr_poly *poly(lr_context *ctx, int limbs, int batch, uint64_t tag) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
+    lr_poly *p = poly(ctx, limbs, batch);
     uint64_t N = 0;
     OK(lr_context_info(ctx, &N, nullptr, nullptr));
     std::vector<uint64_t> h((size_t)batch * limbs * N, 0);
@@ -70,8 +49,8 @@ int main(int argc, char **argv) {
     // ---- a lone plan at N = 2^16 forks its independent launches to an auxiliary stream (PlanFork): one ciphertext, device 1
     {
         lr_context *q = nullptr, *p = nullptr;
-        OK(lr_context_create(1 << 16, Qm16, NQ, 1, &q));
-        OK(lr_context_create(1 << 16, Pm16, NP, 1, &p));
+        OK(lr_context_create(1 << 16, Q16, NQ, 1, &q));
+        OK(lr_context_create(1 << 16, P16, NP, 1, &p));
         lr_ckks_plan *pl = nullptr;
         OK(lr_ckks_plan_create(q, p, 1, &pl));
         lr_poly *key = poly(q, NQ + NP, 2 * BETA, 5), *a0 = poly(q, NQ, 1, 100), *a1 = poly(q, NQ, 1, 200), *o0 = poly(q, NQ, 1, 0), *o1 = poly(q, NQ, 1, 0);
@@ -91,7 +70,7 @@ int main(int argc, char **argv) {
     lr_ckks_plan *lplan[LANES];
     for (int i = 0; i < LANES; ++i) {
         OK(lr_context_create(N, Qm, NQ, 0, &lq[i]));
-        OK(lr_context_create(N, Pm, NP, 0, &lp[i]));
+        OK(lr_context_create(N, P3, NP, 0, &lp[i]));
         OK(lr_ckks_plan_create(lq[i], lp[i], MAXB, &lplan[i]));
     }
     lr_ckks_batcher *bat = nullptr;
@@ -105,8 +84,8 @@ int main(int argc, char **argv) {
     lr_ckks_plan *bks[LANES];
     for (int i = 0; i < LANES; ++i) {
         OK(lr_context_create(N, Qm, NQ, 0, &bq[i]));
-        OK(lr_context_create(N, Pm, NP, 0, &bp[i]));
-        OK(lr_context_create(N, Qm16, NQ, 0, &bm[i]));              // (any other NTT-friendly basis of the same length stands in for QMul)
+        OK(lr_context_create(N, P3, NP, 0, &bp[i]));
+        OK(lr_context_create(N, Q16, NQ, 0, &bm[i]));              // (any other NTT-friendly basis of the same length stands in for QMul)
         OK(lr_bfv_plan_create(bq[i], bm[i], 65537, MAXB, &bmul[i]));
         OK(lr_ckks_plan_create(bq[i], bp[i], MAXB, &bks[i]));
     }
@@ -117,7 +96,7 @@ int main(int argc, char **argv) {
     // ---- contexts shared by all threads (immutable after creation; their scratch is leased per call), on both "devices"
     lr_context *sq = nullptr, *sp = nullptr, *rq = nullptr;
     OK(lr_context_create(N, Qm, NQ, 0, &sq));
-    OK(lr_context_create(N, Pm, NP, 0, &sp));
+    OK(lr_context_create(N, P3, NP, 0, &sp));
     OK(lr_context_create(N, Qm, NQ, 1, &rq));                    // the "root" of the peer copies lives on device 1
     lr_poly *root = nullptr;
     OK(lr_poly_alloc(rq, NQ, T, &root));
@@ -268,8 +247,6 @@ int main(int argc, char **argv) {
         OK(lr_context_destroy(lp[i]));
     }
     for (lr_context *c : {sq, sp, rq}) OK(lr_context_destroy(c));
-    CHECK(hipstub_live_allocations() == 0);                          // every device buffer and pinned table went with its handle
-    std::printf("threads %d iterations %d: served %d, refused %d, callers of the failed batch %d, batches %llu (largest %d), failures %d\n", T, ITERS,
-                served.load(), refused.load(), injected_seen.load(), (unsigned long long)batches, largest, g_fail.load());
-    return g_fail.load() == 0 ? 0 : 1;
+    return driver_end(ALLOCATIONS, refused.load(), "threads %d iterations %d: served %d, refused %d, callers of the failed batch %d, batches %llu (largest %d)", T, ITERS,
+                served.load(), refused.load(), injected_seen.load(), (unsigned long long)batches, largest);
 }

@@ -29,10 +29,6 @@
     } while (0)
 #include "driver_check.hpp"
 
-// Q5 / P3 of driver_check.hpp with DefaultParams[PN16QP1761]'s first primes (congruent to 1 modulo 2^17)
-static const uint64_t P2[2] = {1125899908612097ull, 1125899909398529ull};
-static const uint64_t Q16[4] = {36028797019488257ull, 35184372744193ull, 35184373006337ull, 35184376545281ull};
-static const uint64_t P16[2] = {36028797023420417ull, 36028797024206849ull};
 static const int MAXB = 5;
 
 struct Ring {
@@ -42,7 +38,7 @@ struct Ring {
     const uint64_t *P;
     int nP;
 };
-static const Ring kRings[3] = {{1 << 12, Q5, 5, P3, 3}, {1 << 15, Q5, 5, P2, 2}, {1 << 16, Q16, 4, P16, 2}};
+static const Ring kRings[3] = {{1 << 12, Q5, 5, P3, 3}, {1 << 15, Q5, 5, P3, 2}, {1 << 16, Q16, 4, P16, 2}};
 
 static const int kVariants = 10;
 static const char *set_variant(lr_options *o, int v) {
@@ -326,7 +322,5 @@ int main(int argc, char **argv) {
         }
     }
     CHECK(forks16 > 0 && forks_other == 0 && grouped > 0);                // the lone plan forks at N = 2^16 only; the digits' extensions are grouped
-    CHECK(hipstub_live_allocations() == 0);                                // every pool and table went with its handle
-    std::printf("key_switch: calls %d, refusals %d, forks %llu, grouped extensions %llu, failures %d\n", g_calls.load(), g_refusals.load(), forks16, grouped, g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS, g_refusals, "key_switch: calls %d, refusals %d, forks %llu, grouped extensions %llu", g_calls.load(), g_refusals.load(), forks16, grouped);
 }

@@ -1,10 +1,9 @@
 // The key generator's host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_keygen_sanitizers.py): the REAL
-// host code -- lr_keygen.cpp with lr_abi_*.cpp, lr_host.hpp, lr_precompute.cpp -- compiled with g++ against the host-only HIP stand-in,
-// the recording launch stubs of tests/cpp/hipstub/ and the stand-ins of the key generator's own launchers (keygen_stub.cpp,
-// ckks_encryptor_stub.cpp), which touch the first and the last byte of everything a kernel would read or write.  Every entry point in
-// its host and device-pointer form, both shapes (lr_options::no_epilogue), 1, 3 and max_batch keys (5, and 70: more than one pass) with the pool and the staging buffer
-// reused across consecutive host-form calls, wide polys, shared and per-key secret keys, |P| = 1 and a ragged |P| = 2 whose last digit
-// owns one row; two handles on two threads; the launch counts of both shapes; every refusal.
+// host code -- lr_keygen.cpp with every other host unit of the library -- compiled with g++ against the host-only HIP stand-in and the
+// launch stand-ins of tests/cpp/hipstub/, which touch the first and the last byte of everything a kernel would read or write.  Every entry
+// point in its host and device-pointer form, both shapes (lr_options::no_epilogue), 1, 3 and max_batch keys (5, and 70: more than one pass)
+// with the pool and the staging buffer reused across consecutive host-form calls, wide polys, shared and per-key secret keys, |P| = 1 and a
+// ragged |P| = 2 whose last digit owns one row; two handles on two threads; the launch counts of both shapes; every refusal.
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <atomic>
 #include <cstdint>
@@ -14,59 +13,20 @@
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#define REFUSED REFUSED_MSG      // here a refusal is logged with its message
+#include "driver_check.hpp"
 
 namespace lr {
 extern std::atomic<unsigned long long> g_stub_launches, g_ckks_expand_launches, g_keygen_skin_launches, g_keygen_finish_launches, g_keygen_pk_launches;
 }  // namespace lr
 
-static std::atomic<int> g_fail{0};
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-// a refused call: the code as CHECK sees it, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
-static std::vector<std::string> g_refusal_log;
-#define REFUSED(cond)                                    \
-    do {                                                 \
-        CHECK(cond);                                     \
-        g_refusal_log.push_back(lr_last_error_string()); \
-    } while (0)
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
-static const uint64_t Qm[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 1099516280833ull};
 static const int MAXB = 5;
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
-
-struct Rings {
-    lr_context *q = nullptr, *p = nullptr;
-    int nq, np;
-    Rings(uint64_t N, int nq_, int np_, const lr_options *opt) : nq(nq_), np(np_) {
-        OK(opt ? lr_context_create_ex(N, Qm, nq, 0, opt, &q) : lr_context_create(N, Qm, nq, 0, &q));
-        OK(opt ? lr_context_create_ex(N, Qm + nq, np, 0, opt, &p) : lr_context_create(N, Qm + nq, np, 0, &p));
-    }
-    ~Rings() {
-        OK(lr_context_destroy(p));
-        OK(lr_context_destroy(q));
-    }
-};
 
 // one key generator through every entry point; returns the number of accepted calls
 // max_keys above kKeygenKeysPerLaunch (32): the call runs as several passes over the pool, each with its own offsets into the bytes, the
 // secret keys, the Galois elements and the key array
 static int exercise(uint64_t N, int nq, int np, const lr_options *opt, int max_keys = MAXB) {
-    Rings r(N, nq, np, opt);
+    Rings r(N, Qm, nq, np, opt);
     const int rows = nq + np, beta = (nq + np - 1) / np;
     lr_keygen *kg = nullptr;
     OK(opt ? lr_keygen_create_ex(r.q, r.p, max_keys, opt, &kg) : lr_keygen_create(r.q, r.p, max_keys, &kg));
@@ -116,7 +76,7 @@ static void sequences() {
         lr_options opt;
         OK(lr_options_init(&opt));
         opt.no_epilogue = call_by_call;
-        Rings r(N, nq, np, &opt);
+        Rings r(N, Qm, nq, np, &opt);
         lr_keygen *kg = nullptr;
         OK(lr_keygen_create_ex(r.q, r.p, n, &opt, &kg));
         lr_poly *sk = poly(r.q, nq + np, 1), *pk0 = poly(r.q, nq + np, 1), *pk1 = poly(r.q, nq + np, 1);
@@ -162,7 +122,7 @@ static int refusals() {
     const uint64_t N = 16;
     const int nq = 3, np = 1, rows = 4, beta = 3;
     int count = 0;
-    Rings r(N, nq, np, nullptr), other(N, nq, np, nullptr);
+    Rings r(N, Qm, nq, np, nullptr), other(N, Qm, nq, np, nullptr);
     lr_context *small = nullptr, *big = nullptr, *dev1 = nullptr;
     OK(lr_context_create(4, Qm, nq, 0, &small));
     OK(lr_context_create(2 * N, Qm + nq, np, 0, &big));
@@ -313,11 +273,5 @@ int main() {
         b.join();
         calls += threaded.load();
     }
-    CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
-    CHECK((int)g_refusal_log.size() == refused);
-    std::printf("refusal messages begin\n");
-    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
-    std::printf("refusal messages end\n");
-    std::printf("keygen: calls %d, refusals %d, failures %d\n", calls, refused, g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS | EVENTS | LOG, refused, "keygen: calls %d, refusals %d", calls, refused);
 }

@@ -35,31 +35,10 @@
 
 #include <sys/mman.h>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
-
-namespace lr {
-extern std::atomic<unsigned long long> g_stub_launches;
-}
-
-static int g_fail = 0, g_calls = 0, g_refusals = 0;
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-// a refusal: the code, and no launch
-#define REFUSED(x, code)                                                   \
-    do {                                                                   \
-        const unsigned long long before_ = lr::g_stub_launches.load();     \
-        CHECK((x) == (code));                                              \
-        CHECK(lr::g_stub_launches.load() == before_);                      \
-        ++g_refusals;                                                      \
-    } while (0)
+// a call that went through: ran() below
+#define RUN(x) do { const unsigned long long b_ = lr::g_stub_launches.load(); ran(C, (x), b_, false); } while (0)
+#define NTT(x) do { const unsigned long long b_ = lr::g_stub_launches.load(); ran(C, (x), b_, true); } while (0)
+#include "driver_check.hpp"
 
 static const uint64_t Q60[5] = {1152921504606584833ull, 1152921504598720513ull, 1152921504592429057ull, 1152921504581419009ull, 1152921504580894721ull};
 static const uint64_t Q61[2] = {1152921504614055937ull, 1152921504615628801ull};
@@ -121,14 +100,6 @@ static void ran(Config &C, int rc, unsigned long long before, bool plain_transfo
     if (s.empty()) return;
     if (plain_transform) s += "x" + std::to_string(launches);
     C.names.insert(s);
-}
-#define RUN(x) do { const unsigned long long b_ = lr::g_stub_launches.load(); ran(C, (x), b_, false); } while (0)
-#define NTT(x) do { const unsigned long long b_ = lr::g_stub_launches.load(); ran(C, (x), b_, true); } while (0)
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
 }
 
 static void transforms(Config &C, int batch) {
@@ -393,7 +364,5 @@ int main(int argc, char **argv) {
         for (int logn : kLogN)
             for (int v : {0, 1, 13, 8, 9}) run_config(logn, m, v);
     }
-    CHECK(hipstub_live_allocations() == 0);
-    std::printf("ntt_dispatch: calls %d, refusals %d, failures %d\n", g_calls, g_refusals, g_fail);
-    return g_fail ? 1 : 0;
+    return driver_end(ALLOCATIONS, g_refusals, "ntt_dispatch: calls %d, refusals %d", g_calls.load(), g_refusals.load());
 }

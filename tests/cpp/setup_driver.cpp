@@ -1,11 +1,10 @@
-// The collective setup's host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_setup_sanitizers.py): the
-// REAL host code -- lr_setup.cpp with lr_abi_*.cpp, lr_host.hpp, lr_qp_handle.hpp, lr_precompute.cpp -- compiled with g++ against the
-// host-only HIP stand-in, the recording launch stubs of tests/cpp/hipstub/ and the stand-ins of the handle's own launchers
-// (setup_stub.cpp, ckks_encryptor_stub.cpp, collective_stub.cpp), which touch the first and the last byte of everything a kernel would
-// read or write.  Every entry point in its host and device-pointer form, both shapes (lr_options::no_epilogue), 1, 3 and max_batch
-// parties (5, and 70: more than one pass) with the pool and the staging buffer reused across consecutive host-form calls, wide polys,
-// shared and per-party keys, |P| = 1 and a ragged |P| = 2 whose last digit owns one row; two handles on two threads; the launch counts of
-// both shapes; every refusal a context can be made for (N > 2^30 has none: include/lattigo_ring.h).
+// The collective setup's host side under AddressSanitizer + UBSan and under ThreadSanitizer (tests/test_host_setup_sanitizers.py): the REAL
+// host code -- lr_setup.cpp with every other host unit of the library -- compiled with g++ against the host-only HIP stand-in and the
+// launch stand-ins of tests/cpp/hipstub/, which touch the first and the last byte of everything a kernel would read or write.  Every entry
+// point in its host and device-pointer form, both shapes (lr_options::no_epilogue), 1, 3 and max_batch parties (5, and 70: more than one
+// pass) with the pool and the staging buffer reused across consecutive host-form calls, wide polys, shared and per-party keys, |P| = 1 and
+// a ragged |P| = 2 whose last digit owns one row; two handles on two threads; the launch counts of both shapes; every refusal a context can
+// be made for (N > 2^30 has none: include/lattigo_ring.h).
 // Exit code 0 = every check held; a sanitizer report aborts the run.  Nothing here computes: parity is the GPU suite's business.
 #include <atomic>
 #include <cstdint>
@@ -15,70 +14,21 @@
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "lattigo_ring.h"
+#define REFUSED REFUSED_MSG      // here a refusal is logged with its message
+#include "driver_check.hpp"
 
 namespace lr {
 extern std::atomic<unsigned long long> g_stub_launches, g_ckks_expand_launches, g_fold_launches, g_setup_ckg_launches, g_setup_share_launches,
     g_setup_key_launches;
 }  // namespace lr
 
-static std::atomic<int> g_fail{0};
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #cond, __LINE__, lr_last_error_string()); \
-            ++g_fail;                                                                                            \
-        }                                                                                                        \
-    } while (0)
-#define OK(x) CHECK((x) == LR_OK)
-// a refused call: the code as CHECK sees it, and the message its caller reads goes to the log that main prints (tests/cpp/expected/)
-static std::vector<std::string> g_refusal_log;
-#define REFUSED(cond)                                    \
-    do {                                                 \
-        CHECK(cond);                                     \
-        g_refusal_log.push_back(lr_last_error_string()); \
-    } while (0)
-
-// DefaultParams[PN15QP880]'s first primes (congruent to 1 modulo 2^16)
-static const uint64_t Qm[5] = {1125899908022273ull, 1099512938497ull, 1099514314753ull, 1099515691009ull, 1099516280833ull};
-// 64 primes congruent to 1 modulo 32 from 2^40 up: with one limb of P, one row more than Q||P may hold
-static const uint64_t Q64[64] = {
-    1099511627873ull, 1099511628161ull, 1099511628769ull, 1099511629121ull, 1099511629409ull, 1099511629537ull, 1099511629889ull, 1099511629921ull,
-    1099511630177ull, 1099511630209ull, 1099511630561ull, 1099511630593ull, 1099511630849ull, 1099511631457ull, 1099511631937ull, 1099511632993ull,
-    1099511633153ull, 1099511633377ull, 1099511634017ull, 1099511634113ull, 1099511635009ull, 1099511635361ull, 1099511636129ull, 1099511636161ull,
-    1099511636833ull, 1099511637857ull, 1099511638177ull, 1099511638241ull, 1099511638529ull, 1099511638817ull, 1099511639297ull, 1099511639393ull,
-    1099511639713ull, 1099511640001ull, 1099511641153ull, 1099511641729ull, 1099511641889ull, 1099511642209ull, 1099511642401ull, 1099511643137ull,
-    1099511643521ull, 1099511643617ull, 1099511644321ull, 1099511646017ull, 1099511646241ull, 1099511646433ull, 1099511646529ull, 1099511646721ull,
-    1099511647009ull, 1099511647841ull, 1099511647873ull, 1099511648513ull, 1099511649121ull, 1099511649409ull, 1099511649473ull, 1099511649793ull,
-    1099511651009ull, 1099511651041ull, 1099511651137ull, 1099511651297ull, 1099511652257ull, 1099511652769ull, 1099511652929ull, 1099511653249ull};
 static const int MAXB = 5;
 static const int ENTRY_POINTS = 20;      // accepted calls per party count in exercise(): 14 share calls, 3 finalize steps, 3 folds
-
-static lr_poly *poly(lr_context *ctx, int limbs, int batch) {
-    lr_poly *p = nullptr;
-    OK(lr_poly_alloc(ctx, limbs, batch, &p));
-    return p;
-}
-
-struct Rings {
-    lr_context *q = nullptr, *p = nullptr;
-    int nq, np;
-    Rings(uint64_t N, int nq_, int np_, const lr_options *opt) : nq(nq_), np(np_) {
-        OK(opt ? lr_context_create_ex(N, Qm, nq, 0, opt, &q) : lr_context_create(N, Qm, nq, 0, &q));
-        OK(opt ? lr_context_create_ex(N, Qm + nq, np, 0, opt, &p) : lr_context_create(N, Qm + nq, np, 0, &p));
-    }
-    ~Rings() {
-        OK(lr_context_destroy(p));
-        OK(lr_context_destroy(q));
-    }
-};
 
 // one handle through every entry point; returns the number of accepted calls.  max_n above kSetupPartiesPerLaunch (32): a call runs as
 // several passes over the pool, each with its own offsets into the bytes, the keys, the Galois elements and the share array
 static int exercise(uint64_t N, int nq, int np, const lr_options *opt, int max_n = MAXB) {
-    Rings r(N, nq, np, opt);
+    Rings r(N, Qm, nq, np, opt);
     const int rows = nq + np, beta = (nq + np - 1) / np;
     lr_setup *s = nullptr;
     OK(opt ? lr_setup_create_ex(r.q, r.p, max_n, opt, &s) : lr_setup_create(r.q, r.p, max_n, &s));
@@ -150,7 +100,7 @@ static void sequences() {
         lr_options opt;
         OK(lr_options_init(&opt));
         opt.no_epilogue = call_by_call;
-        Rings r(N, nq, np, &opt);
+        Rings r(N, Qm, nq, np, &opt);
         lr_setup *s = nullptr;
         OK(lr_setup_create_ex(r.q, r.p, n, &opt, &s));
         lr_poly *sk = poly(r.q, rows, n), *u = poly(r.q, rows, n), *sk1 = poly(r.q, rows, 1), *crs = poly(r.q, rows, 1), *crp = poly(r.q, rows, beta);
@@ -230,7 +180,7 @@ static void sequences() {
 static int refusals() {
     const uint64_t N = 16;
     const int nq = 3, np = 1, rows = 4, beta = 3;
-    Rings r(N, nq, np, nullptr), other(N, nq, np, nullptr);
+    Rings r(N, Qm, nq, np, nullptr), other(N, Qm, nq, np, nullptr);
     lr_context *small = nullptr, *big = nullptr, *dev1 = nullptr;
     OK(lr_context_create(4, Qm, nq, 0, &small));
     OK(lr_context_create(2 * N, Qm + nq, np, 0, &big));
@@ -453,11 +403,5 @@ int main() {
         b.join();
         calls += threaded.load();
     }
-    CHECK(hipstub_live_allocations() == 0 && hipstub_live_events() == 0);
-    CHECK((int)g_refusal_log.size() == refused);
-    std::printf("refusal messages begin\n");
-    for (const std::string &m : g_refusal_log) std::printf("%s\n", m.c_str());
-    std::printf("refusal messages end\n");
-    std::printf("setup: calls %d, refusals %d, failures %d\n", calls, refused, g_fail.load());
-    return g_fail.load() ? 1 : 0;
+    return driver_end(ALLOCATIONS | EVENTS | LOG, refused, "setup: calls %d, refusals %d", calls, refused);
 }

@@ -5,27 +5,15 @@ tests/cpp/bfv_chain_driver.cpp: lr_bfv_inner_sum and lr_bfv_rotate_chain on both
 batches 1, 2 and max_batch, every aliasing the header allows, first calls on fresh plans, the launch counts of each route, two plans on
 two threads, and every refusal.  The stand-in of the new launcher touches the first and the last word of every row the kernel would read
 or write, so a wrong pool size, stride or pair is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver
+from host_stub_build import SANITIZERS, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_bfv_chain_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "bfv_chain_driver", flags, tag)
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the routes, not the caller's env
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
-    steps = int(res.stdout.split("step launches ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "bfv_chain_driver", tag, flags, env)
+    steps = int(stdout.split("step launches ")[1].split(",")[0])
     # 5 degrees x 3 option sets x (3 batches x 38 calls + 6 first calls) and 2 threads x 2 batches x 38 calls
-    assert calls == 5 * 3 * (3 * 38 + 6) + 2 * 2 * 38, res.stdout
-    assert refusals > 5 * 3 * 30 and steps > 0, res.stdout
+    assert calls == 5 * 3 * (3 * 38 + 6) + 2 * 2 * 38, stdout
+    assert refusals > 5 * 3 * 30 and steps > 0, stdout

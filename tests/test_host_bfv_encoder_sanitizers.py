@@ -2,21 +2,10 @@
 buffer, the named stages of both routes) under AddressSanitizer + UBSan (CPU build only), driven by tests/cpp/bfv_encoder_driver.cpp: both
 routes, batches 1, 3 and max_batch, n_values 0, 1 and N, host-value and device-pointer entry points, and every refusal.  The stubs touch the
 first and the last word of everything a kernel would read or write, so a wrong buffer size, stride or batch count is a sanitizer report."""
-import os
-import subprocess
-
-from host_stub_build import build_host_driver
+from host_stub_build import ASAN_UBSAN, run_host_driver
 
 
 def test_bfv_encoder_host_side_under_asan_ubsan(tmp_path):
-    exe = build_host_driver(str(tmp_path), "bfv_encoder_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan", units=["lr_bfv_encoder"],
-                            stubs=["bfv_encoder_stub"])
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the routes, not the caller's env
-    env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "bfv_encoder_driver", *ASAN_UBSAN)
     # 7 encoders (2 degrees x 3 routes, and N = 2^4) x 3 batches x 3 n_values x 8 entry-point calls; 6 refusals at creation and 22 at the calls
-    assert calls == 7 * 3 * 3 * 8 and refusals == 28, res.stdout
+    assert calls == 7 * 3 * 3 * 8 and refusals == 28, stdout

@@ -6,29 +6,18 @@ two option sets, three max_batch values, ten schedules, outputs of exactly level
 counts of each route, two plans on two threads, and every refusal.  The stand-in of its launcher (tests/cpp/hipstub/stub_launch.cpp)
 touches the first and the last word of every row and table entry the kernel would read or write, so a wrong pool size, stride, level or
 table offset is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver
+from host_stub_build import SANITIZERS, number, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_ckks_basis_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_basis_driver", flags, tag)
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the routes, not the caller's env
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    number = lambda what: int(res.stdout.split(what + " ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "ckks_basis_driver", tag, flags, env)
     # per ring and option set: 3 max_batch values x (10 schedules + 1 at batch 1) x 2 output sizes, 2 calls at batch 8, the accepted call among the
     # refusals, 3 first calls x 2 x 2; on the merged route (3 rings, default options) the MulRelin calls and the call of the launch
     # count: 3 + 2 + 2 chunks and one call per max_batch; 2 threads x 10 schedules x 2
-    assert number("calls") == 4 * 2 * (3 * 11 * 2 + 2 + 1 + 3 * 2 * 2) + 3 * (3 + 2 + 2 + 3) + 2 * 10 * 2, res.stdout
-    assert number("refusals") == 4 * 2 * 52, res.stdout
-    assert number("tail launches") > 0 and number("combine launches") > 0, res.stdout
-    assert number("tail products") > number("tail launches"), res.stdout           # chunks of more than one product ran
+    assert calls == 4 * 2 * (3 * 11 * 2 + 2 + 1 + 3 * 2 * 2) + 3 * (3 + 2 + 2 + 3) + 2 * 10 * 2, stdout
+    assert refusals == 4 * 2 * 52, stdout
+    assert number(stdout, "tail launches") > 0 and number(stdout, "combine launches") > 0, stdout
+    assert number(stdout, "tail products") > number(stdout, "tail launches"), stdout           # chunks of more than one product ran

@@ -6,31 +6,19 @@ degrees, three option sets, levels 0, 2 and the top, batches 1, 2 and max_batch,
 different strides, first calls on fresh plans, the launch counts of each route, two plans on two threads, and every refusal.  The stand-in
 of its launcher (tests/cpp/hipstub/stub_launch.cpp) touches the first and the last word of every row the kernel would read or write, so a
 wrong pool size, stride or level is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver
+from host_stub_build import SANITIZERS, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_ckks_chain_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_chain_driver", flags, tag)
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the plans' options decide the routes, not the caller's env
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
-    steps = int(res.stdout.split("step launches ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "ckks_chain_driver", tag, flags, env)
+    steps = int(stdout.split("step launches ")[1].split(",")[0])
     # 4 degrees x 3 option sets x (3 levels x 3 batches x 48 calls + 1 accepted call among the refusals + 6 first calls) and
     # 2 threads x 2 batches x 48 calls
-    assert calls == 4 * 3 * (3 * 3 * 48 + 1 + 6) + 2 * 2 * 48, res.stdout
-    assert refusals == 4 * 3 * 24, res.stdout
+    assert calls == 4 * 3 * (3 * 3 * 48 + 1 + 6) + 2 * 2 * 48, stdout
+    assert refusals == 4 * 3 * 24, stdout
     # the fused route (accumulating chains; three degrees, two option sets): per level and batch 6 aliasings x (0 + 1 + 2 + 3) steps, the
     # accepted call's 2 and the first calls' 2 x (3 + 1); and the thread at N = 2^12
-    assert steps == 3 * 2 * (3 * 3 * 6 * 6 + 2 + 2 * 4) + 2 * 6 * 6, res.stdout
+    assert steps == 3 * 2 * (3 * 3 * 6 * 6 + 2 + 2 * 4) + 2 * 6 * 6, stdout

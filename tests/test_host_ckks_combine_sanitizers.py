@@ -5,29 +5,16 @@ every degree pair with b present and absent and every flag combination, batches 
 limb count, members that lie apart by more than their limbs, the receiver fresh, a, b and both; every refusal with the message its caller
 reads and no launch; the constants function on two threads.  The stub keeps every launch and touches the first and the last word of every
 row a kernel would read or write, so a wrong stride, level, degree or batch is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver, expected_refusals, refusal_messages
+from host_stub_build import SANITIZERS, expected_refusals, refusal_messages, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_ckks_combine_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_combine_driver", flags, tag)
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    print(res.stdout)
-    assert res.returncode == 0, (res.stdout[-3000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    assert refusal_messages(res.stdout) == expected_refusals("ckks_combine_driver")       # the texts that reach the callers, message for message
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    launches = int(res.stdout.split("launches ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "ckks_combine_driver", tag, flags, env)
+    assert refusal_messages(stdout) == expected_refusals("ckks_combine_driver")       # the texts that reach the callers, message for message
+    launches = int(stdout.split("launches ")[1].split(",")[0])
     # 3 x 4 degree pairs x 16 flag combinations, 4 x 7 calls on a receiver that is an operand and one at N = 2^12: one launch each, and the
     # two accepted calls among the refusals; 24 + 3 + 9 + 1 refusals of the device call, 10 of the constants
-    assert calls == 221 and launches == 223 and refusals == 47, res.stdout
+    assert calls == 221 and launches == 223 and refusals == 47, stdout

@@ -5,33 +5,20 @@ tests/cpp/ckks_lincomb_driver.cpp: 0, 1, 16, 17 and 33 terms with and without th
 1 and 3, a level below the polys' limb count, members that lie apart by more than their limbs, a term listed twice; every refusal with the
 message its caller reads and no launch; the constants function on two threads.  The stub keeps every launch and touches the first and the
 last word of every row a kernel would read or write, so a wrong stride, level, limb range or term count is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver, expected_refusals, refusal_messages
+from host_stub_build import SANITIZERS, expected_refusals, refusal_messages, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_ckks_lincomb_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "ckks_lincomb_driver", flags, tag)
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    print(res.stdout)
-    assert res.returncode == 0, (res.stdout[-3000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    assert refusal_messages(res.stdout) == expected_refusals("ckks_lincomb_driver")       # the texts that reach the callers, message for message
+    stdout, calls, refusals = run_host_driver(tmp_path, "ckks_lincomb_driver", tag, flags, env)
+    assert refusal_messages(stdout) == expected_refusals("ckks_lincomb_driver")       # the texts that reach the callers, message for message
     # the passes of every split: 0 terms is one pass (the constant, or zeros), none when there is nothing to do; 16 one, 17 two, 33 three
     passes = {}
-    for line in res.stdout.splitlines():
+    for line in stdout.splitlines():
         if line.startswith("split T="):
             passes.setdefault(int(line.split("T=")[1].split()[0]), set()).add(int(line.split(": ")[1].split(" passes")[0]))
     assert passes == {0: {0, 1}, 1: {1}, 16: {1}, 17: {2}, 33: {3}}, passes
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
     # 5 term counts x 4 variants, the call with nothing to do and one at N = 2^12; 18 + 3 + 8 + 2 refusals of the device call, 8 of the constants
-    assert calls == 22 and refusals == 39, res.stdout
+    assert calls == 22 and refusals == 39, stdout

@@ -5,30 +5,16 @@ device-pointer form, the default shape and lr_options::no_epilogue, batches 1, 3
 consecutive host-form calls, every level, |P| = 1 and |P| = 2, 33 shares (a second fold pass) with out aliasing a share and the base, two
 handles on two threads, the launch counts of both shapes, and every refusal.  The stubs touch the first and the last byte of everything a
 kernel would read or write, so a wrong buffer size, stride, level or share count is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver, expected_refusals, refusal_messages
+from host_stub_build import SANITIZERS, expected_refusals, refusal_messages, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_collective_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "collective_driver", flags, tag, units=["lr_collective"],
-                            stubs=["bfv_encryptor_stub", "ckks_encryptor_stub", "collective_stub"])
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the shapes, not the caller's env
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    print(res.stdout)
-    assert res.returncode == 0, (res.stdout[-3000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    assert refusal_messages(res.stdout) == expected_refusals("collective_driver")       # the texts that reach the callers, message for message
-    assert res.stdout.count("launches ") == 2 * (1 + 7), res.stdout               # the ModDowns and seven calls, in both shapes
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "collective_driver", tag, flags, env)
+    assert refusal_messages(stdout) == expected_refusals("collective_driver")       # the texts that reach the callers, message for message
+    assert stdout.count("launches ") == 2 * (1 + 7), stdout               # the ModDowns and seven calls, in both shapes
     # 8 runs (2 degrees x 2, 2 more at N = 16, and 2 on threads) x 2 rounds x 3 batches x 12 calls (8 share forms, 4 folds);
     # 9 refusals at creation, 69 at the calls
-    assert calls == 8 * 2 * 3 * 12 and refusals == 78, res.stdout
+    assert calls == 8 * 2 * 3 * 12 and refusals == 78, stdout

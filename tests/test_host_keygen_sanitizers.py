@@ -4,28 +4,15 @@ only), driven by tests/cpp/keygen_driver.cpp: every entry point in its host and 
 lr_options::no_epilogue, 1, 3 and max_batch keys (5, and 70: three passes of at most 32 keys) with pool and staging reuse across consecutive host-form calls, |P| = 1 and a ragged
 |P| = 2, two handles on two threads, the launch counts of both shapes, and every refusal.  The stubs touch the first and the last byte of
 everything a kernel would read or write, so a wrong buffer size, stride, digit or key count is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver, expected_refusals, refusal_messages
+from host_stub_build import SANITIZERS, expected_refusals, refusal_messages, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_keygen_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "keygen_driver", flags, tag, units=["lr_keygen"],
-                            stubs=["bfv_encryptor_stub", "ckks_encryptor_stub", "keygen_stub"])
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the shapes, not the caller's env
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    assert refusal_messages(res.stdout) == expected_refusals("keygen_driver")       # the texts that reach the callers, message for message
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "keygen_driver", tag, flags, env)
+    assert refusal_messages(stdout) == expected_refusals("keygen_driver")       # the texts that reach the callers, message for message
     # 10 runs (2 degrees x 2, 2 more at N = 16, 2 with 70 keys, and 2 on threads) x 2 rounds x 3 key counts x 5 entry points x 2 forms;
     # 8 refusals at creation, 58 at the calls
-    assert calls == 10 * 2 * 3 * 10 and refusals == 66, res.stdout
+    assert calls == 10 * 2 * 3 * 10 and refusals == 66, stdout

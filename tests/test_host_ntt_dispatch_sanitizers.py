@@ -9,11 +9,10 @@ After those, the modulus classes at the limits of the admission bounds (tests/li
 above and just below 2^33) under the options that move them between the assembly variants, the FP64 body and the C++ kernels: the variants
 the contexts report must be the ones the Python restatement of the predicates gives, and the kernel names are pinned by the same golden."""
 import os
-import subprocess
 
 import limit_moduli as lm
 from conftest import ROOT
-from host_stub_build import build_host_driver
+from host_stub_build import ASAN_UBSAN, run_host_driver
 
 # five primes = 1 mod 2^17 per class (NTT-friendly for every ring of the driver)
 LIMIT_CLASSES = {"61-": lm.below(61, 16, 5), "57-": lm.below(57, 16, 5), "57+": lm.above(57, 16, 5), "33+": lm.above(33, 16, 5),
@@ -38,23 +37,16 @@ ROUTE_WITNESSES = {
 
 
 def test_ntt_dispatch_host_side_under_asan_ubsan(tmp_path):
-    exe = build_host_driver(str(tmp_path), "ntt_dispatch_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan")
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the contexts' options decide the routes, not the caller's env
-    env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     args = [str(a) for name, qs in LIMIT_CLASSES.items() for a in [name] + qs]
-    res = subprocess.run([exe] + args, capture_output=True, text=True, timeout=1500, env=env)
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout[-2000:]
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "ntt_dispatch_driver", *ASAN_UBSAN, args=args, timeout=1500)
     # 5 rings x 4 moduli sets x 10 option sets, one more option set at N = 2^14 and three more at N = 2^15
     # ... and the five limit classes x 5 rings x 5 option sets
     configs = 4 * (5 * 10 + 1 + 3) + len(LIMIT_CLASSES) * 5 * len(LIMIT_OPTIONS)
     # per batch (1 and 3): 18 + 10 transforms, 4 x 5 + 2 x 5 divisions, 3 x 3 rescales of a ciphertext, 3 x 3 ModDowns, 4 x 3 monomial products,
     # 3 x 4 permutations, 2 key switches; the six host-slice transforms at batch 1 only; the three calls of the chunked launch once
-    assert calls == configs * (2 * (28 + 30 + 9 + 9 + 12 + 12 + 2) + 6) + 3, res.stdout[-300:]
-    assert refusals == configs * REFUSALS_PER_CONFIG, res.stdout[-300:]
-    got = [ln for ln in res.stdout.splitlines() if ln.startswith("routes ")]
+    assert calls == configs * (2 * (28 + 30 + 9 + 9 + 12 + 12 + 2) + 6) + 3, stdout[-300:]
+    assert refusals == configs * REFUSALS_PER_CONFIG, stdout[-300:]
+    got = [ln for ln in stdout.splitlines() if ln.startswith("routes ")]
     want = open(os.path.join(ROOT, "tests", "golden", "ntt_dispatch_routes.txt")).read().splitlines()
     assert len(got) == configs
     for g, w in zip(got, want):

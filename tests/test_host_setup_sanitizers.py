@@ -5,28 +5,15 @@ default shape and lr_options::no_epilogue, 1, 3 and max_batch parties (5, and 70
 staging reuse across consecutive host-form calls, |P| = 1 and a ragged |P| = 2, two handles on two threads, the launch counts of both
 shapes, and every refusal.  The stubs touch the first and the last byte of everything a kernel would read or write, so a wrong buffer
 size, stride, digit or party count is a sanitizer report."""
-import os
-import subprocess
-
 import pytest
 
-from host_stub_build import build_host_driver, expected_refusals, refusal_messages
+from host_stub_build import SANITIZERS, expected_refusals, refusal_messages, run_host_driver
 
 
-@pytest.mark.parametrize("tag,flags,env", [
-    ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}),
-    ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"}),
-])
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_setup_host_side_under_sanitizers(tmp_path, tag, flags, env):
-    exe = build_host_driver(str(tmp_path), "setup_driver", flags, tag, units=["lr_setup"],
-                            stubs=["bfv_encryptor_stub", "ckks_encryptor_stub", "collective_stub", "setup_stub"])
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}       # the handles' options decide the shapes, not the caller's env
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(clean, **env))
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-6000:])
-    assert "failures 0" in res.stdout, res.stdout
-    assert refusal_messages(res.stdout) == expected_refusals("setup_driver")        # the texts that reach the callers, message for message
-    calls = int(res.stdout.split("calls ")[1].split(",")[0])
-    refusals = int(res.stdout.split("refusals ")[1].split(",")[0])
+    stdout, calls, refusals = run_host_driver(tmp_path, "setup_driver", tag, flags, env)
+    assert refusal_messages(stdout) == expected_refusals("setup_driver")        # the texts that reach the callers, message for message
     # 10 runs (2 degrees x 2, 2 more at N = 16, 2 with 70 parties, and 2 on threads) x 2 rounds x 3 party counts x 20 accepted calls
     # (14 share calls, 3 finalize steps, 3 folds); 9 refusals at creation (the 64-limb LR_ERR_UNSUPPORTED among them), 109 at the calls
-    assert calls == 10 * 2 * 3 * 20 and refusals == 118, res.stdout
+    assert calls == 10 * 2 * 3 * 20 and refusals == 118, stdout

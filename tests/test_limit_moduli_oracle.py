@@ -367,22 +367,15 @@ def test_host_admission_predicates_are_the_restated_ones(tmp_path):
     keymac_wide_ok (lr_abi_ckks.cpp) for every extension and key-switch admission set, and the recording launch stubs hand back what the
     launch structs carried; limit_moduli's Python restatement must say the same, on both sides of every bound.  (This is where a changed
     bound shows without a device: the sets are chosen so that one term more or less flips the value.)"""
-    import os
-    import subprocess
-
-    from host_stub_build import build_host_driver
-    exe = build_host_driver(str(tmp_path), "admission_driver", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "asan_ubsan")
+    from host_stub_build import ASAN_UBSAN, run_host_driver
     logn = 12
     sets = [s for s in lm.admission_sets(logn).values() if s.kind in ("ext", "keymac")]
     args = []
     for s in sets:
         args += [s.kind, s.name, logn, len(s.moduli), len(s.P)] + ([s.terms] if s.kind == "ext" else []) + s.moduli + s.P
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LR_")}
-    env = dict(clean, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    res = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=300, env=env)
-    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
+    stdout, _, _ = run_host_driver(tmp_path, "admission_driver", *ASAN_UBSAN, args=args, timeout=300, summary=False)      # (it prints no summary line)
     got = {}
-    for ln in res.stdout.splitlines():
+    for ln in stdout.splitlines():
         f = ln.split()
         got[(f[1], f[2])] = [int(v) for v in f[3:]]
     for s in sets:
